@@ -1,7 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- streamline-steps/s of the MI355X environment step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows M] [--legs ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--windows M] [--legs ...] [--no-cpu-baseline] ...
+
+A plain run measures the headline and nothing else: it sets up, runs W
+warm-up steps, times ONE window of exactly K steps (no kernel events inside
+it), writes the outputs of the last timed step if --dump-outputs is given and
+prints the JSON line (`value`, `ms_per_step` of that window).  Everything else
+described below -- the legs other than `weak`, the windows beyond the first,
+the kernel events and the `roofline` object, the per-kernel breakdown, the
+whole episode, the collate, the CPU baseline -- runs with --full only (then as
+described, 11 windows by default).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path handed
+its caller after its last step, as DIR/<name>.npy (float32 / float64, about
+25 MB; `dump_outputs`), in streamline order so that two builds can be compared
+array by array: the inputs (volume, seeds, scripted actions) are seeded and the
+same from run to run for the same arguments.
 
 Headline workload (BASELINE.json configs[1]): "env.step only" on
 a synthetic 96^3 x 45-SH volume, n_actor = 262144 streamlines per GPU, ball
@@ -13,13 +29,14 @@ One "step" = one pass of the hot path over the batch: scripted actions ->
 env.step_device() -> env.harvest().  A streamline-step = one active
 streamline advanced by one step (the reference's `t += n_active`,
 TrackToLearn/algorithms/ddpg.py:219).  W warm-up steps run on their own
-episode; then M windows (default 11) of EXACTLY K steps each are timed, every
-window bracketed by barrier + torch.cuda.synchronize() on both sides and
-started from a fresh (untimed) reset, so all windows time the same K steps.
-`value` / `ms_per_step` are those of the MEDIAN window (max over ranks per
-window); min / max over the windows are printed next to them (`windows`).
-Every fourth window also brackets the dominant kernel with HIP events (for
-`roofline`); those records cost a few percent, both medians are printed.
+episode; then M windows (1 in a plain run, 11 by default with --full) of
+EXACTLY K steps each are timed, every window bracketed by barrier +
+torch.cuda.synchronize() on both sides and started from a fresh (untimed)
+reset, so all windows time the same K steps.  `value` / `ms_per_step` are
+those of the MEDIAN window (max over ranks per window); min / max over the
+windows are printed next to them (`windows`).  With --full every fourth
+window also brackets the dominant kernel with HIP events (for `roofline`);
+those records cost a few percent, both medians are printed.
 
 With N > 1 the driver launches one process per GPU (torch.distributed.run);
 called bare with --gpus N > 1 this script launches those N ranks itself (as
@@ -29,8 +46,8 @@ collective on the step path.  The one exchange the path has -- collating
 finished tracts on rank 0 (exact-size gather to root over RCCL) -- is timed
 as `collate_ms`.
 
-Legs (all of them by default; `--legs weak,hbm` etc. restricts, which is how
-the rocprofv3 passes under profiles/ look at one workload at a time):
+Legs of a --full run (all of them by default; `--legs weak,hbm` etc. restricts,
+which is how the rocprofv3 passes under profiles/ look at one workload at a time):
 
   weak     the headline: 262144 streamlines PER GPU ("scaling": "weak").
            -> `value`, `windows`, `roofline`, `whole_episode`, `collate_ms`.
@@ -80,7 +97,7 @@ the rocprofv3 passes under profiles/ look at one workload at a time):
            GPU's shard of config 4 at N = 8 (131072 streamlines on the 145^3
            volume).  -> `roofline_hbm_regime` (rank 0's kernel times).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   roofline     dominant kernel (k_state_dd: 7-point SH gather + state row
                write).  `achieved` = HBM bytes the kernel moves per launch /
                its average launch duration (HIP events on the launch stream,
@@ -423,11 +440,14 @@ class Dist:
         return t.cpu().numpy()
 
 
-def timed_windows(env, rows, steps, warmup, n_win, seed, grp, host_contract=False):
+def timed_windows(env, rows, steps, warmup, n_win, seed, grp, host_contract=False,
+                  events=True, after_last=None):
     """`warmup` untimed steps, then `n_win` windows of exactly `steps` steps,
     each from a fresh untimed reset and bracketed by barrier + synchronize.
     Returns a dict: per-window wall times (max over ranks), streamline-steps of
-    one window (sum over ranks), the dominant kernel's event time on THIS rank."""
+    one window (sum over ranks), the dominant kernel's event time on THIS rank
+    (`events`: every fourth window bracketed; none without).  `after_last(state)`
+    is called, untimed, with what the last step of the last window returned."""
     import torch
     counter = {'state': env.reset(0, rows), 'step': 0, 'resets': 0}
     run_steps(env, warmup, seed, counter, rows, host_contract)
@@ -445,7 +465,7 @@ def timed_windows(env, rows, steps, warmup, n_win, seed, grp, host_contract=Fals
     state_ms, state_n, evented = 0.0, 0, []
     for w in range(n_win):
         counter = {'state': env.reset(0, rows), 'step': 0, 'resets': 0}
-        with_events = (w % 4 == 1) or n_win == 1
+        with_events = events and ((w % 4 == 1) or n_win == 1)
         if with_events:
             env.profile_begin(max_launches=steps + 8, classes=('state',))
         grp.barrier()
@@ -461,6 +481,8 @@ def timed_windows(env, rows, steps, warmup, n_win, seed, grp, host_contract=Fals
             state_ms += ms
             state_n += cnt
             evented.append(w)
+    if after_last is not None:
+        after_last(counter['state'])
     t_all = grp.reduce(times, 'max')            # per window, max over the ranks
     total_units = float(grp.reduce([n_units], 'sum')[0])     # of ONE window, all ranks
     t_sorted = np.sort(t_all)
@@ -487,6 +509,56 @@ def timed_windows(env, rows, steps, warmup, n_win, seed, grp, host_contract=Fals
     }
 
 
+#: streamlines whose state row and history `dump_outputs` writes (fixed, seeded sample)
+DUMP_SAMPLE = 4096
+
+
+def dump_outputs(env, state, out_dir, sample=DUMP_SAMPLE):
+    """What the timed path handed its caller after its last step, as
+    out_dir/<name>.npy, indexed by streamline (the row order of the library's
+    processing order is not part of the result):
+
+      lengths, flags, dones   (n,) float32: per streamline of the batch
+      head                    (n, 3) float32: its last point (voxel space)
+      sample_ids              (s,) float64: a fixed, seeded sample of the n
+      state                   (s, width): the state row `harvest()` returned for
+                              each of them, zeros once a streamline stopped
+      history                 (s, max_nb_steps + 1, 3) float32: its points,
+                              zeros past its length
+      n_active                (1,) float64: streamlines still being tracked
+
+    With 262144 streamlines and s = 4096 that is about 25 MB."""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    n, n_act = env._n_total, env._n_active
+    assert state.shape[0] == n_act, (state.shape, n_act)
+    dev = state.device
+    lengths = env._buf_lengths[:n].long()
+    hist = env._buf_streamlines[:n]
+    ids_np = np.sort(np.random.RandomState(0).choice(n, min(sample, n), replace=False))
+    ids = torch.from_numpy(ids_np).to(dev)
+    # state row i belongs to streamline continue_idx[i]
+    row_of = torch.full((n,), -1, dtype=torch.long, device=dev)
+    row_of[env._idx_view(n_act).long()] = torch.arange(n_act, device=dev)
+    rows = row_of[ids]
+    live = (rows >= 0)[:, None]
+    zero = torch.zeros((), dtype=state.dtype, device=dev)
+    st = torch.where(live, state[rows.clamp(min=0)], zero)
+    pts = hist[ids]
+    inside = torch.arange(pts.shape[1], device=dev)[None, :] < lengths[ids][:, None]
+    pts = torch.where(inside[..., None], pts, zero.to(pts.dtype))
+    head = hist[torch.arange(n, device=dev), (lengths - 1).clamp(0, hist.shape[1] - 1)]
+    arrays = {
+        'lengths': lengths.float(), 'flags': env._buf_flags[:n].float(),
+        'dones': env._buf_dones[:n].float(), 'head': head, 'sample_ids': ids.double(),
+        'state': st, 'history': pts,
+        'n_active': torch.tensor([float(n_act)], dtype=torch.float64),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy())
+
+
 def pipelined_windows(subject, device, seeds, parts, steps, warmup, n_win, seed, grp):
     """`parts` envs over the same volumes, each with 1/parts of the seeds and a
     HIP stream of its own, stepped alternately: windows of exactly `steps` steps
@@ -501,18 +573,23 @@ def pipelined_windows(subject, device, seeds, parts, steps, warmup, n_win, seed,
         streams.append(torch.cuda.Stream())
 
     def window(n_steps):
-        states = []
+        states, ep_step = [], [0] * parts
         for env, s in zip(envs, streams):
             with torch.cuda.stream(s):
                 states.append(env.reset(0, rows))
         grp.barrier()
         torch.cuda.synchronize()
         total, t0 = 0, time.perf_counter()
-        for step in range(n_steps):
+        for _ in range(n_steps):
             for k, (env, s) in enumerate(zip(envs, streams)):
                 with torch.cuda.stream(s):
+                    if env._n_active == 0:
+                        # the part's episode is over: a new one, as run_steps does
+                        states[k] = env.reset(0, rows)
+                        ep_step[k] = 0
                     total += env._n_active
-                    env.step_device(env.scripted_actions(states[k], step, seed, WOBBLE))
+                    env.step_device(env.scripted_actions(states[k], ep_step[k], seed, WOBBLE))
+                    ep_step[k] += 1
             for k, (env, s) in enumerate(zip(envs, streams)):
                 with torch.cuda.stream(s):
                     states[k], _ = env.harvest()
@@ -721,19 +798,32 @@ def main(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=12)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--windows', type=int, default=11,
-                    help='timed windows of --steps steps each (median reported)')
-    ap.add_argument('--legs', default='all',
-                    help='comma list of ' + ','.join(LEGS) + ' (default: all)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='every leg and figure (default: the headline alone, one window)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy')
+    ap.add_argument('--windows', type=int, default=None,
+                    help='timed windows of --steps steps each (median reported; '
+                         'default 1, with --full 11)')
+    ap.add_argument('--legs', default=None,
+                    help='with --full: comma list of ' + ','.join(LEGS) + ' (default: all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full')
     ap.add_argument('--no-whole-episode', action='store_true',
-                    help='skip the episode-to-exhaustion figure (SURVEY 8d (ii))')
+                    help='with --full: skip the episode-to-exhaustion figure (SURVEY 8d (ii))')
     ap.add_argument('--whole-episode', action='store_true',
-                    help='(default now; kept for older command lines)')
+                    help='(default with --full; kept for older command lines)')
     args = ap.parse_args(argv)
-    legs = set(LEGS) if args.legs == 'all' else set(args.legs.split(','))
+    legs = set(LEGS) if args.legs in (None, 'all') else set(args.legs.split(','))
     if not legs <= set(LEGS):
         sys.exit(f'--legs: unknown leg in {sorted(legs)} (known: {LEGS})')
+    if not args.full:
+        if args.legs is not None:
+            sys.exit('--legs chooses among the legs of a --full run')
+        # the headline alone: no CPU baseline, no whole episode, no kernel events
+        legs = {'weak'}
+        args.no_cpu_baseline = args.no_whole_episode = True
+    if args.dump_outputs and 'weak' not in legs:
+        sys.exit('--dump-outputs writes the outputs of the weak leg: keep it in --legs')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return self_launch(args, argv)
@@ -772,7 +862,7 @@ def main(argv=None):
     grp = Dist(world, device if backend == 'nccl' else 'cpu')
     seed = 1 + rank
     free_tail = os.environ.get('TTL_BENCH_FREE_TAIL', '1') != '0'
-    n_win = max(1, args.windows)
+    n_win = max(1, args.windows if args.windows is not None else (11 if args.full else 1))
     # rehearsals on small boxes may shrink config 4 (never the driver's runs)
     c4_total = int(os.environ.get('TTL_BENCH_C4_TOTAL', WORKLOADS['c4']['n_total']))
 
@@ -792,13 +882,20 @@ def main(argv=None):
         mask_c2 = subject[1].data
         if 'weak' in legs:
             env.seeds = synthetic_seeds(mask_c2, N_ACTOR, seed=100 + rank)
-            weak = timed_windows(env, N_ACTOR, args.steps, args.warmup, n_win, seed, grp)
+            dump = None
+            if args.dump_outputs and rank == 0:
+                def dump(state):
+                    dump_outputs(env, state, args.dump_outputs)
+            weak = timed_windows(env, N_ACTOR, args.steps, args.warmup, n_win, seed, grp,
+                                 events=args.full, after_last=dump)
             weak['steps'] = args.steps
-            weak['other_kernels_ms_per_step'] = kernel_breakdown(env, N_ACTOR, args.steps, seed)
-            if not args.no_whole_episode:
-                weak['whole_episode'] = whole_episode(env, N_ACTOR, seed, free_tail)
-            if world > 1:
-                weak['collate'] = collate(env, grp)
+            if args.full:
+                weak['other_kernels_ms_per_step'] = kernel_breakdown(env, N_ACTOR, args.steps,
+                                                                     seed)
+                if not args.no_whole_episode:
+                    weak['whole_episode'] = whole_episode(env, N_ACTOR, seed, free_tail)
+                if world > 1:
+                    weak['collate'] = collate(env, grp)
             out['weak'] = weak
         if 'strong' in legs:
             if world == 1 and 'weak' in out:
@@ -991,17 +1088,19 @@ def main(argv=None):
             'resets_in_timed_region': weak['resets'] if weak else None,
             'parallelism': f'streamlines sharded over {world} GPU(s), '
                            'volumes replicated',
-            'legs': sorted(legs),
+            'legs': sorted(legs), 'full': args.full,
         }
         if weak:
             line['streamline_steps'] = weak['streamline_steps']
             line['windows'] = weak['windows']
-            roof = roofline_object(weak, 'c2', subject[1].data, ['pmc_traffic.json'], note_c2)
-            if roof is not None:
-                roof['whole_step_algorithmic_GBs'] = \
-                    roof['whole_step_algorithmic_bytes_per_unit'] * weak['value'] / world / 1e9
-                roof['other_kernels_ms_per_step'] = weak['other_kernels_ms_per_step']
-            line['roofline'] = roof
+            if args.full:
+                roof = roofline_object(weak, 'c2', subject[1].data, ['pmc_traffic.json'],
+                                       note_c2)
+                if roof is not None:
+                    roof['whole_step_algorithmic_GBs'] = \
+                        roof['whole_step_algorithmic_bytes_per_unit'] * weak['value'] / world / 1e9
+                    roof['other_kernels_ms_per_step'] = weak['other_kernels_ms_per_step']
+                line['roofline'] = roof
             if weak.get('whole_episode'):
                 line['whole_episode'] = weak['whole_episode']
             if 'collate' in weak:

@@ -7,15 +7,17 @@
 name=${1:-r02}
 rounds=${2:-3}
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+tmp=$(mktemp -d)
+# trees from before bench.py had --full ran every leg without it
+full_a=""; grep -q -- "'--full'" _ab/$name/bench.py && full_a=--full
 for r in $(seq 1 $rounds); do
-  (cd _ab/$name && timeout -k 10 200 python bench.py --no-cpu-baseline 2>/dev/null) > gpurun_out/ab_${name}_A$r.json
-  timeout -k 10 200 python bench.py --no-cpu-baseline --legs weak 2>/dev/null > gpurun_out/ab_${name}_B$r.json
-  python3 - "$name" "$r" <<'PY'
+  (cd _ab/$name && timeout -k 10 200 python bench.py $full_a --no-cpu-baseline 2>/dev/null) > $tmp/ab_${name}_A$r.json
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --legs weak 2>/dev/null > $tmp/ab_${name}_B$r.json
+  python3 - "$name" "$r" "$tmp" <<'PY'
 import json, sys
-name, r = sys.argv[1:3]
+name, r, tmp = sys.argv[1:4]
 for side in 'AB':
-    d = json.load(open(f'gpurun_out/ab_{name}_{side}{r}.json'))
+    d = json.load(open(f'{tmp}/ab_{name}_{side}{r}.json'))
     roof = d['roofline']
     print(side, r, f"value {d['value']/1e6:.1f} M  ms/step {d['ms_per_step']:.4f}  k_state {roof['avg_launch_ms']:.4f}  "
           f"other {json.dumps({k: round(v, 4) for k, v in roof['other_kernels_ms_per_step'].items() if not isinstance(v, str)})}  "

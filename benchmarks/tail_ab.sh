@@ -4,15 +4,15 @@
 #   B = k_tail at every size (TTL_TAIL_FUSED_MAX_ROWS=1048576)
 rounds=${1:-4}
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+tmp=$(mktemp -d)
 for r in $(seq 1 $rounds); do
   for v in A B; do
     if [ $v = A ]; then export TTL_TAIL_FUSED=0; unset TTL_TAIL_FUSED_MAX_ROWS; else export TTL_TAIL_FUSED=1 TTL_TAIL_FUSED_MAX_ROWS=1048576; fi
-    timeout -k 10 200 python bench.py --no-cpu-baseline --legs weak 2>/dev/null > gpurun_out/tail_ab_$v.json
-    python3 - "$v" "$r" <<'PY'
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --legs weak 2>/dev/null > $tmp/tail_ab_$v.json
+    python3 - "$v" "$r" "$tmp" <<'PY'
 import json, sys
-v, r = sys.argv[1:3]
-d = json.load(open(f'gpurun_out/tail_ab_{v}.json'))
+v, r, tmp = sys.argv[1:4]
+d = json.load(open(f'{tmp}/tail_ab_{v}.json'))
 roof = d['roofline']
 print(v, r, f"value {d['value']/1e6:.1f} M  ms/step {d['ms_per_step']:.4f}  k_state {roof['avg_launch_ms']:.4f}  "
       f"other {json.dumps({k: round(x, 4) for k, x in roof['other_kernels_ms_per_step'].items() if not isinstance(x, str)})}  "

@@ -4,15 +4,15 @@
 # Profiled passes run ONE leg of bench.py at a time (`--legs`, the same timed
 # windows; without the forked CPU workers and without the episode-to-exhaustion
 # tail whose small launches would dilute the per-kernel averages):
-#   headline leg  bench.py --no-cpu-baseline --no-whole-episode --legs weak
-#   HBM regime    bench.py --no-cpu-baseline --no-whole-episode --legs hbm   (145^3 volume, 131072 rows)
+#   headline leg  bench.py --full --no-cpu-baseline --no-whole-episode --legs weak
+#   HBM regime    bench.py --full --no-cpu-baseline --no-whole-episode --legs hbm   (145^3 volume, 131072 rows)
 # per leg:
 # 1. rocprofv3 --kernel-trace --stats        -> profiles/<tag>[_c4shard]_kernel_stats.csv,
 #                                               <tag>[_c4shard]_bench_under_rocprof.json
 # 2. two separate --pmc passes (FETCH_SIZE, WRITE_SIZE; TCC has 4 slots)
 #                                             -> profiles/<tag>[_c4shard]_pmc_traffic.txt,
 #                                                pmc_traffic.json / pmc_traffic_c4shard.json
-# then 3. python3 bench.py (every leg, fresh pmc json files: roofline.achieved / frac filled)
+# then 3. python3 bench.py --full (every leg, fresh pmc json files: roofline.achieved / frac filled)
 #                                             -> profiles/<tag>_bench.json
 # Results are copied under gpurun_out/profiles_<tag>/ (the only path that
 # travels back); copy them into profiles/ afterwards.
@@ -27,7 +27,7 @@ T="timeout -k 10 400"
 for leg in weak hbm; do
   sfx=""; js=pmc_traffic.json
   if [ $leg = hbm ]; then sfx="_c4shard"; js=pmc_traffic_c4shard.json; fi
-  B="python3 bench.py --no-cpu-baseline --no-whole-episode --legs $leg"
+  B="python3 bench.py --full --no-cpu-baseline --no-whole-episode --legs $leg"
   rm -f $O/stats$sfx.rows
   export TTL_GATHER_ROWS_LOG=$O/stats$sfx.rows
   $T rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats$sfx -- $B > $O/stats$sfx.json 2> $O/stats$sfx.log
@@ -61,6 +61,6 @@ rm -rf $O/c5
 $T python3 benchmarks/bench_oracle_net.py > $R/${tag}_oracle_net_bench.jsonl 2> /dev/null
 bash profiles/collect_pmc_oracle_net.sh $tag > /dev/null 2>&1 || true
 cp profiles/${tag}_pmc_oracle_net.txt $R/ 2> /dev/null || true
-timeout -k 10 900 python3 bench.py > $O/bench.json
+timeout -k 10 900 python3 bench.py --full > $O/bench.json
 cp $O/bench.json $R/${tag}_bench.json
 python3 benchmarks/show_bench.py $R/${tag}_bench.json

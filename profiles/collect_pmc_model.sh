@@ -16,7 +16,7 @@ R=gpurun_out/profiles_$tag
 mkdir -p $O $R
 OUT=$R/${tag}_pmc_kstate${extra:+_$extra}.txt
 : > $OUT
-CMD="python3 bench.py --no-cpu-baseline --no-whole-episode --windows 2"
+CMD="python3 bench.py --full --no-cpu-baseline --no-whole-episode --windows 2"
 i=0
 while read -r group; do
   [ -z "$group" ] && continue

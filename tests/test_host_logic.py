@@ -313,6 +313,15 @@ def test_bench_refuses_unknown_legs():
     assert out.returncode != 0 and 'unknown leg' in out.stderr
 
 
+def test_bench_legs_need_full():
+    """A plain run measures the headline alone: choosing legs is for --full."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--legs', 'shapes'],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and '--full' in out.stderr
+
+
 def test_header_is_plain_c99(tmp_path):
     """include/ttl_hip.h is the C ABI: it must compile as pedantic C99 on its
     own (no C++, no HIP, no torch types in any signature)."""

@@ -373,9 +373,60 @@ def test_bench_self_launch_reports_failed_ranks():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """A plain `bench.py --steps K --warmup W` times one window of K steps and
+    nothing else; --dump-outputs writes what the last timed step returned, the
+    same arrays from run to run."""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f'out{k}'
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1',
+                              '--steps', '5', '--warmup', '2', '--dump-outputs', str(d)],
+                             capture_output=True, text=True, timeout=300,
+                             env=dict(os.environ, PYTHONPATH=ROOT))
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = _last_json_line(out.stdout)
+        assert line['unit'] == 'streamline-steps/s' and line['higher_is_better'] is True
+        assert line['dtype'] == 'f32' and line['steps'] == 5 and line['warmup'] == 2
+        assert line['value'] > 0 and line['ms_per_step'] > 0
+        assert line['windows']['n'] == 1 and line['config']['legs'] == ['weak']
+        for moved in ('roofline', 'cpu_baseline', 'whole_episode', 'strong', 'config5'):
+            assert moved not in line, moved
+        assert 0 < line['streamline_steps'] <= 5 * 262144
+        arrays = {p.stem: np.load(p) for p in sorted(d.glob('*.npy'))}
+        assert set(arrays) == {'lengths', 'flags', 'dones', 'head', 'sample_ids', 'state',
+                               'history', 'n_active'}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+        assert arrays['lengths'].shape == (262144,) and arrays['state'].shape == (4096, 327)
+        # the seed and one point per step of the window's episode
+        assert arrays['lengths'].min() >= 1 and arrays['lengths'].max() == 6
+        assert 0 < arrays['n_active'][0] <= 262144
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+
+
+@pytest.mark.gpu
+def test_bench_full_windows_longer_than_an_episode():
+    """`--steps` beyond the length of an episode (at most 267 steps at 200 mm):
+    every leg starts a new episode where the last one ran out, the pipelined
+    halves included."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--legs',
+                          'weak,pipelined', '--no-cpu-baseline', '--no-whole-episode',
+                          '--steps', '300', '--warmup', '2', '--windows', '1'],
+                         capture_output=True, text=True, timeout=600,
+                         env=dict(os.environ, PYTHONPATH=ROOT))
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = _last_json_line(out.stdout)
+    assert line['config']['resets_in_timed_region'] >= 1
+    assert line['value'] > 0 and line['pipelined_halves']['value'] > 0
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_rehearsal_on_one_gpu():
     """The N > 1 path of bench.py as far as a 1-GPU box can take it: the bare
-    `--gpus 2` call launches two ranks itself (both on cuda:0, gloo instead of
+    `--gpus 2 --full` call launches two ranks itself (both on cuda:0, gloo instead of
     RCCL, which refuses two ranks on one device), shards, times the windows of
     every leg, gathers the finished tracts to rank 0 and prints ONE line that
     carries the weak-scaling value, the strong-scaling leg (262144 streamlines
@@ -386,7 +437,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
                TTL_BENCH_BACKEND='gloo', TTL_BENCH_C4_TOTAL='262144',
                TTL_BENCH_C5_TOTAL='16384')
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2',
-                          '--windows', '3', '--no-cpu-baseline'],
+                          '--full', '--windows', '3', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=1100, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = _last_json_line(out.stdout)
@@ -429,11 +480,11 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_other_shapes_leg():
-    """`bench.py --legs shapes`: the other BASELINE shapes in the line (one GPU),
+    """`bench.py --full --legs shapes`: the other BASELINE shapes in the line (one GPU),
     the reference's own calling contract among them."""
     env = dict(os.environ, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--legs', 'shapes',
-                          '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--legs',
+                          'shapes', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = _last_json_line(out.stdout)
@@ -450,11 +501,11 @@ def test_bench_other_shapes_leg():
 
 @pytest.mark.gpu
 def test_bench_learner_leg():
-    """`bench.py --legs learner`: BASELINE config 3's training step (SAC, hidden
+    """`bench.py --full --legs learner`: BASELINE config 3's training step (SAC, hidden
     1024-1024, n_actor 65536) in the line."""
     env = dict(os.environ, PYTHONPATH=ROOT)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--legs', 'learner',
-                          '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--legs',
+                          'learner', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = _last_json_line(out.stdout)
@@ -479,12 +530,12 @@ def test_bench_learner_leg():
 
 @pytest.mark.gpu
 def test_bench_config5_leg():
-    """`bench.py --legs config5`: BASELINE config 5's training step (oracle
+    """`bench.py --full --legs config5`: BASELINE config 5's training step (oracle
     bonus + oracle stopping) at one GPU's shard, with both oracle paths live
     and timed."""
     env = dict(os.environ, PYTHONPATH=ROOT, TTL_BENCH_C5_TOTAL='32768')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--legs', 'config5',
-                          '--no-cpu-baseline'],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--legs',
+                          'config5', '--no-cpu-baseline'],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     line = _last_json_line(out.stdout)
