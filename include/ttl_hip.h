@@ -41,7 +41,7 @@ extern "C" {
 #define TTL_API
 #endif
 
-#define TTL_ABI_VERSION 11
+#define TTL_ABI_VERSION 12
 
 #define TTL_OK 0
 #define TTL_ERR_INVALID (-1) /* bad argument / shape / alignment             */
@@ -446,6 +446,35 @@ TTL_API int ttl_oracle_segments(const float *history, int64_t row_pitch, const i
                                 int32_t id_stride, int32_t n, int32_t n_points,
                                 const float *lin, int32_t nb_points, float *dirs_out,
                                 void *hip_stream);
+
+/* The oracle validator's input (ABI v12; TrackToLearn/experiment/oracle_validator.py:
+ * 41-46, oracles/oracle.py:52-72) for a ragged tractogram: streamline i is
+ * points [offsets[i], offsets[i + 1]) (points: [M][3] f32, offsets: [n + 1] int64), of any
+ * length >= 2.  It is resampled to nb_points along the arc length exactly as
+ * ttl_resample_streamlines() resamples it laid out padded (the same bits), and the
+ * nb_points - 1 float32 differences go to dirs_out [n][nb_points - 1][3] f32.  One wavefront
+ * per streamline; LDS does not grow with the length (the cumulative arc length is recomputed
+ * from 64 lane prefixes).  A row of fewer than 2 points gives zero vectors.  Device pointers. */
+TTL_API int ttl_oracle_segments_packed(const float *points, const int64_t *offsets, int32_t n,
+                                       int32_t nb_points, float *dirs_out, void *hip_stream);
+
+/* The oracle validator's coverage map (ABI v12; oracle_validator.py:48-53: scilpy
+ * compute_tract_counts_map, binarised): for every streamline i < n of the ragged layout
+ * above with scores[i] > threshold (scores: device f32 [n], or NULL to take every
+ * streamline), visited[(x * Y + y) * Z + z] = 1 for the voxels it passes through
+ * (dims = {X, Y, Z}, host memory; visited: device u8 [X * Y * Z], zeroed by the caller,
+ * only ones are written).  Points are float32 voxel coordinates with corner origin: voxel
+ * v spans [v, v + 1).  Walk, in float64: mark floor(c_0); for each segment a -> b with
+ * va = floor(a), vb = floor(b), d = b - a, axis i crosses the integer planes between va_i
+ * and vb_i (va_i + 1 .. vb_i when d_i > 0, va_i .. vb_i + 1 when d_i < 0), plane beta at
+ * t = (beta - a_i) / d_i; crossings in increasing t, the lower axis first on ties; each one
+ * steps that axis's index by sign(d_i) and marks the new voxel.  Voxels outside [0, dims)
+ * are skipped, not clamped, and cost no work: per segment the work is the voxels marked
+ * plus O(log dims).  Segments with a non-finite end mark nothing.  One wavefront per
+ * streamline, one lane per segment; plain byte stores, no atomics. */
+TTL_API int ttl_tract_coverage(const float *points, const int64_t *offsets, int32_t n,
+                               const float *scores, float threshold, const int32_t *dims,
+                               uint8_t *visited, void *hip_stream);
 
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where

@@ -1,0 +1,438 @@
+"""The oracle validator (TrackToLearn/experiment/oracle_validator.py): the
+coverage walk and the coordinate conversions on the CPU against the NumPy
+restatement (tests/ref_oracle_validator.py), and on the GPU the two kernels
+(``ttl_oracle_segments_packed``, ``ttl_tract_coverage``), the scores against
+the reference's loop over ``OracleSingleton.predict`` and the trainer's
+``--oracle_validator`` end to end."""
+import time
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import ref_oracle_validator as ref
+
+DEV = 'cuda:0'
+
+
+# ------------------------------------------------------------------ helpers
+def random_walks(rng, n, lo, hi, box, step=(0.5, 0.75), start=None):
+    """n random-walk streamlines of lo..hi points, steps of 0.5-0.75 voxel,
+    starting uniformly in [0, box)^3 (or in ``start``)."""
+    lines = []
+    for _ in range(n):
+        L = int(rng.integers(lo, hi + 1))
+        d = rng.normal(size=(L - 1, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        d *= rng.uniform(step[0], step[1], (L - 1, 1))
+        p0 = rng.uniform(0, box, 3) if start is None else rng.uniform(*start, 3)
+        lines.append(np.concatenate([p0[None], p0 + np.cumsum(d, 0)]).astype(np.float32))
+    return lines
+
+
+def env_for(mask, affine=None, reference=None):
+    from tracktolearn_amd.datasets.utils import MRIDataVolume
+    aff = np.eye(4) if affine is None else affine
+    return SimpleNamespace(
+        tracking_mask=MRIDataVolume(mask, aff), affine_vox2rasmm=aff,
+        reference=reference if reference is not None else
+        {'affine': aff, 'shape': mask.shape[:3]})
+
+
+HAND = [   # (a, b, dims, voxels the segment enters)
+    # axis-aligned run
+    ((0.5, 0.5, 0.5), (3.5, 0.5, 0.5), (5, 5, 5), [(1, 0, 0), (2, 0, 0), (3, 0, 0)]),
+    # diagonal through an edge: the tie goes to the lower axis
+    ((0.5, 0.5, 0.5), (1.5, 1.5, 0.5), (4, 4, 4), [(1, 0, 0), (1, 1, 0)]),
+    ((2.5, 2.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(1, 2, 0), (1, 1, 0), (0, 1, 0), (0, 0, 0)]),
+    # points exactly on a face
+    ((1.0, 0.5, 0.5), (2.5, 0.5, 0.5), (4, 4, 4), [(2, 0, 0)]),
+    ((0.5, 0.5, 0.5), (1.0, 0.5, 0.5), (4, 4, 4), [(1, 0, 0)]),
+    ((1.0, 0.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0)]),
+    # negative coordinates: outside voxels are skipped, not clamped
+    ((-1.5, 0.5, 0.5), (1.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0), (1, 0, 0)]),
+    ((0.5, -0.25, 0.5), (0.5, -2.5, 0.5), (4, 4, 4), []),
+    # leaving the volume
+    ((3.5, 0.5, 0.5), (6.5, 0.5, 0.5), (5, 5, 5), [(4, 0, 0)]),
+    ((3.5, 3.5, 0.5), (5.5, 6.5, 0.5), (5, 5, 5), [(3, 4, 0), (4, 4, 0)]),
+    # zero length
+    ((1.25, 1.25, 1.25), (1.25, 1.25, 1.25), (4, 4, 4), []),
+    # a point 10^6 voxels away (both ends of the run outside on one side)
+    ((2.5, 2.5, 2.5), (2.5 + 1e6, 2.5 + 1e6, 2.5), (5, 5, 5),
+     [(3, 2, 2), (3, 3, 2), (4, 3, 2), (4, 4, 2)]),
+    ((-1e6, 2.5, 2.5), (3.5, 2.5, 2.5), (5, 5, 5),
+     [(0, 2, 2), (1, 2, 2), (2, 2, 2), (3, 2, 2)]),
+]
+
+
+# ----------------------------------------------------------------- CPU tests
+@pytest.mark.parametrize('a,b,dims,want', HAND)
+def test_walk_hand_built(a, b, dims, want):
+    assert ref.walk_segment(a, b, dims) == want
+    far = max(abs(v) for v in a + b) > 1e3
+    if not far:                      # the crossing-by-crossing definition agrees
+        assert ref.walk_segment_naive(a, b, dims) == want
+
+
+def test_walk_far_point_is_bounded():
+    """A segment from 10^6 voxels away costs the voxels it marks, not 10^6
+    steps (the naive definition would sort ~2 10^6 crossings here)."""
+    t0 = time.perf_counter()
+    for _ in range(100):
+        got = ref.walk_segment((-1e6, -1e6 + 0.3, 2.5), (2.5, 2.8, 2.5), (5, 5, 5))
+    assert time.perf_counter() - t0 < 2.0
+    assert got and all(0 <= v < 5 for vox in got for v in vox)
+
+
+def test_walk_bounded_equals_definition():
+    """The clipped walk (what the kernel runs) marks exactly the voxels of the
+    crossing-by-crossing definition, with ends inside, outside, on planes."""
+    rng = np.random.default_rng(0)
+    dims = (5, 6, 7)
+    for k in range(4000):
+        a = rng.uniform(-4, 11, 3)
+        b = a + rng.normal(0, 4, 3)
+        if k % 5 == 0:
+            b = np.floor(b) + rng.choice([0.0, 0.5], 3)
+        if k % 7 == 0:
+            a = np.floor(a)
+        if k % 11 == 0:
+            b = a.copy()
+            b[k % 3] += rng.normal(0, 3)
+        assert ref.walk_segment(a, b, dims) == ref.walk_segment_naive(a, b, dims), (a, b)
+
+
+def test_coverage_map_vectorised_equals_walk():
+    rng = np.random.default_rng(1)
+    dims = (6, 7, 8)
+    lines = random_walks(rng, 200, 2, 40, 8, step=(0.2, 2.5), start=(-3, 10))
+    from tracktolearn_amd.experiment.oracle_validator import pack
+    points, offsets = pack(lines)
+    accept = rng.random(len(lines)) < 0.7
+    want = np.zeros(dims, np.uint8)
+    for ln, ok in zip(lines, accept):
+        if ok:
+            for v in ref.streamline_voxels(ln, dims, ref.walk_segment_naive):
+                want[v] = 1
+    got = ref.coverage_map(points, offsets, dims, accept, max_crossings=4)
+    assert want.any() and np.array_equal(got, want)
+
+
+def _corner_case_lines():
+    return [np.array([[1.0, 2.0, 3.0], [2.5, 2.0, 3.0], [4.0, 4.25, 3.0]], np.float32),
+            np.array([[0.0, 0.0, 0.0], [-0.5, 1.5, 2.75]], np.float32),
+            np.array([[3.0, 3.0, 3.0]], np.float32)]
+
+
+@pytest.mark.parametrize('ext', ['trk', 'tck'])
+def test_file_to_corner_voxels(tmp_path, ext):
+    """RAS+mm file -> the reference's voxel space, corner origin: 2 mm
+    voxels, an offset origin; streamlines of < 2 points dropped."""
+    from tracktolearn_amd.experiment.oracle_validator import load_corner_voxels
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.tractogram import Tractogram
+    aff = np.diag([2.0, 2.0, 2.0, 1.0])
+    aff[:3, 3] = [-10.0, 20.0, 4.0]
+    vox = _corner_case_lines()
+    world = Tractogram(vox).apply_affine(aff)
+    path = str(tmp_path / f't.{ext}')
+    if ext == 'trk':
+        sio.save_trk(world, path, sio.create_tractogram_header(aff, (8, 8, 8), (2.0, 2.0, 2.0)))
+    else:
+        sio.save_tck(world, path)
+    points, offsets = load_corner_voxels(path, aff)
+    assert offsets.tolist() == [0, 3, 5]
+    want = np.concatenate(vox[:2]) + np.float32(0.5)
+    assert points.dtype == np.float32 and np.array_equal(points, want)
+
+
+def test_tracker_to_corner_voxels():
+    from tracktolearn_amd.experiment.oracle_validator import (
+        corner_voxels_from_tracker, keep_streamlines, pack)
+    lines = keep_streamlines(_corner_case_lines())
+    points, offsets = pack(lines)
+    assert offsets.tolist() == [0, 3, 5]
+    ref_aff = np.diag([2.0, 2.0, 2.0, 1.0])
+    ref_aff[:3, 3] = [-10.0, 20.0, 4.0]
+    # equal affines: exactly p + 0.5f
+    same = corner_voxels_from_tracker(points, ref_aff.copy(), ref_aff)
+    assert np.array_equal(same, points + np.float32(0.5))
+    # a 1 mm tracking grid in the same world: 0.5 p + 0.5
+    track = np.eye(4)
+    track[:3, 3] = ref_aff[:3, 3]
+    half = corner_voxels_from_tracker(points, track, ref_aff)
+    assert np.array_equal(half, points * np.float32(0.5) + np.float32(0.5))
+
+
+def test_short_streamlines_dropped(tmp_path):
+    """Streamlines of < 2 points are dropped before anything else; none left
+    -> {} (no GPU work: the validator runs on a CPU-placed oracle here)."""
+    from tracktolearn_amd.experiment.oracle_validator import (
+        OracleValidator, keep_streamlines)
+    from tracktolearn_amd.oracles.oracle import OracleSingleton
+    from tracktolearn_amd.oracles.transformer_oracle import save_random_checkpoint
+    from tracktolearn_amd.tractogram import Tractogram
+    lines = [np.zeros((0, 3), np.float32), np.ones((1, 3), np.float32),
+             np.ones((2, 3), np.float32)]
+    assert [len(s) for s in keep_streamlines(lines)] == [2]
+    ck = save_random_checkpoint(str(tmp_path / 'o.ckpt'), n_head=1, n_layers=1)
+    OracleSingleton.reset()
+    try:
+        val = OracleValidator(ck, 'cpu')
+        assert val.name == 'Oracle'
+        env = env_for(np.ones((4, 4, 4), np.uint8))
+        assert val(Tractogram(lines[:2]), env) == {}
+    finally:
+        OracleSingleton.reset()
+
+
+def test_validator_needs_a_checkpoint(tmp_path):
+    from tracktolearn_amd.experiment.oracle_validator import OracleValidator
+    empty = tmp_path / 'empty.ckpt'
+    empty.write_bytes(b'')
+    for ck in ('', None, str(tmp_path / 'missing.ckpt'), str(empty)):
+        with pytest.raises(ValueError):
+            OracleValidator(ck, DEV)
+
+
+def test_blocked_resampler_matches_plain_restatement():
+    """The blocked-order restatement is the same resampler as
+    tests/ref_resample.py up to float64 summation order."""
+    from ref_resample import resample_streamlines
+    rng = np.random.default_rng(2)
+    for L in (2, 3, 64, 65, 130, 1000):
+        ln = random_walks(rng, 1, L, L, 10)[0]
+        want = resample_streamlines(torch.from_numpy(ln[None]), torch.tensor([L]), 128)[0]
+        np.testing.assert_allclose(ref.resample_blocked(ln), want.numpy(), atol=1e-5, rtol=0)
+
+
+# ----------------------------------------------------------------- GPU tests
+def _packed_dev(lines):
+    from tracktolearn_amd.experiment.oracle_validator import pack
+    points, offsets = pack(lines)
+    return torch.from_numpy(points).to(DEV), torch.from_numpy(offsets).to(DEV)
+
+
+def _padded(lines):
+    L = max(len(s) for s in lines)
+    pad = np.zeros((len(lines), L, 3), np.float32)
+    for i, s in enumerate(lines):
+        pad[i, :len(s)] = s
+    return (torch.from_numpy(pad).to(DEV),
+            torch.tensor([len(s) for s in lines], dtype=torch.long, device=DEV))
+
+
+@pytest.mark.gpu
+def test_segments_packed_equal_padded_resampler():
+    """Ragged batches (2-600 points, repeated points included) give the bits of
+    resample_streamlines on the padded layout + the float32 difference; a
+    20 000-point streamline (above k_resample's LDS limit) the bits of the
+    blocked-order restatement, within 1e-5 of tests/ref_resample.py."""
+    from ref_resample import resample_streamlines as cpu_resample
+    from tracktolearn_amd.oracles.oracle import (oracle_segments_packed,
+                                                 resample_streamlines)
+    rng = np.random.default_rng(3)
+    for batch in range(3):
+        lines = random_walks(rng, 700, 2, 600, 60, step=(0.05, 1.5))
+        for s in lines[::9]:                       # zero-length segments
+            k = int(rng.integers(0, len(s)))
+            s[k:k + 3] = s[k]
+        points, offsets = _packed_dev(lines)
+        got = oracle_segments_packed(points, offsets)
+        pad, lengths = _padded(lines)
+        res = resample_streamlines(pad, lengths, 128)
+        want = res[:, 1:] - res[:, :-1]
+        assert torch.equal(got, want), batch
+    long = random_walks(rng, 1, 20000, 20000, 4, step=(0.02, 0.08))[0]
+    points, offsets = _packed_dev([long])
+    got = oracle_segments_packed(points, offsets)[0].cpu().numpy()
+    assert np.array_equal(got, ref.segments_blocked(long))
+    plain = cpu_resample(torch.from_numpy(long[None]), torch.tensor([20000]), 128)[0]
+    np.testing.assert_allclose(got, (plain[1:] - plain[:-1]).numpy(), atol=1e-5, rtol=0)
+
+
+def _gpu_coverage(lines, dims, scores=None):
+    from tracktolearn_amd.experiment.oracle_validator import tract_coverage
+    points, offsets = _packed_dev(lines)
+    v = tract_coverage(points, offsets, dims, scores)
+    return v.view(*dims).cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_coverage_hand_built_and_random():
+    from tracktolearn_amd.experiment.oracle_validator import pack
+    for a, b, dims, want in HAND:
+        line = np.array([a, b], np.float32)
+        got = _gpu_coverage([line], dims)
+        expect = np.zeros(dims, np.uint8)
+        for v in ref.streamline_voxels(line, dims):
+            expect[v] = 1
+        for v in want:
+            assert expect[v] == 1
+        assert np.array_equal(got, expect), (a, b)
+    rng = np.random.default_rng(4)
+    dims = (40, 40, 40)
+    lines = random_walks(rng, 20000, 2, 120, 40, start=(-4, 44))
+    got = _gpu_coverage(lines, dims)
+    points, offsets = pack(lines)
+    want = ref.coverage_map(points, offsets, dims)
+    assert 0 < want.sum() < want.size
+    assert np.array_equal(got, want)
+
+
+def _calibrated_checkpoint(tmp_path, lines, n_head=2, n_layers=1):
+    """A random oracle whose scores straddle 0.5 on ``lines``."""
+    from tracktolearn_amd.oracles.oracle import OracleSingleton
+    from tracktolearn_amd.oracles.transformer_oracle import save_random_checkpoint
+    ck = save_random_checkpoint(str(tmp_path / 'o.ckpt'), n_head=n_head,
+                                n_layers=n_layers, seed=7)
+    OracleSingleton.reset()
+    sc = OracleSingleton(ck, DEV).predict_packed(*_packed_dev(lines)).double().cpu()
+    logits = torch.log(sc / (1 - sc)).numpy()
+    blob = torch.load(ck, map_location='cpu', weights_only=True)
+    blob['state_dict']['head.bias'] -= float(np.median(logits))
+    ck2 = str(tmp_path / 'o2.ckpt')
+    torch.save(blob, ck2)
+    OracleSingleton.reset()
+    return ck2
+
+
+def _reference_loop(oracle, lines):
+    """oracle_validator.py:38-46: predict in slices of 4 096."""
+    out = []
+    for i in range(0, len(lines), 4096):
+        pad, lengths = _padded(lines[i:i + 4096])
+        out.append(oracle.predict(pad, lengths))
+    return torch.cat(out)
+
+
+@pytest.mark.gpu
+def test_scores_coverage_and_dict(tmp_path, monkeypatch):
+    """OracleValidator's scores are OracleSingleton.predict's in slices of
+    4 096 (fused: bit for bit; module under autocast: within 5e-3), its
+    coverage the restatement's on the GPU's accepted set, and chunks of 4 096
+    and 65 536 give the same bits (every chunk > 512 rows)."""
+    from tracktolearn_amd.experiment.oracle_validator import OracleValidator, pack
+    from tracktolearn_amd.oracles.oracle import OracleSingleton
+    from tracktolearn_amd.tractogram import Tractogram
+    rng = np.random.default_rng(5)
+    dims = (30, 30, 30)
+    mask = np.zeros(dims, np.uint8)
+    mask[3:27, 3:27, 3:27] = 1
+    # multiples of 2^-10: tracker coordinates p = line - 0.5 map back exactly
+    lines = [(np.round(s * 1024) / 1024).astype(np.float32)
+             for s in random_walks(rng, 20000, 20, 160, 30)]
+    env = env_for(mask)
+    ck = _calibrated_checkpoint(tmp_path, lines)
+    try:
+        val = OracleValidator(ck, DEV)
+        assert val.model.net is not None
+        points, offsets = _packed_dev(lines)
+        got = val.model.predict_packed(points, offsets)
+        want = _reference_loop(val.model, lines)
+        assert torch.equal(got, want)
+        assert torch.equal(val.model.predict_packed(points, offsets, chunk=4096), got)
+        accepted = (got > 0.5).cpu().numpy()
+        assert 0.2 < accepted.mean() < 0.8
+        # the validator on the in-memory tractogram (tracker voxels: + 0.5)
+        tracker_lines = [s - np.float32(0.5) for s in lines]
+        assert all(np.array_equal(t + np.float32(0.5), s) for t, s in zip(tracker_lines, lines))
+        out = val(Tractogram(tracker_lines), env)
+        p, o = pack(lines)
+        visited = ref.coverage_map(p, o, dims, accepted)
+        assert out == ref.oracle_and_coverage(got.cpu().numpy(), visited, mask)
+        assert np.array_equal(_gpu_coverage(lines, dims, got), visited)
+
+        monkeypatch.setenv('TTL_ORACLE_FUSED', '0')
+        OracleSingleton.reset()
+        val = OracleValidator(ck, DEV)
+        assert val.model.net is None
+        mod = val.model.predict_packed(points, offsets)
+        mod_ref = _reference_loop(val.model, lines)
+        assert (mod - mod_ref).abs().max().item() < 5e-3
+        flip = (mod > 0.5) != (mod_ref > 0.5)
+        assert ((mod_ref[flip] - 0.5).abs() < 5e-3).all()
+    finally:
+        OracleSingleton.reset()
+
+
+@pytest.mark.gpu
+def test_file_and_memory_paths_agree(tmp_path):
+    """Dyadic coordinates (multiples of 2^-10) and an identity affine: every
+    conversion is exact, so the .trk path and the in-memory path agree."""
+    from tracktolearn_amd.experiment.oracle_validator import OracleValidator
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.oracles.oracle import OracleSingleton
+    from tracktolearn_amd.tractogram import Tractogram
+    rng = np.random.default_rng(6)
+    dims = (24, 24, 24)
+    mask = np.zeros(dims, np.uint8)
+    mask[2:22, 2:22, 2:22] = 1
+    lines = [np.round(s * 1024) / 1024 for s in random_walks(rng, 3000, 10, 80, 23)]
+    lines = [s.astype(np.float32) for s in lines] + [np.ones((1, 3), np.float32)]
+    ck = _calibrated_checkpoint(tmp_path, lines[:-1])
+    try:
+        val = OracleValidator(ck, DEV)
+        env = env_for(mask)
+        tract = Tractogram(lines)
+        path = str(tmp_path / 'v.trk')
+        sio.save_trk(Tractogram(lines), path,
+                     sio.create_tractogram_header(np.eye(4), dims, (1.0, 1.0, 1.0)))
+        mem, disk = val(tract, env), val(path, env)
+        assert set(mem) == {'Oracle', 'Coverage'} and 0 < mem['Oracle'] < 1
+        assert mem['Coverage'] > 0
+        assert mem == disk
+    finally:
+        OracleSingleton.reset()
+
+
+def _write_dataset(path, D=20):
+    from tracktolearn_amd.datasets.SubjectDataset import write_npz_dataset
+    from tracktolearn_amd.utils.synthetic import synthetic_volumes
+    subs = {}
+    for i, sid in enumerate(('sub-a', 'sub-b')):
+        sh, mask, pk = synthetic_volumes(D, 45, seed=50 + i)
+        aff = np.eye(4, dtype=np.float32)
+        subs[sid] = {'input_volume': (sh, aff), 'peaks_volume': (pk, aff),
+                     'tracking_volume': (mask, aff), 'seeding_volume': (mask, aff)}
+    write_npz_dataset(path, {'training': subs})
+
+
+@pytest.mark.gpu
+def test_sac_auto_train_oracle_validator(tmp_path, capsys):
+    """--oracle_validator end to end: the scores are printed at every
+    validation and kept in plots/oracle.npy and plots/coverage.npy; without
+    the flag neither file appears."""
+    from tracktolearn_amd.oracles.oracle import OracleSingleton
+    from tracktolearn_amd.oracles.transformer_oracle import save_random_checkpoint
+    from tracktolearn_amd.trainers import sac_auto_train
+    ds = str(tmp_path / 'ds.npz')
+    _write_dataset(ds)
+    ck = save_random_checkpoint(str(tmp_path / 'o.ckpt'), n_head=2, n_layers=1, seed=3)
+    common = ['--log_interval', '1', '--n_actor', '512', '--hidden_dims', '32-32',
+              '--batch_size', '64', '--replay_size', '20000', '--npv', '1',
+              '--min_length', '2', '--max_length', '20', '--oracle_bonus', '0',
+              '--oracle_checkpoint', ck, '--rng_seed', '4']
+    OracleSingleton.reset()
+    try:
+        exp = tmp_path / 'exp'
+        sac_auto_train.main([str(exp), 'toy', 'run1', ds, '--max_ep', '2'] + common +
+                            ['--oracle_validator'])
+        out = capsys.readouterr().out
+        assert 'oracle_validator is outside the scope' not in out
+        assert out.count("'Oracle':") == 4 and out.count("'Coverage':") == 4
+        oracle = np.load(exp / 'plots' / 'oracle.npy')
+        coverage = np.load(exp / 'plots' / 'coverage.npy')
+        assert oracle.shape == (4, 2) and coverage.shape == (4, 2)
+        assert ((oracle[:, 1] >= 0) & (oracle[:, 1] <= 1)).all()
+        assert (coverage[:, 1] >= 0).all() and coverage[:, 1].max() > 0
+
+        plain = tmp_path / 'plain'
+        sac_auto_train.main([str(plain), 'toy', 'run2', ds, '--max_ep', '1'] + common)
+        assert (plain / 'plots' / 'train_reward.npy').exists()
+        assert not (plain / 'plots' / 'oracle.npy').exists()
+        assert not (plain / 'plots' / 'coverage.npy').exists()
+        assert "'Oracle':" not in capsys.readouterr().out
+    finally:
+        OracleSingleton.reset()

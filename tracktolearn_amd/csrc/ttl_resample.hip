@@ -4,6 +4,7 @@
 // One wavefront per streamline: float64 segment lengths -> blocked wave scan
 // of the cumulative arc length in LDS -> each lane places its target points
 // by binary search and interpolates linearly inside the segment.
+// k_oracle_segments_packed does the same for ragged input of any length.
 #include "ttl_internal.h"
 
 namespace {
@@ -181,6 +182,119 @@ __global__ __launch_bounds__(BLOCK) void k_oracle_segments(
     }
 }
 
+// Ragged streamlines (points + int64 offsets) -> the network's input, one wavefront per
+// streamline, for any length: LDS holds the 64 exclusive lane prefixes of k_resample's
+// blocked scan, not the cumulative arc length itself.  A value cum[m] is recomputed on
+// demand by re-walking its owner lane's block, which gives the bits k_resample stores
+// (cum[j + 1] = local_j + before).  The target search replays k_resample's binary search
+// probe by probe while the interval spans several lane blocks (cum may step back by an
+// ulp at a block boundary, where `before` comes from a subtraction); inside one block cum
+// is non-decreasing, so the rest of that search is the first m with cum[m + 1] > target,
+// found by one walk of the block.
+__device__ inline double seg_len(const float *__restrict__ p, long long j) {
+    const double dx = (double)p[3 * (j + 1) + 0] - (double)p[3 * j + 0];
+    const double dy = (double)p[3 * (j + 1) + 1] - (double)p[3 * j + 1];
+    const double dz = (double)p[3 * (j + 1) + 2] - (double)p[3 * j + 2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// cum[m], 1 <= m <= nseg: the blocked-scan prefix k_resample keeps in LDS
+__device__ inline double cum_at(const float *__restrict__ p, const double *pre, long long per,
+                                long long m) {
+    const long long seg = m - 1, owner = seg / per;
+    double local = 0.0;
+    for (long long j = owner * per; j <= seg; ++j) local = local + seg_len(p, j);
+    return local + pre[owner];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_oracle_segments_packed(
+    const float *__restrict__ points, const long long *__restrict__ offsets, int n, int nb,
+    float *__restrict__ dirs) {
+    extern __shared__ __align__(16) double pk_lds[];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // per wave: pre [64] doubles, res [3 nb] floats
+    const size_t per_wave = ((size_t)64 * 8 + (size_t)nb * 12 + 15) & ~(size_t)15;
+    char *base = reinterpret_cast<char *>(pk_lds) + (size_t)wv * per_wave;
+    double *pre = reinterpret_cast<double *>(base);
+    float *res = reinterpret_cast<float *>(base + 64 * 8);
+    const int waves = (BLOCK / 64) * gridDim.x;
+    for (int row = blockIdx.x * (BLOCK / 64) + wv; row < n; row += waves) {
+        const long long o0 = offsets[row], L = offsets[row + 1] - o0;
+        float *o = dirs + (size_t)row * (size_t)(nb - 1) * 3;
+        if (L < 1) {                            // nothing to resample: zero vectors
+            for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = 0.0f;
+            continue;
+        }
+        const float *p = points + 3 * o0;
+        const long long nseg = L - 1;
+        const long long per = nseg > 0 ? (nseg + 63) >> 6 : 1;
+        const long long lo = min((long long)lane * per, nseg), hi = min(lo + per, nseg);
+        double local = 0.0;
+        for (long long j = lo; j < hi; ++j) local = local + seg_len(p, j);
+        double before = local;                  // inclusive scan over lanes, as k_resample
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const double up = __shfl_up(before, off);
+            if (lane >= off) before = before + up;
+        }
+        pre[lane] = before - local;             // exclusive
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const double total = nseg > 0 ? cum_at(p, pre, per, nseg) : 0.0;
+        for (int k = lane; k < nb; k += 64) {
+            float x, y, z;
+            if (k == nb - 1 || nseg == 0) {     // the last point is kept exactly
+                x = p[3 * nseg + 0];
+                y = p[3 * nseg + 1];
+                z = p[3 * nseg + 2];
+            } else {
+                const double target = total * ((double)k / (double)(nb - 1));
+                // k_resample: j = #{m in [0, nseg) : cum[m + 1] <= target} by binary search
+                long long a = 0, b = nseg;
+                while (a < b) {
+                    if (a / per == (b - 1) / per) {     // one block: cum is monotone here
+                        const long long owner = a / per;
+                        double acc = 0.0;
+                        long long first = b;
+                        for (long long j = owner * per; j < b; ++j) {
+                            acc = acc + seg_len(p, j);
+                            if (j >= a && acc + pre[owner] > target) {
+                                first = j;
+                                break;
+                            }
+                        }
+                        a = first;
+                        break;
+                    }
+                    const long long mid = (a + b) >> 1;
+                    if (cum_at(p, pre, per, mid + 1) <= target) a = mid + 1;
+                    else b = mid;
+                }
+                const long long j = min(a, nseg - 1);
+                const double c0 = j > 0 ? cum_at(p, pre, per, j) : 0.0;
+                const double c1 = cum_at(p, pre, per, j + 1);
+                const double den = c1 - c0;
+                const double r = den > 0.0 ? (target - c0) / den : 0.0;
+                const double ax = p[3 * j + 0], ay = p[3 * j + 1], az = p[3 * j + 2];
+                const double bx = p[3 * j + 3], by = p[3 * j + 4], bz = p[3 * j + 5];
+                x = (float)(ax + r * (bx - ax));
+                y = (float)(ay + r * (by - ay));
+                z = (float)(az + r * (bz - az));
+            }
+            res[3 * k + 0] = x;
+            res[3 * k + 1] = y;
+            res[3 * k + 2] = z;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = res[e + 3] - res[e];
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();        // pre / res are reused by the next streamline
+    }
+}
+
 // OracleReward's sparse bonus (oracle_reward.py:84-93): term = 0 everywhere,
 // bonus at the stopped rows whose score is > 0.5 (rows past n_scored were never
 // scored: 0); reward += term.
@@ -247,6 +361,26 @@ int ttl_oracle_segments(const float *history, int64_t row_pitch, const int32_t *
     hipLaunchKernelGGL(k_oracle_segments, dim3(want < 8192 ? want : 8192), dim3(BLOCK), lds,
                        (hipStream_t)hip_stream, history, (long long)row_pitch, ids, id_stride, n,
                        n_points, lin ? 1 : 0, L, nb_points, dirs_out);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+int ttl_oracle_segments_packed(const float *points, const int64_t *offsets, int32_t n,
+                               int32_t nb_points, float *dirs_out, void *hip_stream) {
+    if (!points || !offsets || !dirs_out || n < 1 || nb_points < 2)
+        return fail(TTL_ERR_INVALID, "ttl_oracle_segments_packed: bad arguments");
+    const size_t per_wave = ((size_t)64 * 8 + (size_t)nb_points * 12 + 15) & ~(size_t)15;
+    const size_t lds = (size_t)(BLOCK / 64) * per_wave;
+    if (lds > 160u * 1024u)
+        return fail(TTL_ERR_INVALID, "ttl_oracle_segments_packed: %d output points exceed the LDS",
+                    nb_points);
+    if (lds > 64u * 1024u)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_oracle_segments_packed,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int want = (n + (BLOCK / 64) - 1) / (BLOCK / 64);
+    hipLaunchKernelGGL(k_oracle_segments_packed, dim3(want < 8192 ? want : 8192), dim3(BLOCK),
+                       lds, (hipStream_t)hip_stream, points, (const long long *)offsets, n,
+                       nb_points, dirs_out);
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

@@ -7,7 +7,8 @@ under autocast; here resampling, differencing and batching stay on the GPU.
 
 Reference quirk kept on purpose: with more than one batch,
 the final *partial* batch is never evaluated and its scores stay 0
-(oracle.py:62-84); ``drop_tail=False`` scores everything.
+(oracle.py:62-84); ``drop_tail=False`` scores everything, and so does
+``predict_packed`` (ragged input, the oracle validator's path).
 """
 import contextlib
 import os
@@ -56,6 +57,37 @@ def resample_streamlines(points, lengths, nb_points=128):
             l32.data_ptr() if l32 is not None else None,
             l64.data_ptr() if l64 is not None else None,
             n, L, int(nb_points), out.data_ptr(), stream), 'ttl_resample_streamlines')
+    return out
+
+
+def oracle_segments_packed(points, offsets, nb_points=128, out=None):
+    """The network's input for a ragged batch on the GPU
+    (``ttl_oracle_segments_packed``, one wavefront per streamline, any length):
+    streamline i is ``points[offsets[i]:offsets[i + 1]]`` (points (M, 3)
+    float32, offsets (n + 1,) int64, CUDA tensors) -> (n, nb_points - 1, 3)
+    float32, the differences of ``resample_streamlines`` on the same
+    streamline laid out padded, bit for bit.  ``out`` may be given."""
+    import ctypes as C
+
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    if not points.is_cuda:
+        raise _lib.TTLError('oracle_segments_packed needs CUDA tensors: there is no CPU path')
+    n = int(offsets.shape[0]) - 1
+    if out is None:
+        out = torch.empty((max(n, 0), nb_points - 1, 3), dtype=torch.float32,
+                          device=points.device)
+    if n <= 0:
+        return out
+    pts = points.to(torch.float32).contiguous()
+    off = offsets.to(points.device, torch.int64).contiguous()
+    if tuple(out.shape) != (n, nb_points - 1, 3) or not out.is_contiguous():
+        raise ValueError('oracle_segments_packed: out must be a contiguous (n, nb_points - 1, 3)')
+    with torch.cuda.device(points.device):
+        stream = C.c_void_p(torch.cuda.current_stream(points.device).cuda_stream)
+        _lib.check(lib.ttl_oracle_segments_packed(
+            pts.data_ptr(), off.data_ptr(), n, int(nb_points), out.data_ptr(), stream),
+            'ttl_oracle_segments_packed')
     return out
 
 
@@ -165,24 +197,65 @@ class OracleSingleton:
             lengths = torch.full((n,), points.shape[1], dtype=torch.long,
                                  device=self.device)
         spans = self._spans(n)
-        autocast = (torch.autocast('cuda') if self.device.type == 'cuda'
-                    else contextlib.nullcontext())
         for lo, hi in spans:
             data = self._resample(points[lo:hi], lengths[lo:hi], 128)
             dirs = (data[:, 1:] - data[:, :-1]).float()
             if self.net is not None:
                 result[lo:hi] = self.net(dirs)
                 continue
-            rows = hi - lo
-            padded = -(-rows // self.pad_rows) * self.pad_rows if self.pad_rows else rows
-            if padded != rows:
-                if self._pad_buf is None or self._pad_buf.shape[0] < padded or \
-                        self._pad_buf.shape[1:] != dirs.shape[1:]:
-                    self._pad_buf = torch.zeros((max(padded, self.batch_size),) + tuple(dirs.shape[1:]),
-                                                dtype=dirs.dtype, device=dirs.device)
-                self._pad_buf[:rows].copy_(dirs)
-                self._pad_buf[rows:padded].zero_()
-                dirs = self._pad_buf[:padded]
-            with autocast, torch.no_grad():
-                result[lo:hi] = self.model(dirs).float()[:rows]
+            result[lo:hi] = self._module_scores(dirs)
+        return result
+
+    def _module_scores(self, dirs):
+        """The PyTorch module under autocast on ``dirs`` (rows, 127, 3), the
+        rows zero-padded to a multiple of ``pad_rows``."""
+        autocast = (torch.autocast('cuda') if self.device.type == 'cuda'
+                    else contextlib.nullcontext())
+        rows = dirs.shape[0]
+        padded = -(-rows // self.pad_rows) * self.pad_rows if self.pad_rows else rows
+        if padded != rows:
+            if self._pad_buf is None or self._pad_buf.shape[0] < padded or \
+                    self._pad_buf.shape[1:] != dirs.shape[1:]:
+                self._pad_buf = torch.zeros((max(padded, self.batch_size),) + tuple(dirs.shape[1:]),
+                                            dtype=dirs.dtype, device=dirs.device)
+            self._pad_buf[:rows].copy_(dirs)
+            self._pad_buf[rows:padded].zero_()
+            dirs = self._pad_buf[:padded]
+        with autocast, torch.no_grad():
+            return self.model(dirs).float()[:rows]
+
+    #: streamlines per ``predict_packed`` launch pair: the segment vectors of
+    #: one chunk take 65 536 x 127 x 3 x 4 B ~ 100 MB
+    packed_chunk = 65536
+
+    def predict_packed(self, points, offsets, chunk=None):
+        """Scores (n,) float32 on the device of a ragged tractogram: streamline
+        i is ``points[offsets[i]:offsets[i + 1]]`` (points (M, 3) float32,
+        offsets (n + 1,) int64, on the device or the host), any length >= 2.
+        Every row is scored (no tail drop, unlike ``predict`` over several
+        batches): per chunk of ``chunk`` streamlines, resampling + differencing
+        in one launch (``ttl_oracle_segments_packed``, the same bits as
+        ``resample_streamlines`` on the padded layout), then the fused network,
+        or the module under autocast with ``predict``'s padding.  Launched on
+        the current stream of ``self.device``."""
+        from tracktolearn_amd import _lib
+        if self.device.type != 'cuda':
+            raise _lib.TTLError('predict_packed needs a CUDA device: there is no CPU path')
+        chunk = int(chunk or self.packed_chunk)
+        n = int(offsets.shape[0]) - 1
+        result = torch.empty(max(n, 0), dtype=torch.float32, device=self.device)
+        if n <= 0:
+            return result
+        with torch.cuda.device(self.device):
+            points = points.to(self.device, torch.float32).contiguous()
+            offsets = offsets.to(self.device, torch.int64).contiguous()
+            dirs = torch.empty((min(n, chunk), 127, 3), dtype=torch.float32,
+                               device=self.device)
+            for lo in range(0, n, chunk):
+                rows = min(chunk, n - lo)
+                oracle_segments_packed(points, offsets[lo:lo + rows + 1], 128, dirs[:rows])
+                if self.net is not None:
+                    result[lo:lo + rows] = self.net(dirs[:rows])
+                else:
+                    result[lo:lo + rows] = self._module_scores(dirs[:rows])
         return result

@@ -2,10 +2,13 @@
 
 Mirror of TrackToLearn/trainers/train.py (``run`` / ``rl_train``, argument
 groups) and of the parts of TrackToLearn/experiment/experiment.py it needs
-(env factory, stopping stats, validation tractogram saving, monitors).  The
-Tractometer / oracle validators and Comet.ml are outside the hot-path scope
-(SURVEY 2.1): ``--use_comet``, ``--tractometer_validator`` and
-``--oracle_validator`` are accepted and ignored with a notice.
+(env factory, stopping stats, validation tractogram saving, monitors, the
+validators).  ``--oracle_validator`` scores every validation tractogram with
+TractOracle on the GPU (experiment/oracle_validator.py: ``Oracle`` and
+``Coverage``, printed and kept in ``plots/oracle.npy`` / ``coverage.npy``).
+The Tractometer validator and Comet.ml are outside the hot-path scope
+(SURVEY 2.1): ``--use_comet`` and ``--tractometer_validator`` are accepted and
+ignored with a notice.
 """
 import json
 import os
@@ -65,7 +68,9 @@ class TrackToLearnTraining(object):
         self.last_episode = 0
         self.device = get_device()
         self.use_comet = g['use_comet']
-        for flag in ('use_comet', 'tractometer_validator', 'oracle_validator'):
+        self.validators = []
+        self.score_monitors = {}
+        for flag in ('use_comet', 'tractometer_validator'):
             if g[flag]:
                 print(f'NOTE: --{flag} is outside the scope of this build and '
                       'is ignored')
@@ -141,6 +146,13 @@ class TrackToLearnTraining(object):
         sio.save_trk(world, filename, header)
         return filename
 
+    def score_tractogram(self, filename, env):
+        """Scores of a tractogram by every validator (experiment.py:236-254)."""
+        all_scores = {}
+        for scorer in self.validators:
+            all_scores.update(scorer(filename, env))
+        return all_scores
+
     def setup_monitors(self):
         p = self.experiment_path
         self.train_reward_monitor = LossHistory('Train Reward', 'train_reward', p)
@@ -190,6 +202,16 @@ class TrackToLearnTraining(object):
             self.save_rasmm_tractogram(valid_tractogram, valid_env.subject_id,
                                        valid_env.affine_vox2rasmm,
                                        valid_env.reference)
+            if self.validators:
+                # the streamlines just saved, scored from memory (no file round
+                # trip; score_tractogram takes the file)
+                scores = self.score_tractogram(valid_tractogram, valid_env)
+                print(scores)
+                for key, value in scores.items():
+                    monitor = self.score_monitors.get(key)
+                    if monitor is not None:
+                        monitor.update(value)
+                        monitor.end_epoch(i_episode)
         self.log(valid_tractogram, valid_reward, i_episode)
         self.save_model(alg)
 
@@ -200,6 +222,19 @@ class TrackToLearnTraining(object):
         t = 0
         train_tracker = Tracker(alg, self.n_actor, prob=0.0, compress=0.0)
         valid_tracker = Tracker(alg, self.n_actor, prob=1.0, compress=0.0)
+        # validators (train.py:216-226; the Tractometer stays out)
+        self.validators = []
+        self.score_monitors = {}
+        if self.oracle_validator:
+            from tracktolearn_amd.experiment.oracle_validator import \
+                OracleValidator
+            self.validators.append(OracleValidator(self.oracle_checkpoint,
+                                                   self.device))
+            # Comet is ignored: the scores are kept as plots/<name>.npy
+            p = self.experiment_path
+            self.score_monitors = {
+                'Oracle': LossHistory('Oracle', 'oracle', p),
+                'Coverage': LossHistory('Coverage', 'coverage', p)}
         self._validate(valid_tracker, valid_env, alg, i_episode)
         while i_episode < self.max_ep:
             self.last_episode = i_episode
@@ -310,7 +345,7 @@ def add_oracle_args(parser: ArgumentParser):
                         default='models/tractoracle.ckpt',
                         help='Checkpoint file (.ckpt) of the Oracle')
     oracle.add_argument('--oracle_validator', action='store_true',
-                        help='Run a TractOracle model during validation (ignored).')
+                        help='Run a TractOracle model during validation.')
     oracle.add_argument('--oracle_stopping_criterion', action='store_true',
                         help='Stop streamlines according to the Oracle.')
     oracle.add_argument('--oracle_bonus', default=10, type=float,
