@@ -6,7 +6,7 @@ Run:  python tests/golden/make_golden.py         (only where /root/reference
 exists; the GPU box never sees the reference, only the .npz files travel).
 Every trace seeds its own seed stream (`seed_stream`), so each fixture is
 reproduced byte for byte by this script whatever traces are added or removed
-around it; tests/test_golden_reproducible.py checks that for all four
+around it; tests/test_golden_reproducible.py checks that for all five
 generators wherever the reference tree is present.
 
 How the reference is made importable: its third-party

@@ -651,7 +651,9 @@ class FusedSACUpdate(_FusedNets):
         if not overlap:
             ops.adam_polyak(aq.online, aq.grad, aq.m, aq.v, aq.target, self.consts[4:6], alg.tau)
         if want_losses:
-            lo = self.loss_out
+            # a copy: the next update rewrites ``loss_out`` while the episode loop
+            # still holds this update's entries (one device copy, no host sync)
+            lo = self.loss_out.clone()
             return {'actor_loss': lo[0], 'critic_loss': lo[1] + lo[2], 'loss_q1': lo[1],
                     'loss_q2': lo[2], 'Q1': lo[3], 'Q2': lo[4], 'backup': lo[5]}
         return {}
@@ -879,8 +881,10 @@ class FusedTD3Update(_FusedNets):
     def _losses(self, want, actor):
         if not want:
             return {}
-        lo = self.loss_out
-        al = self.actor_loss[0] if actor else 0.0
+        # copies: the next update rewrites both buffers while the episode loop
+        # still holds this update's entries (device copies, no host sync)
+        lo = self.loss_out.clone()
+        al = self.actor_loss[0].clone() if actor else 0.0
         if self.NQ == 2:
             return {'actor_loss': al, 'critic_loss': lo[1] + lo[2], 'loss_q1': lo[1],
                     'loss_q2': lo[2], 'Q1': lo[3], 'Q2': lo[4], "Q'": lo[5]}

@@ -14,8 +14,15 @@ def add_to_means(means, dic):
 
 
 def mean_losses(dic):
-    return {k: np.mean(torch.stack([torch.as_tensor(v) for v in dic[k]])
-                       .cpu().numpy(), axis=0) for k in dic.keys()}
+    """Mean of every list of per-update entries.  An entry is a 0-d tensor or a
+    plain number (TD3's ``actor_loss`` is 0.0 in the updates that skip the
+    actor): numbers join the tensors on their device before stacking."""
+    out = {}
+    for k, values in dic.items():
+        dev = next((v.device for v in values if isinstance(v, torch.Tensor)), None)
+        out[k] = np.mean(torch.stack([torch.as_tensor(v, device=dev) for v in values])
+                         .cpu().numpy(), axis=0)
+    return out
 
 
 def mean_rewards(dic):
