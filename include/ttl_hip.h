@@ -409,7 +409,10 @@ TTL_API int ttl_peaks_from_sh(const float *sh, int64_t n_voxels, int32_t n_coef,
  * deterministic and scores a row independently of its batch; the two agree to the rounding of
  * the fp16 score (the order of one float32 sum differs).  d_model 32, 128 tokens, n_head in
  * {1, 2, 4}, ReLU post-norm layers, ff_dim a multiple of 32, at most 8192 (TTL_ERR_UNSUPPORTED
- * otherwise).  The weights come packed by
+ * otherwise).  b_1 of two layers is staged in LDS, 8 ff_dim bytes on top of the workgroup
+ * kernel's 56 KB: the sum is checked against the device's limit per workgroup before the
+ * launch (120 KB of the MI355X's 160 KB at 8192; TTL_ERR_UNSUPPORTED where it does not fit).
+ * The weights come packed by
  * tracktolearn_amd/oracles/fused_net.py:pack_oracle_net (fp16 MFMA fragments in the k order an
  * accumulator tile presents, per-row vectors in accumulator row order):
  *   packed_half  [n_layers][8 + 4 ff_dim / 32][64][8] f16: W_q, W_k, W_v, W_o, W_1 chunks, W_2 chunks

@@ -1,6 +1,6 @@
 """Every committed fixture is reproduced by the committed generator.
 
-Where /root/reference exists (the build container), the five generators under
+Where /root/reference exists (the build container), the six generators under
 tests/golden/ are run into a scratch directory (TTL_GOLDEN_OUT) and every
 .npz they write is compared with the committed file of the same name, array
 for array (dtype, shape and bytes).  On the GPU box the reference tree is
@@ -17,7 +17,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 GENERATORS = ('make_golden.py', 'make_golden_tracker.py', 'make_golden_learner.py',
-              'make_golden_oracle.py', 'make_golden_training.py')
+              'make_golden_oracle.py', 'make_golden_training.py',
+              'make_golden_oracle_net.py')
 
 
 @pytest.mark.skipif(not os.path.isdir('/root/reference'),

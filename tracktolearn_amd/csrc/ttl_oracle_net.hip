@@ -744,6 +744,44 @@ __global__ __launch_bounds__(256, 2) void k_oracle_net_wg(NetArgs P) {
     if (warm == 0xfff1fff2u && P.n < 0) P.out[row] = 0.f;
 }
 
+constexpr int TTL_ORACLE_NET_MAX_FF = 8192;
+
+// Static + dynamic LDS of `kernel` (slot: 0..2 the wave kernel of 1 / 2 / 4 heads, 3..5 the
+// workgroup kernel) against the device's limit per workgroup, BEFORE the launch: the runtime
+// does not reject a launch that asks for more -- the queue aborts.  What the kernel and the
+// device report is read once per device and thread (the call is on the training step's path);
+// hipFuncAttributeMaxDynamicSharedMemorySize is raised when a call needs more dynamic LDS than
+// any before it, as ttl_oracle_segments does.
+int reserve_lds(const void *kernel, int slot, size_t dynamic, int ff_dim) {
+    struct Seen { size_t limit, fixed, allowed; bool known; };
+    static thread_local Seen seen[64][6] = {};
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Seen fresh{};
+    Seen &k = (dev >= 0 && dev < 64) ? seen[dev][slot] : fresh;
+    if (!k.known) {
+        int limit = 0;
+        HIP_TRY(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        HIP_TRY(hipFuncGetAttributes(&fa, kernel));
+        k.limit = (size_t)(limit > 0 ? limit : 0);
+        k.fixed = fa.sharedSizeBytes;
+        k.allowed = 0;
+        k.known = true;
+    }
+    if (k.fixed + dynamic > k.limit)
+        return fail(TTL_ERR_UNSUPPORTED,
+                    "ttl_oracle_net_forward: feed-forward width %d needs %zu B of LDS (%zu static "
+                    "+ %zu for b_1 of two layers), the device gives a workgroup %zu",
+                    ff_dim, k.fixed + dynamic, k.fixed, dynamic, k.limit);
+    if (dynamic > k.allowed) {
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)dynamic));
+        k.allowed = dynamic;
+    }
+    return TTL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -757,9 +795,11 @@ int ttl_oracle_net_forward(const float *dirs, int64_t n, const void *packed_half
     if (n <= 0 || n_layers <= 0 || ff_dim <= 0 || ff_dim % 32)
         return fail(TTL_ERR_INVALID, "ttl_oracle_net_forward: bad shape (n %lld, layers %d, ff %d)",
                     (long long)n, n_layers, ff_dim);
-    if (ff_dim > 8192)      // b_1 of two layers in LDS: 8 ff bytes of the default 64 KB
-        return fail(TTL_ERR_UNSUPPORTED, "ttl_oracle_net_forward: feed-forward width %d > 8192",
-                    ff_dim);
+    // (the width the packing and FusedOracleNet.supports() stop at; what the device's LDS
+    // allows is checked below, for the kernel that will be launched)
+    if (ff_dim > TTL_ORACLE_NET_MAX_FF)
+        return fail(TTL_ERR_UNSUPPORTED, "ttl_oracle_net_forward: feed-forward width %d > %d",
+                    ff_dim, TTL_ORACLE_NET_MAX_FF);
     if (n_head != 1 && n_head != 2 && n_head != 4)
         return fail(TTL_ERR_UNSUPPORTED, "ttl_oracle_net_forward: 1, 2 or 4 heads (got %d)", n_head);
     if (((uintptr_t)packed_half & 15u) || ((uintptr_t)packed_float & 15u))
@@ -776,7 +816,19 @@ int ttl_oracle_net_forward(const float *dirs, int64_t n, const void *packed_half
         return v ? atoi(v) : -1;
     }();
     const bool wg = wg_mode == 1 || (wg_mode != 0 && n <= TTL_ORACLE_NET_WG_MAX_ROWS);
-    const size_t lds = (size_t)2 * ff_dim * sizeof(float);          // b_1, two layers
+    // LDS of the launch: b_1 of two layers as dynamic LDS (2 ff floats = 8 ff bytes: 16 KB at
+    // the default width 2 048, 64 KB at 8 192), on top of the kernel's static LDS --
+    // k_oracle_net_wg: pbuf 48 KB + fbuf 8 KB = 56 KB, 72 KB / 120 KB in all; k_oracle_net:
+    // none.  The device gives a workgroup 160 KB (gfx950).
+    const size_t lds = (size_t)2 * ff_dim * sizeof(float);
+    const int which = n_head == 1 ? 0 : n_head == 2 ? 1 : 2;
+    const void *kernel = wg ? (which == 0 ? (const void *)k_oracle_net_wg<1>
+                               : which == 1 ? (const void *)k_oracle_net_wg<2>
+                                            : (const void *)k_oracle_net_wg<4>)
+                            : (which == 0 ? (const void *)k_oracle_net<1>
+                               : which == 1 ? (const void *)k_oracle_net<2>
+                                            : (const void *)k_oracle_net<4>);
+    if (int rc = reserve_lds(kernel, (wg ? 3 : 0) + which, lds, ff_dim)) return rc;
     if (wg) {
         const dim3 grid((unsigned)n), block(256);
         if (n_head == 1) k_oracle_net_wg<1><<<grid, block, lds, s>>>(P);

@@ -110,28 +110,60 @@ def pack_oracle_net(model, device):
     }
 
 
+MAX_FF = 8192                       # TTL_ORACLE_NET_MAX_FF of csrc/ttl_oracle_net.hip
+WG_STATIC_LDS = 56 * 1024           # k_oracle_net_wg: pbuf 48 KB + fbuf 8 KB
+GFX950_LDS = 160 * 1024             # per workgroup on the MI355X
+
+
+def lds_bytes(ff, workgroup_kernel=True):
+    """LDS of a launch, as csrc/ttl_oracle_net.hip states it: b_1 of two layers
+    (2 ff floats) as dynamic LDS, on top of the workgroup kernel's 56 KB."""
+    return (WG_STATIC_LDS if workgroup_kernel else 0) + 2 * ff * 4
+
+
+def lds_limit(device=None):
+    """LDS the device gives one workgroup (the MI355X's where there is none)."""
+    device = torch.device(device) if device is not None else torch.device('cpu')
+    if device.type == 'cuda':
+        return torch.cuda.get_device_properties(device).shared_memory_per_block
+    return GFX950_LDS
+
+
+def _layer_supported(m, n_head, ff):
+    at = m.self_attn
+    return (at.num_heads == n_head and at.embed_dim == D_MODEL and at.batch_first
+            and at.in_proj_weight is not None and at.in_proj_bias is not None
+            and not m.norm_first
+            and m.linear1.in_features == D_MODEL and m.linear1.out_features == ff
+            and m.linear2.in_features == ff and m.linear2.out_features == D_MODEL
+            and getattr(m.activation, '__name__', '') == 'relu'
+            and abs(m.norm1.eps - 1e-5) < 1e-12 and abs(m.norm2.eps - 1e-5) < 1e-12)
+
+
 class FusedOracleNet:
     """``scores = FusedOracleNet(model)(dirs)`` for dirs (N, 127, 3) float32 on
     the model's CUDA device: (N,) float32 scores in (0, 1)."""
 
     @staticmethod
     def supports(model):
-        """Whether ``model`` is the architecture the kernel implements."""
+        """Whether ``model`` is the architecture the kernel implements: every
+        encoder layer alike (width, heads, activation, norm order, eps), and a
+        feed-forward width whose LDS (``lds_bytes``) the device gives a
+        workgroup -- what ``ttl_oracle_net_forward`` checks before it launches."""
         try:
             layers = list(model.bert.layers)
             l0 = layers[0]
+            ff = l0.linear1.out_features
             return (model.embedding_size == D_MODEL and model.input_size // 3 + 1 == TOKENS
                     and model.output_size == 1 and model.bert.norm is None and len(layers) >= 1
                     and all(isinstance(m, nn.TransformerEncoderLayer) for m in layers)
-                    and l0.self_attn.num_heads in (1, 2, 4) and l0.self_attn.batch_first
-                    and not l0.norm_first and l0.linear1.out_features % 32 == 0
-                    and l0.linear1.out_features <= 8192
-                    and getattr(l0.activation, '__name__', '') == 'relu'
-                    and l0.self_attn.in_proj_weight is not None
-                    and abs(l0.norm1.eps - 1e-5) < 1e-12
+                    and l0.self_attn.num_heads in (1, 2, 4)
+                    and ff % 32 == 0 and 0 < ff <= MAX_FF
+                    and lds_bytes(ff) <= lds_limit(next(model.parameters()).device)
+                    and all(_layer_supported(m, l0.self_attn.num_heads, ff) for m in layers)
                     and isinstance(model.embedding[0], nn.Linear)
                     and model.embedding[0].in_features == 3)
-        except (AttributeError, IndexError, TypeError):
+        except (AttributeError, IndexError, TypeError, StopIteration):
             return False
 
     def __init__(self, model, device=None):
