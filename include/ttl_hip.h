@@ -41,7 +41,7 @@ extern "C" {
 #define TTL_API
 #endif
 
-#define TTL_ABI_VERSION 12
+#define TTL_ABI_VERSION 13
 
 #define TTL_OK 0
 #define TTL_ERR_INVALID (-1) /* bad argument / shape / alignment             */
@@ -497,6 +497,50 @@ TTL_API int ttl_oracle_bonus(const float *scores, int32_t n_scored, const int32_
 TTL_API int ttl_pack_streamlines(const float *history, int64_t row_pitch, const int64_t *keep,
                          const int64_t *offsets, int32_t n, float *points_out,
                          void *hip_stream);
+
+/* The tracker's output stage (ABI v13): length filter, optional compression
+ * and ragged pack of a finished batch, on the env's buffers in place.  Device pointers;
+ * n == 0 is a successful no-op.
+ *
+ * ttl_tract_select, one wavefront per row of history ([n] rows of row_pitch floats, as
+ * for ttl_pack_streamlines; T = row_pitch / 3 points):
+ *  1. keep = lengths[i] - 1 if flags[i] has TTL_FLAG_CURVATURE or TTL_FLAG_MASK, else
+ *     lengths[i] (clamped to [0, T]).
+ *  2. arc = sum over the keep - 1 segments of sqrt(dx*dx + dy*dy + dz*dz) in float64, d =
+ *     the float32 difference of consecutive points widened to float64, squares added left
+ *     to right.  Lane l adds segments l, l + 64, ... in order and a fixed butterfly adds
+ *     the 64 partial sums: the bits depend on the points and keep alone.  keep < 2 gives
+ *     0.  The row is accepted iff min_arc <= arc <= max_arc.
+ *  3. An accepted row with tol_error > 0 and keep > 2 is compressed greedily
+ *     (tractogram.compress_streamline): prev = 0; for nxt = 2 .. keep-1: a = p[prev], b =
+ *     p[nxt] in float64, ab = b - a, L = sqrt(ab.x^2 + ab.y^2 + ab.z^2); the chord is
+ *     admissible iff L <= max_segment_length and every q = p[j] - a, prev < j < nxt, has
+ *     sqrt(|q - t ab|^2) <= tol_error with t = clamp((q . ab) / (L L), 0, 1) (|q| <=
+ *     tol_error when L == 0); if it is not, point nxt-1 is kept and prev = nxt-1.  Points
+ *     0 and keep-1 are always kept.  The lanes test the interior points of one chord, 64
+ *     at a time, and a ballot decides it.  No operation is fused.  With tol_error == 0, or
+ *     keep <= 2, every kept point survives.
+ *  Out: counts[i] = surviving points (0 for a rejected row), accepted[i] = 0 / 1, and
+ *  mask[i][ttl_tract_mask_words(row_pitch)]: bit j & 63 of word j >> 6 set iff point j
+ *  survives (all zero for a rejected row).  Rows of up to ttl_tract_stage_points() points
+ *  are staged in the LDS and read from memory once; longer rows are read in place.
+ *
+ * ttl_tract_emit, one wavefront per row, after the caller's inclusive prefix sums
+ * count_ends / accept_ends (int64) over counts / accepted: accepted row i is output row k
+ * = accept_ends[i] - 1; counts_out[k] = counts[i], rows_out[k] = i, and its survivors go,
+ * in order, to points_out + 3 * (count_ends[i] - counts[i]).  points_out holds
+ * count_ends[n-1] points, counts_out and rows_out accept_ends[n-1] entries. */
+TTL_API int32_t ttl_tract_mask_words(int64_t row_pitch);
+TTL_API int32_t ttl_tract_stage_points(void);
+TTL_API int ttl_tract_select(const float *history, int64_t row_pitch, const int32_t *lengths,
+                             const int32_t *flags, int32_t n, double min_arc, double max_arc,
+                             double tol_error, double max_segment_length, int32_t *counts,
+                             int32_t *accepted, uint64_t *mask, void *hip_stream);
+TTL_API int ttl_tract_emit(const float *history, int64_t row_pitch, int32_t n,
+                           const int32_t *counts, const int32_t *accepted,
+                           const int64_t *count_ends, const int64_t *accept_ends,
+                           const uint64_t *mask, float *points_out, int64_t *counts_out,
+                           int32_t *rows_out, void *hip_stream);
 
 TTL_API const char *ttl_last_error(void);
 TTL_API uint32_t ttl_abi_version(void);

@@ -1,0 +1,255 @@
+// ttl_tract.hip -- the tracker's output stage on the device: the
+// arc-length filter of TrackToLearn/tracking/tracker.py:120-121, the greedy
+// linearisation of tractogram.compress_streamline and the ragged pack of what
+// survives; part of libttl_hip.so.  Two kernels over the env's history buffer,
+// one wavefront per streamline each, with an exclusive prefix sum (the
+// caller's) between them:
+//   k_tract_select  kept length, float64 arc, accept, survivor bitmask + count
+//   k_tract_emit    survivors -> packed points, compacted counts and rows
+// All float64 arithmetic is plain IEEE (no fused multiply-add), in the order
+// include/ttl_hip.h states.
+#include "ttl_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+constexpr int BLOCK = TTL_BLOCK;
+constexpr int WAVES = BLOCK / 64;
+// points of one row a wave stages in the LDS (float32, 12 B each: 4.5 KB per
+// wave); longer rows read the history from global memory instead
+constexpr int STAGE_PTS = 384;
+
+// orders this wave's LDS writes before its later LDS reads (the LDS executes
+// one wave's instructions in order; this keeps the compiler from moving them)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+struct D3 {
+    double x, y, z;
+};
+
+__device__ __forceinline__ D3 point(const float *__restrict__ p, int j) {
+    return D3{(double)p[3 * j], (double)p[3 * j + 1], (double)p[3 * j + 2]};
+}
+
+// bits [64 w, 64 w + 64) of the mask whose first `keep` bits are set
+__device__ __forceinline__ unsigned long long prefix_word(int w, int keep) {
+    const int left = keep - 64 * w;
+    return left >= 64 ? ~0ull : (left <= 0 ? 0ull : ((1ull << left) - 1ull));
+}
+
+// The greedy compression of the first `keep` (> 2) points of p (LDS or global);
+// survivor words go to mrow[0 .. nwords), the survivor count is returned.  Every
+// variable that steers the loops is the same in all 64 lanes.
+__device__ int compress_row(const float *__restrict__ p, int keep, double tol, double max_seg,
+                            unsigned long long *__restrict__ mrow, int nwords, int lane) {
+    int wcur = 0, count = 1, prev = 0;
+    unsigned long long word = 1ull;                  // point 0
+    auto keep_point = [&](int k) {
+        const int w = k >> 6;
+        while (wcur < w) {
+            if (lane == 0) mrow[wcur] = word;
+            word = 0ull;
+            ++wcur;
+        }
+        word |= 1ull << (k & 63);
+        ++count;
+    };
+    for (int nxt = 2; nxt < keep; ++nxt) {
+        const D3 a = point(p, prev), b = point(p, nxt);
+        const double abx = b.x - a.x, aby = b.y - a.y, abz = b.z - a.z;
+        const double L = sqrt(abx * abx + aby * aby + abz * abz);
+        bool ok = L <= max_seg;
+        if (ok) {
+            const double LL = L * L;
+            for (int j0 = prev + 1; j0 < nxt; j0 += 64) {
+                const int j = j0 + lane;
+                bool bad = false;
+                if (j < nxt) {
+                    const D3 c = point(p, j);
+                    double dx = c.x - a.x, dy = c.y - a.y, dz = c.z - a.z;
+                    if (L > 0.0) {
+                        double t = (dx * abx + dy * aby + dz * abz) / LL;
+                        t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+                        dx = dx - t * abx;
+                        dy = dy - t * aby;
+                        dz = dz - t * abz;
+                    }
+                    bad = !(sqrt(dx * dx + dy * dy + dz * dz) <= tol);
+                }
+                if (__ballot(bad) != 0ull) {
+                    ok = false;
+                    break;
+                }
+            }
+        }
+        if (!ok) {
+            keep_point(nxt - 1);
+            prev = nxt - 1;
+        }
+    }
+    keep_point(keep - 1);
+    while (wcur < nwords) {
+        if (lane == 0) mrow[wcur] = word;
+        word = 0ull;
+        ++wcur;
+    }
+    return count;
+}
+
+template <bool STAGED>
+__global__ __launch_bounds__(BLOCK) void k_tract_select(
+    const float *__restrict__ hist, long long row_pitch, const int *__restrict__ lengths,
+    const int *__restrict__ flags, int n, double min_arc, double max_arc, double tol,
+    double max_seg, int *__restrict__ counts, int *__restrict__ accepted,
+    unsigned long long *__restrict__ mask, int nwords) {
+    __shared__ float stage[STAGED ? WAVES * STAGE_PTS * 3 : 1];
+    const int i = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int lane = threadIdx.x & 63;
+    const int T = (int)(row_pitch / 3);
+    int keep = lengths[i] - ((flags[i] & (TTL_FLAG_CURVATURE | TTL_FLAG_MASK)) != 0 ? 1 : 0);
+    keep = keep < 0 ? 0 : (keep > T ? T : keep);
+    const float *p = hist + (size_t)i * (size_t)row_pitch;
+    if (STAGED) {
+        float *s = stage + (threadIdx.x >> 6) * (STAGE_PTS * 3);
+        for (int f = lane; f < 3 * keep; f += 64) s[f] = p[f];
+        wave_sync();
+        p = s;
+    }
+    // arc length: float32 differences widened to float64; lane l sums segments l, l + 64,
+    // ... in that order, then a fixed butterfly adds the 64 partial sums (every lane ends
+    // with the same bits: each level adds the same two values in both lanes of a pair)
+    double arc = 0.0;
+    for (int j = lane; j < keep - 1; j += 64) {
+        const double dx = (double)(p[3 * j + 3] - p[3 * j]);
+        const double dy = (double)(p[3 * j + 4] - p[3 * j + 1]);
+        const double dz = (double)(p[3 * j + 5] - p[3 * j + 2]);
+        arc += sqrt(dx * dx + dy * dy + dz * dz);
+    }
+    for (int m = 32; m >= 1; m >>= 1) arc += __shfl_xor(arc, m, 64);
+    arc = __shfl(arc, 0, 64);
+    const bool ok = min_arc <= arc && arc <= max_arc;
+    unsigned long long *mrow = mask + (size_t)i * (size_t)nwords;
+    int count;
+    if (ok && tol > 0.0 && keep > 2) {
+        count = compress_row(p, keep, tol, max_seg, mrow, nwords, lane);
+    } else {
+        count = ok ? keep : 0;
+        for (int w = lane; w < nwords; w += 64) mrow[w] = prefix_word(w, count);
+    }
+    if (lane == 0) {
+        counts[i] = count;
+        accepted[i] = ok ? 1 : 0;
+    }
+}
+
+// Survivors of the accepted rows, streamline-major.  Per 64-point word of the mask: a
+// word whose set bits are its lowest ones is a straight copy; any other is compacted
+// through the LDS (survivor r of the word writes floats 3 r .. 3 r + 2), so that the
+// stores run along the packed output either way.
+__global__ __launch_bounds__(BLOCK) void k_tract_emit(
+    const float *__restrict__ hist, long long row_pitch, int n, const int *__restrict__ counts,
+    const int *__restrict__ accepted, const long long *__restrict__ count_ends,
+    const long long *__restrict__ accept_ends, const unsigned long long *__restrict__ mask,
+    int nwords, float *__restrict__ points_out, long long *__restrict__ counts_out,
+    int *__restrict__ rows_out) {
+    __shared__ float pack[WAVES * 192];
+    const int i = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (i >= n || !accepted[i]) return;
+    const int lane = threadIdx.x & 63;
+    const int count = counts[i];
+    const long long k = accept_ends[i] - 1;
+    if (lane == 0) {
+        counts_out[k] = count;
+        rows_out[k] = i;
+    }
+    const float *src = hist + (size_t)i * (size_t)row_pitch;
+    float *dst = points_out + 3 * (size_t)(count_ends[i] - count);
+    const unsigned long long *mrow = mask + (size_t)i * (size_t)nwords;
+    float *s = pack + (threadIdx.x >> 6) * 192;
+    for (int w = 0; w < nwords; ++w) {
+        const unsigned long long word = mrow[w];
+        if (word == 0ull) continue;
+        const int c = __popcll(word);
+        const float *from = src + (size_t)w * 192;
+        if ((word & (word + 1ull)) == 0ull) {
+            for (int f = lane; f < 3 * c; f += 64) dst[f] = from[f];
+        } else {
+            if ((word >> lane) & 1ull) {
+                const int r = __popcll(word & ((1ull << lane) - 1ull));
+                s[3 * r] = from[3 * lane];
+                s[3 * r + 1] = from[3 * lane + 1];
+                s[3 * r + 2] = from[3 * lane + 2];
+            }
+            wave_sync();
+            for (int f = lane; f < 3 * c; f += 64) dst[f] = s[f];
+            wave_sync();
+        }
+        dst += 3 * c;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int32_t ttl_tract_mask_words(int64_t row_pitch) {
+    return row_pitch < 3 ? 0 : (int32_t)((row_pitch / 3 + 63) / 64);
+}
+
+int32_t ttl_tract_stage_points(void) { return STAGE_PTS; }
+
+int ttl_tract_select(const float *history, int64_t row_pitch, const int32_t *lengths,
+                     const int32_t *flags, int32_t n, double min_arc, double max_arc,
+                     double tol_error, double max_segment_length, int32_t *counts,
+                     int32_t *accepted, uint64_t *mask, void *hip_stream) {
+    if (n < 0 || row_pitch < 3 || row_pitch / 3 > INT32_MAX / 4)
+        return fail(TTL_ERR_INVALID, "ttl_tract_select: n=%d, row_pitch=%lld", n,
+                    (long long)row_pitch);
+    if (n == 0) return TTL_OK;
+    if (!history || !lengths || !flags || !counts || !accepted || !mask)
+        return fail(TTL_ERR_INVALID, "ttl_tract_select: null argument");
+    if (!(tol_error >= 0.0) || max_segment_length != max_segment_length ||
+        min_arc != min_arc || max_arc != max_arc)
+        return fail(TTL_ERR_INVALID, "ttl_tract_select: tol_error must be >= 0 and no bound NaN");
+    const int nwords = ttl_tract_mask_words(row_pitch);
+    const dim3 grid((n + WAVES - 1) / WAVES), block(BLOCK);
+    if (row_pitch / 3 <= STAGE_PTS)
+        hipLaunchKernelGGL(k_tract_select<true>, grid, block, 0, (hipStream_t)hip_stream, history,
+                           (long long)row_pitch, lengths, flags, n, min_arc, max_arc, tol_error,
+                           max_segment_length, counts, accepted, (unsigned long long *)mask,
+                           nwords);
+    else
+        hipLaunchKernelGGL(k_tract_select<false>, grid, block, 0, (hipStream_t)hip_stream, history,
+                           (long long)row_pitch, lengths, flags, n, min_arc, max_arc, tol_error,
+                           max_segment_length, counts, accepted, (unsigned long long *)mask,
+                           nwords);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+int ttl_tract_emit(const float *history, int64_t row_pitch, int32_t n, const int32_t *counts,
+                   const int32_t *accepted, const int64_t *count_ends,
+                   const int64_t *accept_ends, const uint64_t *mask, float *points_out,
+                   int64_t *counts_out, int32_t *rows_out, void *hip_stream) {
+    if (n < 0 || row_pitch < 3 || row_pitch / 3 > INT32_MAX / 4)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit: n=%d, row_pitch=%lld", n,
+                    (long long)row_pitch);
+    if (n == 0) return TTL_OK;
+    // points_out may be null when no point survives; the kernel then stores none
+    if (!history || !counts || !accepted || !count_ends || !accept_ends || !mask ||
+        !counts_out || !rows_out)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit: null argument");
+    hipLaunchKernelGGL(k_tract_emit, dim3((n + WAVES - 1) / WAVES), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, history, (long long)row_pitch, n, counts, accepted,
+                       (const long long *)count_ends, (const long long *)accept_ends,
+                       (const unsigned long long *)mask,
+                       ttl_tract_mask_words(row_pitch), points_out, (long long *)counts_out,
+                       rows_out);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+}  // extern "C"

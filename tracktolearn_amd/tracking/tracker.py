@@ -2,9 +2,11 @@
 
 Mirror of TrackToLearn/tracking/tracker.py (track / track_and_train /
 track_and_validate).  The per-streamline Python work of the reference's
-generator (length filter, optional compression, voxel->file space) is kept for
-the yielded items, but the length filter itself runs on the GPU over the whole
-batch so that rejected streamlines are never downloaded.
+generator (length filter, optional compression, voxel->file space) runs on the
+GPU over the whole finished batch (``parallel.select_tracts``): only the points
+that end up in the file are downloaded.  ``device_output=False`` keeps the
+earlier path (torch length filter on the device, compression per streamline on
+the host) as the comparison baseline.
 """
 from collections import defaultdict
 
@@ -59,7 +61,7 @@ class Tracker(object):
     (tracker.py:19-60)."""
 
     def __init__(self, alg, n_actor, prob=0., compress=0.0, min_length=20,
-                 max_length=200, save_seeds=False):
+                 max_length=200, save_seeds=False, device_output=None):
         self.alg = alg
         self.n_actor = n_actor
         self.prob = prob
@@ -67,6 +69,9 @@ class Tracker(object):
         self.min_length = min_length
         self.max_length = max_length
         self.save_seeds = save_seeds
+        #: filter + compression + pack by the HIP output stage; None: whenever
+        #: the env's buffers are on the GPU.  False: the host path
+        self.device_output = device_output
         #: one process per GPU: every rank tracks its contiguous shard of each
         #: seed batch and rank 0 yields the collated streamlines
         self.rank, self.group_size = 0, 1
@@ -75,11 +80,34 @@ class Tracker(object):
             self.rank, self.group_size = dist.get_rank(), dist.get_world_size()
 
     # ------------------------------------------------------------------ #
-    def _batch_arrays(self, env, scaled_min, scaled_max):
+    def _device_output(self, env):
+        if self.device_output is None:
+            return bool(env._buf_streamlines.is_cuda)
+        return bool(self.device_output)
+
+    def _batch_arrays(self, env, scaled_min, scaled_max, tol_vox=0.0):
         """Streamlines of the finished batch whose arc length (voxels) is in
-        [scaled_min, scaled_max]: the filter of tracker.py:120-121 evaluated
-        on the device.  Returns (packed points (M, 3) f32, kept lengths (k,)
-        i64, seeds (k, 3) f64) as device tensors."""
+        [scaled_min, scaled_max] (the filter of tracker.py:120-121), compressed
+        to ``tol_vox`` voxels when that is > 0 (tracker.py:123-125): one
+        ``select_tracts`` over the env's buffers.  Returns (packed points
+        (M, 3) f32, points per streamline (k,) i64, seeds (k, 3) f64 -- a host
+        tensor: ``env.initial_points`` at the downloaded row indices)."""
+        from tracktolearn_amd.parallel import select_tracts
+        n = env._n_total
+        points, counts, rows = select_tracts(
+            env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
+            scaled_min, scaled_max, tol_vox)
+        if n == 0:              # an empty shard of a sharded batch
+            seeds = np.zeros((0, 3), dtype=np.float64)
+        else:
+            seeds = np.ascontiguousarray(
+                np.asarray(env.initial_points)[rows.cpu().numpy()], dtype=np.float64)
+        return points, counts, torch.from_numpy(seeds.reshape(-1, 3))
+
+    def _batch_arrays_host(self, env, scaled_min, scaled_max):
+        """``device_output=False``: the length filter as torch expressions on
+        the device, no compression.  Returns (packed points (M, 3) f32, kept
+        lengths (k,) i64, seeds (k, 3) f64) as device tensors."""
         n = env._n_total
         from tracktolearn_amd.parallel import kept_lengths, pack_points
         if n == 0:              # an empty shard of a sharded batch
@@ -102,12 +130,18 @@ class Tracker(object):
             env.initial_points, dtype=np.float64)).to(hist.device)[sel]
         return points, keep_sel, seeds
 
-    def _batch_items(self, env, scaled_min, scaled_max, transform=None):
+    def _batch_items(self, env, scaled_min, scaled_max, transform=None, tol_vox=0.0):
         """(streamline, seed) pairs of the finished batch on this process;
         with a process group, every rank's pairs, on rank 0 only.
         ``transform`` (packed (M, 3) points -> packed points) is applied to the
-        whole batch before it is cut into streamlines."""
-        points, keep_sel, seeds = self._batch_arrays(env, scaled_min, scaled_max)
+        whole batch before it is cut into streamlines.  With the device output
+        stage the streamlines are already compressed to ``tol_vox`` (each rank
+        sends only the points it kept)."""
+        if self._device_output(env):
+            points, keep_sel, seeds = self._batch_arrays(env, scaled_min, scaled_max,
+                                                         tol_vox)
+        else:
+            points, keep_sel, seeds = self._batch_arrays_host(env, scaled_min, scaled_max)
         if self.group_size > 1:
             # gather-to-root of exact sizes: only rank 0 consumes the tracts
             from tracktolearn_amd.parallel import gather_ragged_to_root
@@ -127,6 +161,34 @@ class Tracker(object):
         for k in range(len(keep_np)):
             yield points[offsets[k]:offsets[k + 1]], seeds[k]
 
+    def batch_output(self, env, tracts_format):
+        """The output stage over the env's finished batch: the TractogramItems
+        ``track`` yields for it (length filter, compression, file space)."""
+        affine = env.affine_vox2rasmm
+        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
+        scaled_min_length = self.min_length / vox_size
+        scaled_max_length = self.max_length / vox_size
+        compress_th_vox = self.compress / vox_size
+        # .trk: the file-space conversion is element-wise, so it runs once over
+        # the packed batch -- bit for bit what the per-streamline call gives.
+        # On the host path only without compression, which there comes after
+        on_device = self._device_output(env)
+        whole_batch = tracts_format is TrkFile and (on_device or not self.compress)
+        for streamline, seed in self._batch_items(
+                env, scaled_min_length, scaled_max_length,
+                transform=(lambda p: to_file_space(p, TrkFile, affine, vox_size))
+                if whole_batch else None,
+                tol_vox=compress_th_vox if self.compress else 0.0):
+            if self.compress and not on_device:
+                streamline = compress_streamline(streamline, compress_th_vox)
+            if not whole_batch:
+                streamline = to_file_space(streamline, tracts_format,
+                                           affine, vox_size)
+            seed_dict = {}
+            if self.save_seeds:
+                seed_dict = {'seeds': seed - 0.5}
+            yield TractogramItem(streamline, seed_dict, {})
+
     def track(self, env, tracts_format):
         """Tracking only; a lazy tractogram whose iteration does the work
         (tracker.py:62-150).  Streamlines come out in the space the format
@@ -140,10 +202,6 @@ class Tracker(object):
         np.random.shuffle(env.seeds)
 
         def tracking_generator():
-            vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
-            scaled_min_length = self.min_length / vox_size
-            scaled_max_length = self.max_length / vox_size
-            compress_th_vox = self.compress / vox_size
             for start in tqdm(range(0, len(env.seeds), batch_size),
                               disable=self.rank != 0):
                 end = min(start + batch_size, len(env.seeds))
@@ -156,24 +214,7 @@ class Tracker(object):
                     self.alg.validation_episode(state, env, self.prob)
                 else:           # an empty shard still joins the collectives
                     env._n_total = 0
-                # .trk without compression (ttl_track's default): the file-space
-                # conversion is element-wise, so it runs once over the packed
-                # batch -- bit for bit what the per-streamline call gives
-                whole_batch = tracts_format is TrkFile and not self.compress
-                for streamline, seed in self._batch_items(
-                        env, scaled_min_length, scaled_max_length,
-                        transform=(lambda p: to_file_space(p, TrkFile, affine, vox_size))
-                        if whole_batch else None):
-                    if self.compress:
-                        streamline = compress_streamline(
-                            streamline, compress_th_vox)
-                    if not whole_batch:
-                        streamline = to_file_space(streamline, tracts_format,
-                                                   affine, vox_size)
-                    seed_dict = {}
-                    if self.save_seeds:
-                        seed_dict = {'seeds': seed - 0.5}
-                    yield TractogramItem(streamline, seed_dict, {})
+                yield from self.batch_output(env, tracts_format)
 
         tractogram = LazyTractogram.from_data_func(tracking_generator)
         tractogram.affine_to_rasmm = affine
