@@ -109,30 +109,25 @@ __device__ __forceinline__ void layer_norm(f16x &x, const float *g, const float 
     for (int a = 0; a < 16; ++a) x[a] = (x[a] - mean) * rstd * gg[a] + bb[a];
 }
 
+// x <- LayerNorm(x + fp16(y + bias)): the end of both halves of a layer (y a Linear's fp32
+// sums; Linear outputs are fp16 under autocast, the residual and the norm are not)
+__device__ __forceinline__ void add_and_norm(f16x &x, f16x &y, const float *bias, const float *g,
+                                             const float *b, int hi) {
+    add_rows(y, bias, hi);
+    round_fp16(y);
+#pragma unroll
+    for (int a = 0; a < 16; ++a) x[a] += y[a];
+    layer_norm(x, g, b, hi);
+}
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+
 // S <- 2^((S - m) scale) for the 64 scores of a lane (its query against 64 of the 128 keys),
 // returns their sum over all 128 keys.  Two scores per instruction: S scale - m scale as one
 // v_pk_fma_f32, the running sum as v_pk_add_f32 (the library is built with -ffp-contract=off,
 // so the compiler may not form the fma itself; the softmax is the largest block of VALU work
 // in the kernel, and the VALU, not the MFMA pipe, is what the kernel waits for).
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// (x[8 s .. 8 s + 7] * inv) as an fp16 operand fragment, two elements per instruction in the
-// register pairs the accumulator tile already has (written out so: left to itself the
-// vectoriser pairs elements (1,2), (3,4), (5,6), and pays for it in register copies and
-// v_alignbit shuffles -- a quarter of the attention block's instructions)
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ h8 scaled_frag(const f16x &x, int s, float inv) {
-    const f2 i2 = {inv, inv};
-    h2 q[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f2 v = f2{x[8 * s + 2 * j], x[8 * s + 2 * j + 1]} * i2;
-        q[j] = __builtin_convertvector(v, h2);
-    }
-    return h8{q[0].x, q[0].y, q[1].x, q[1].y, q[2].x, q[2].y, q[3].x, q[3].y};
-}
-
 __device__ __forceinline__ float softmax_numerators(f16x (&S)[NT], float m, float scale) {
     const f2 sc = {scale, scale};
     const float nm = -m * scale;
@@ -156,6 +151,57 @@ __device__ __forceinline__ float softmax_numerators(f16x (&S)[NT], float m, floa
     return l;
 }
 
+// (x[8 s .. 8 s + 7] * inv) as an fp16 operand fragment, two elements per instruction in the
+// register pairs the accumulator tile already has (written out so: left to itself the
+// vectoriser pairs elements (1,2), (3,4), (5,6), and pays for it in register copies and
+// v_alignbit shuffles -- a quarter of the attention block's instructions)
+__device__ __forceinline__ h8 scaled_frag(const f16x &x, int s, float inv) {
+    const f2 i2 = {inv, inv};
+    h2 q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const f2 v = f2{x[8 * s + 2 * j], x[8 * s + 2 * j + 1]} * i2;
+        q[j] = __builtin_convertvector(v, h2);
+    }
+    return h8{q[0].x, q[0].y, q[1].x, q[1].y, q[2].x, q[2].y, q[3].x, q[3].y};
+}
+
+// One packed layer: the device-side mirror of oracles/fused_net.py:pack_oracle_net, and the
+// only place in this file that knows its offsets.  Half fragments are indexed [..][lane]
+// (64 lanes of 8 halves), s = k-step of 16; float vectors are [2 lane halves][16] = the
+// accumulator rows of a lane (add_rows), except b_v, which is indexed by feature.
+struct LayerWeights {
+    const h8 *Wqk;              // [2 mt][2 s][64]: W_q, W_k
+    const h8 *Wv, *Wo;          // [2 s][64]
+    const h8 *W1, *W2;          // [C][2 s][64], C = ff / 32 chunks of hidden units
+    const float *bqk;           // [2][2][16]: b_q, b_k
+    const float *bv;            // [32]
+    const float *bo, *g1, *be1; // [2][16]: out-projection bias, LayerNorm 1
+    const float *b2, *g2, *be2; // [2][16]: second feed-forward bias, LayerNorm 2
+    const float *b1;            // [C][2][16]
+};
+
+__device__ __forceinline__ LayerWeights layer_weights(const NetArgs &P, int layer) {
+    const h8 *WH = reinterpret_cast<const h8 *>(P.wh) + (long long)layer * P.wh_stride;
+    const float *WF = P.wf + (long long)layer * P.wf_stride;
+    LayerWeights L;
+    L.Wqk = WH;
+    L.Wv = WH + 4 * 64;
+    L.Wo = WH + 6 * 64;
+    L.W1 = WH + 8 * 64;
+    L.W2 = L.W1 + (long long)P.ff_chunks * 2 * 64;
+    L.bqk = WF;
+    L.bv = WF + 64;
+    L.bo = WF + 96;
+    L.g1 = WF + 128;
+    L.be1 = WF + 160;
+    L.b2 = WF + 192;
+    L.g2 = WF + 224;
+    L.be2 = WF + 256;
+    L.b1 = WF + 288;
+    return L;
+}
+
 // b_1 of a layer (ff floats, [chunk][2 halves][16]) staged in LDS by the whole workgroup:
 // the feed-forward loop reads 64 bytes of it per lane and chunk, the same bytes in every lane
 // of a half -- through the vector L1 that costs as much of its 64 B/clk as the weights
@@ -163,11 +209,11 @@ __device__ __forceinline__ float softmax_numerators(f16x (&S)[NT], float m, floa
 // is a broadcast read on a pipe the kernel leaves idle.  Two buffers, one barrier per layer:
 // a wave can only reach the write of layer l + 2 after every wave has passed the barrier of
 // layer l + 1, i.e. finished reading layer l.
-__device__ __forceinline__ const float *stage_b1(float *lds, const NetArgs &P, int layer) {
+__device__ __forceinline__ const float *stage_b1(float *lds, const NetArgs &P,
+                                                 const LayerWeights &L, int layer) {
     const int ff = P.ff_chunks * 32;
     float *dst = lds + (layer & 1) * ff;
-    const float *b1 = P.wf + (long long)layer * P.wf_stride + 288;
-    const float4 *src = reinterpret_cast<const float4 *>(b1);
+    const float4 *src = reinterpret_cast<const float4 *>(L.b1);
     for (int i = threadIdx.x; i < ff / 4; i += blockDim.x)
         reinterpret_cast<float4 *>(dst)[i] = src[i];
     __syncthreads();
@@ -183,271 +229,71 @@ __device__ __forceinline__ void load_bias(const float *b1s, int c, int hi, float
     }
 }
 
-// One encoder layer on the wave's streamline.  NQ = 4: all four token tiles; NQ = 1 (the
-// last layer): keys and values of all tokens, but queries, out-projection, feed-forward and
-// LayerNorms of the first tile only (the head reads token 0).  A compile-time NQ keeps the
-// tile loops free of branches, so the scheduler interleaves the tiles' MFMA chains.
-template <int NHEAD, int NQ>
-__device__ __forceinline__ void encoder_layer(f16x (&hT)[NT], const NetArgs &P, int layer,
-                                              int lane, int n, int hi, float *lds) {
-    constexpr int DH = 32 / NHEAD;
-    const h8 *WH = reinterpret_cast<const h8 *>(P.wh) + (long long)layer * P.wh_stride;
-    const float *WF = P.wf + (long long)layer * P.wf_stride;
-    const h8 *Wqk = WH;                     // [2 mt][2 s][64]
-    const h8 *Wv = WH + 4 * 64;             // [2 s][64]
-    const h8 *Wo = WH + 6 * 64;             // [2 s][64]
-    const h8 *W1 = WH + 8 * 64;             // [C][2 s][64]
-    const h8 *W2 = W1 + (long long)P.ff_chunks * 2 * 64;
-    const float *bqk = WF;                  // [2][2][16]
-    const float *bv = WF + 64;              // [32]
-    const float *bo = WF + 96;              // [2][16]
-    const float *g1 = WF + 128, *be1 = WF + 160;
-    const float *b2 = WF + 192, *g2 = WF + 224, *be2 = WF + 256;
-    const float *b1s = stage_b1(lds, P, layer);     // b_1 [C][2][16], in LDS
-
-    // ---- Q^T, K^T [features x tokens] and V [tokens x features]
-    h8 QB[NQ][2], KA[NT][2], VA[NT][2];
-    {
-        const h8 wq0 = Wqk[0 * 64 + lane], wq1 = Wqk[1 * 64 + lane];
-        const h8 wk0 = Wqk[2 * 64 + lane], wk1 = Wqk[3 * 64 + lane];
-        const h8 wv0 = Wv[0 * 64 + lane], wv1 = Wv[1 * 64 + lane];
-        const float bvc = bv[n];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            // h^T as fp16 operand fragments (k = feature, permuted order)
-            h8 hB[2];
-            to_frags(hT[nt], hB);
-            if (nt < NQ) {
-                f16x q = mfma(wq1, hB[1], mfma(wq0, hB[0], zero16()));
-                add_rows(q, bqk, hi);
-                to_frags(q, QB[nt < NQ ? nt : 0]);
-            }
-            f16x k = mfma(wk1, hB[1], mfma(wk0, hB[0], zero16()));
-            add_rows(k, bqk + 32, hi);
-            to_frags(k, KA[nt]);
-            // V tile: rows = tokens of this tile, column (lane) = feature n
-            f16x v = mfma(hB[1], wv1, mfma(hB[0], wv0, zero16()));
-#pragma unroll
-            for (int a = 0; a < 16; ++a) v[a] += bvc;
-            to_frags(v, VA[nt]);
-        }
-    }
-
-    // ---- attention, one query tile at a time; out-projection, residual, LayerNorm 1
-    const float scale = 1.4426950408889634f / sqrtf((float)DH);     // log2(e) / sqrt(dh)
-#pragma unroll
-    for (int nt = 0; nt < NQ; ++nt) {
-        f16x OT = zero16();
-#pragma unroll
-        for (int h = 0; h < NHEAD; ++h) {
-            // scores S^T [keys x queries] of head h
-            f16x S[NT];
-#pragma unroll
-            for (int mt = 0; mt < NT; ++mt) {
-                if constexpr (NHEAD == 1) {
-                    S[mt] = mfma(KA[mt][1], QB[nt][1], mfma(KA[mt][0], QB[nt][0], zero16()));
-                } else if constexpr (NHEAD == 2) {
-                    S[mt] = mfma(KA[mt][h], QB[nt][h], zero16());
-                } else {
-                    // head h = features 8h..8h+7 = elements 4 (h & 1) .. +3 of k-step h >> 1
-                    h8 qm = QB[nt][h >> 1];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        if ((j >> 2) != (h & 1)) qm[j] = (_Float16)0.f;
-                    S[mt] = mfma(KA[mt][h >> 1], qm, zero16());
-                }
-            }
-            // softmax over the keys of each query (= over rows, per lane column)
-            float m = S[0][0];
-#pragma unroll
-            for (int mt = 0; mt < NT; ++mt)
-#pragma unroll
-                for (int a = 0; a < 16; ++a) m = fmaxf(m, S[mt][a]);
-            m = fmaxf(m, swap_halves(m));
-            const float l = softmax_numerators(S, m, scale);
-            const float inv = 1.f / l;
-            // O^T += V^T (rows of head h only) . P^T
-            const bool mine = (n / DH) == h;        // this lane's V column belongs to head h
-#pragma unroll
-            for (int mt = 0; mt < NT; ++mt) {
-                h8 PB[2];
-#pragma unroll
-                for (int s = 0; s < 2; ++s) PB[s] = scaled_frag(S[mt], s, inv);
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    h8 va = VA[mt][s];
-                    if constexpr (NHEAD > 1) {
-                        if (!mine) {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) va[j] = (_Float16)0.f;
-                        }
-                    }
-                    OT = mfma(va, PB[s], OT);
-                }
-            }
-        }
-        // out-projection on the fp16 attention output, residual, LayerNorm 1
-        h8 OB[2];
-        to_frags(OT, OB);
-        f16x o = mfma(Wo[64 + lane], OB[1], mfma(Wo[lane], OB[0], zero16()));
-        add_rows(o, bo, hi);
-        round_fp16(o);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) hT[nt][a] += o[a];
-        layer_norm(hT[nt], g1, be1, hi);
-    }
-
-    // ---- feed-forward: f^T = W_2 . relu(W_1 . h^T + b_1) + b_2, 32 hidden units at a time
-    h8 fB[NQ][2];
-    f16x D2[NQ];
-#pragma unroll
-    for (int nt = 0; nt < NQ; ++nt) {
-        to_frags(hT[nt], fB[nt]);
-        D2[nt] = zero16();
-    }
-    h8 w1a = W1[lane], w1b = W1[64 + lane], w2a = W2[lane], w2b = W2[64 + lane];
-    float bias[16];
-    load_bias(b1s, 0, hi, bias);
-    for (int c = 0; c < P.ff_chunks; ++c) {
-        // prefetch the next chunk's weights and bias while this one is multiplied
-        const int cn = c + 1 < P.ff_chunks ? c + 1 : c;
-        const h8 n1a = W1[(long long)cn * 128 + lane], n1b = W1[(long long)cn * 128 + 64 + lane];
-        const h8 n2a = W2[(long long)cn * 128 + lane], n2b = W2[(long long)cn * 128 + 64 + lane];
-        float nbias[16];
-        load_bias(b1s, cn, hi, nbias);
-        // the tiles' chains side by side: GEMM 1 of every tile (the bias rides in as the
-        // accumulator's initial value), the fp16 round + ReLU of every tile, GEMM 2
-        f16x d1[NQ];
-#pragma unroll
-        for (int nt = 0; nt < NQ; ++nt) {
-#pragma unroll
-            for (int a = 0; a < 16; ++a) d1[nt][a] = bias[a];
-            d1[nt] = mfma(w1a, fB[nt][0], d1[nt]);
-        }
-#pragma unroll
-        for (int nt = 0; nt < NQ; ++nt) d1[nt] = mfma(w1b, fB[nt][1], d1[nt]);
-        h8 F[NQ][2];
-#pragma unroll
-        for (int nt = 0; nt < NQ; ++nt)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    // Linear output in fp16, then ReLU
-                    const _Float16 u = (_Float16)d1[nt][8 * s + j];
-                    F[nt][s][j] = u > (_Float16)0.f ? u : (_Float16)0.f;
-                }
-#pragma unroll
-        for (int nt = 0; nt < NQ; ++nt) D2[nt] = mfma(w2a, F[nt][0], D2[nt]);
-#pragma unroll
-        for (int nt = 0; nt < NQ; ++nt) D2[nt] = mfma(w2b, F[nt][1], D2[nt]);
-        w1a = n1a; w1b = n1b; w2a = n2a; w2b = n2b;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) bias[a] = nbias[a];
-    }
-#pragma unroll
-    for (int nt = 0; nt < NQ; ++nt) {
-        add_rows(D2[nt], b2, hi);
-        round_fp16(D2[nt]);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) hT[nt][a] += D2[nt][a];
-        layer_norm(hT[nt], g2, be2, hi);
-    }
+// The four weight fragments of feed-forward chunk c: W_1 k-steps 0, 1, W_2 k-steps 0, 1
+__device__ __forceinline__ void load_ff_weights(const h8 *W1, const h8 *W2, int c, int lane,
+                                                h8 (&wt)[4]) {
+    wt[0] = W1[(long long)c * 128 + lane];
+    wt[1] = W1[(long long)c * 128 + 64 + lane];
+    wt[2] = W2[(long long)c * 128 + lane];
+    wt[3] = W2[(long long)c * 128 + 64 + lane];
 }
 
-template <int NHEAD>
-__global__ __launch_bounds__(256, 1) void k_oracle_net(NetArgs P) {
-    extern __shared__ __align__(16) float b1_lds[];              // [2][ff]
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    long long row = (long long)blockIdx.x * 4 + wv;              // one wave per streamline
-    // (a wave past the end works on the last streamline again and stores nothing: the
-    // workgroup's barriers need every wave)
-    const bool live = row < P.n;
-    if (!live) row = P.n - 1;
+// Token tile `tile` of the embedded sequence: relu(W_e x + b_e) * sqrt(32) + positional
+// encoding, x = the CLS token at token 0 and segment t - 1 of `dirs` at token t
+__device__ __forceinline__ f16x embed_tile(const NetArgs &P, const float *dirs, int tile,
+                                           int lane) {
     const int n = lane & 31, hi = lane >> 5;
-    const float *dirs = P.dirs + row * (127 * 3);
-
-    // ---- embedding: relu(W_e x + b_e) * sqrt(32) + positional encoding
-    f16x hT[NT];
-    {
-        const float *E = P.embed + hi * 64;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int t = 32 * nt + n;
-            float x0, x1, x2;
-            if (t == 0) {
-                x0 = P.cls[0]; x1 = P.cls[1]; x2 = P.cls[2];
-            } else {
-                const float *d = dirs + (t - 1) * 3;
-                x0 = d[0]; x1 = d[1]; x2 = d[2];
-            }
-            // autocast: inputs and weights of the Linear in fp16, fp32 accumulation,
-            // fp16 result; ReLU and the sqrt(32) scale in fp16; the table add in fp32
-            x0 = (float)(_Float16)x0; x1 = (float)(_Float16)x1; x2 = (float)(_Float16)x2;
-            const float *pe = P.pe + ((long long)nt * 64 + lane) * 16;
-#pragma unroll
-            for (int a = 0; a < 16; ++a) {
-                float e = E[4 * a + 0] * x0 + E[4 * a + 1] * x1 + E[4 * a + 2] * x2 + E[4 * a + 3];
-                e = (float)(_Float16)e;
-                e = e > 0.f ? e : 0.f;
-                e = (float)(_Float16)(e * (float)(_Float16)5.656854249492381f);
-                hT[nt][a] = e + pe[a];
-            }
-        }
+    const float *E = P.embed + hi * 64;
+    const int t = 32 * tile + n;
+    float x0, x1, x2;
+    if (t == 0) {
+        x0 = P.cls[0]; x1 = P.cls[1]; x2 = P.cls[2];
+    } else {
+        const float *d = dirs + (t - 1) * 3;
+        x0 = d[0]; x1 = d[1]; x2 = d[2];
     }
-
-    for (int layer = 0; layer + 1 < P.n_layers; ++layer)
-        encoder_layer<NHEAD, NT>(hT, P, layer, lane, n, hi, b1_lds);
-    encoder_layer<NHEAD, 1>(hT, P, P.n_layers - 1, lane, n, hi, b1_lds);
-
-    // ---- head on the CLS position (token 0 = tile 0, lane column 0 of both halves)
-    float dot = 0.f;
-    {
-        const float *w = P.head + hi * 16;
+    // autocast: inputs and weights of the Linear in fp16, fp32 accumulation,
+    // fp16 result; ReLU and the sqrt(32) scale in fp16; the table add in fp32
+    x0 = (float)(_Float16)x0; x1 = (float)(_Float16)x1; x2 = (float)(_Float16)x2;
+    const float *pe = P.pe + ((long long)tile * 64 + lane) * 16;
+    f16x h;
 #pragma unroll
-        for (int a = 0; a < 16; ++a)
-            dot += (float)(_Float16)hT[0][a] * (float)(_Float16)w[a];
+    for (int a = 0; a < 16; ++a) {
+        float e = E[4 * a + 0] * x0 + E[4 * a + 1] * x1 + E[4 * a + 2] * x2 + E[4 * a + 3];
+        e = (float)(_Float16)e;
+        e = e > 0.f ? e : 0.f;
+        e = (float)(_Float16)(e * (float)(_Float16)5.656854249492381f);
+        h[a] = e + pe[a];
     }
-    dot += swap_halves(dot);
-    if (lane == 0 && live) {
-        float y = (float)(_Float16)(dot + (float)(_Float16)P.head[32]);
-        y = 1.f / (1.f + expf(-y));
-        P.out[row] = (float)(_Float16)y;
-    }
+    return h;
 }
 
-// ------------------------------------------------------------------------
-// The same network with one WORKGROUP per streamline: each of its four waves
-// owns one 32-token tile (16 accumulator registers of h^T instead of 64), the
-// keys and values of all tiles meet in LDS once per layer (16 KB), everything
-// else stays wave-private.  A quarter of the dependent work per wave: the
-// latency of one streamline drops ~3x, and at <= 256 registers two workgroups
-// share a CU, so one wave's conversions and softmax run under another's MFMAs.
-// In the last layer only wave 0 (the tile of token 0) goes on after K / V.
-// ------------------------------------------------------------------------
+// The head on the CLS position (token 0 = tile 0, lane column 0 of both halves): the score
+// that lane 0 stores
+__device__ __forceinline__ float cls_score(const f16x &hT0, const NetArgs &P, int hi) {
+    float dot = 0.f;
+    const float *w = P.head + hi * 16;
+#pragma unroll
+    for (int a = 0; a < 16; ++a) dot += (float)(_Float16)hT0[a] * (float)(_Float16)w[a];
+    dot += swap_halves(dot);
+    float y = (float)(_Float16)(dot + (float)(_Float16)P.head[32]);
+    y = 1.f / (1.f + expf(-y));
+    return (float)(_Float16)y;
+}
+
+// Attention of one query tile against the keys and values of all tiles (register fragments),
+// out-projection on the fp16 attention output, residual, LayerNorm 1: hT is the tile's h^T,
+// QB its queries.
 template <int NHEAD>
 __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
-                                               const h8 (*kv)[NT][2][64], const NetArgs &P,
-                                               int layer, int lane, int n, int hi) {
+                                               const h8 (&KA)[NT][2], const h8 (&VA)[NT][2],
+                                               const LayerWeights &L, int lane, int n, int hi) {
     constexpr int DH = 32 / NHEAD;
-    const h8 *WH = reinterpret_cast<const h8 *>(P.wh) + (long long)layer * P.wh_stride;
-    const float *WF = P.wf + (long long)layer * P.wf_stride;
-    const h8 *Wo = WH + 6 * 64;
-    const float *bo = WF + 96;
-    const float *g1 = WF + 128, *be1 = WF + 160;
-
-    h8 KA[NT][2], VA[NT][2];
-#pragma unroll
-    for (int mt = 0; mt < NT; ++mt)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            KA[mt][s] = kv[0][mt][s][lane];
-            VA[mt][s] = kv[1][mt][s][lane];
-        }
     const float scale = 1.4426950408889634f / sqrtf((float)DH);     // log2(e) / sqrt(dh)
     f16x OT = zero16();
 #pragma unroll
     for (int h = 0; h < NHEAD; ++h) {
+        // scores S^T [keys x queries] of head h
         f16x S[NT];
 #pragma unroll
         for (int mt = 0; mt < NT; ++mt) {
@@ -456,6 +302,7 @@ __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
             } else if constexpr (NHEAD == 2) {
                 S[mt] = mfma(KA[mt][h], QB[h], zero16());
             } else {
+                // head h = features 8h..8h+7 = elements 4 (h & 1) .. +3 of k-step h >> 1
                 h8 qm = QB[h >> 1];
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
@@ -463,6 +310,7 @@ __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
                 S[mt] = mfma(KA[mt][h >> 1], qm, zero16());
             }
         }
+        // softmax over the keys of each query (= over rows, per lane column)
         float m = S[0][0];
 #pragma unroll
         for (int mt = 0; mt < NT; ++mt)
@@ -471,7 +319,8 @@ __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
         m = fmaxf(m, swap_halves(m));
         const float l = softmax_numerators(S, m, scale);
         const float inv = 1.f / l;
-        const bool mine = (n / DH) == h;
+        // O^T += V^T (rows of head h only) . P^T
+        const bool mine = (n / DH) == h;        // this lane's V column belongs to head h
 #pragma unroll
         for (int mt = 0; mt < NT; ++mt) {
             h8 PB[2];
@@ -492,13 +341,148 @@ __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
     }
     h8 OB[2];
     to_frags(OT, OB);
-    f16x o = mfma(Wo[64 + lane], OB[1], mfma(Wo[lane], OB[0], zero16()));
-    add_rows(o, bo, hi);
-    round_fp16(o);
-#pragma unroll
-    for (int a = 0; a < 16; ++a) hT[a] += o[a];
-    layer_norm(hT, g1, be1, hi);
+    f16x o = mfma(L.Wo[64 + lane], OB[1], mfma(L.Wo[lane], OB[0], zero16()));
+    add_and_norm(hT, o, L.bo, L.g1, L.be1, hi);
 }
+
+// One chunk of 32 hidden units of the feed-forward block for N token tiles side by side:
+// D2[t] += W_2 chunk . relu(fp16(W_1 chunk . fB[t] + bias)).  The tiles' chains are issued
+// next to each other: GEMM 1 of every tile (the bias rides in as the accumulator's initial
+// value), the fp16 round + ReLU of every tile, GEMM 2.
+template <int N>
+__device__ __forceinline__ void ff_chunk(const h8 (&wt)[4], const float (&bias)[16],
+                                         const h8 (*fB)[2], f16x *D2) {
+    f16x d1[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+#pragma unroll
+        for (int a = 0; a < 16; ++a) d1[t][a] = bias[a];
+        d1[t] = mfma(wt[0], fB[t][0], d1[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < N; ++t) d1[t] = mfma(wt[1], fB[t][1], d1[t]);
+    h8 F[N][2];
+#pragma unroll
+    for (int t = 0; t < N; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                // Linear output in fp16, then ReLU
+                const _Float16 u = (_Float16)d1[t][8 * s + j];
+                F[t][s][j] = u > (_Float16)0.f ? u : (_Float16)0.f;
+            }
+#pragma unroll
+    for (int t = 0; t < N; ++t) D2[t] = mfma(wt[2], F[t][0], D2[t]);
+#pragma unroll
+    for (int t = 0; t < N; ++t) D2[t] = mfma(wt[3], F[t][1], D2[t]);
+}
+
+// One encoder layer on the wave's streamline.  NQ = 4: all four token tiles; NQ = 1 (the
+// last layer): keys and values of all tokens, but queries, out-projection, feed-forward and
+// LayerNorms of the first tile only (the head reads token 0).  A compile-time NQ keeps the
+// tile loops free of branches, so the scheduler interleaves the tiles' MFMA chains.
+template <int NHEAD, int NQ>
+__device__ __forceinline__ void encoder_layer(f16x (&hT)[NT], const NetArgs &P, int layer,
+                                              int lane, int n, int hi, float *lds) {
+    const LayerWeights L = layer_weights(P, layer);
+    const float *b1s = stage_b1(lds, P, L, layer);
+
+    // ---- Q^T, K^T [features x tokens] and V [tokens x features]
+    h8 QB[NQ][2], KA[NT][2], VA[NT][2];
+    {
+        const h8 wq0 = L.Wqk[0 * 64 + lane], wq1 = L.Wqk[1 * 64 + lane];
+        const h8 wk0 = L.Wqk[2 * 64 + lane], wk1 = L.Wqk[3 * 64 + lane];
+        const h8 wv0 = L.Wv[0 * 64 + lane], wv1 = L.Wv[1 * 64 + lane];
+        const float bvc = L.bv[n];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            // h^T as fp16 operand fragments (k = feature, permuted order)
+            h8 hB[2];
+            to_frags(hT[nt], hB);
+            if (nt < NQ) {
+                f16x q = mfma(wq1, hB[1], mfma(wq0, hB[0], zero16()));
+                add_rows(q, L.bqk, hi);
+                to_frags(q, QB[nt < NQ ? nt : 0]);
+            }
+            f16x k = mfma(wk1, hB[1], mfma(wk0, hB[0], zero16()));
+            add_rows(k, L.bqk + 32, hi);
+            to_frags(k, KA[nt]);
+            // V tile: rows = tokens of this tile, column (lane) = feature n
+            f16x v = mfma(hB[1], wv1, mfma(hB[0], wv0, zero16()));
+#pragma unroll
+            for (int a = 0; a < 16; ++a) v[a] += bvc;
+            to_frags(v, VA[nt]);
+        }
+    }
+
+    // ---- attention, one query tile at a time; out-projection, residual, LayerNorm 1
+#pragma unroll
+    for (int nt = 0; nt < NQ; ++nt) attention_tile<NHEAD>(hT[nt], QB[nt], KA, VA, L, lane, n, hi);
+
+    // ---- feed-forward: f^T = W_2 . relu(W_1 . h^T + b_1) + b_2, 32 hidden units at a time,
+    // all NQ tiles per chunk on one accumulator each
+    h8 fB[NQ][2];
+    f16x D2[NQ];
+#pragma unroll
+    for (int nt = 0; nt < NQ; ++nt) {
+        to_frags(hT[nt], fB[nt]);
+        D2[nt] = zero16();
+    }
+    h8 wt[4];
+    load_ff_weights(L.W1, L.W2, 0, lane, wt);
+    float bias[16];
+    load_bias(b1s, 0, hi, bias);
+    for (int c = 0; c < P.ff_chunks; ++c) {
+        // prefetch the next chunk's weights and bias while this one is multiplied
+        const int cn = c + 1 < P.ff_chunks ? c + 1 : c;
+        h8 nw[4];
+        load_ff_weights(L.W1, L.W2, cn, lane, nw);
+        float nbias[16];
+        load_bias(b1s, cn, hi, nbias);
+        ff_chunk<NQ>(wt, bias, fB, D2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wt[k] = nw[k];
+#pragma unroll
+        for (int a = 0; a < 16; ++a) bias[a] = nbias[a];
+    }
+#pragma unroll
+    for (int nt = 0; nt < NQ; ++nt) add_and_norm(hT[nt], D2[nt], L.b2, L.g2, L.be2, hi);
+}
+
+template <int NHEAD>
+__global__ __launch_bounds__(256, 1) void k_oracle_net(NetArgs P) {
+    extern __shared__ __align__(16) float b1_lds[];              // [2][ff]
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long long row = (long long)blockIdx.x * 4 + wv;              // one wave per streamline
+    // (a wave past the end works on the last streamline again and stores nothing: the
+    // workgroup's barriers need every wave)
+    const bool live = row < P.n;
+    if (!live) row = P.n - 1;
+    const int n = lane & 31, hi = lane >> 5;
+    const float *dirs = P.dirs + row * (127 * 3);
+
+    f16x hT[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) hT[nt] = embed_tile(P, dirs, nt, lane);
+
+    for (int layer = 0; layer + 1 < P.n_layers; ++layer)
+        encoder_layer<NHEAD, NT>(hT, P, layer, lane, n, hi, b1_lds);
+    encoder_layer<NHEAD, 1>(hT, P, P.n_layers - 1, lane, n, hi, b1_lds);
+
+    const float score = cls_score(hT[0], P, hi);
+    if (lane == 0 && live) P.out[row] = score;
+}
+
+// ------------------------------------------------------------------------
+// The same network with one WORKGROUP per streamline: each of its four waves
+// owns one 32-token tile (16 accumulator registers of h^T instead of 64), the
+// keys and values of all tiles meet in LDS once per layer (16 KB), everything
+// else stays wave-private.  A quarter of the dependent work per wave: the
+// latency of one streamline drops ~3x, and at <= 256 registers two workgroups
+// share a CU, so one wave's conversions and softmax run under another's MFMAs.
+// In the last layer only wave 0 (the tile of token 0) goes on after K / V.
+// ------------------------------------------------------------------------
 
 // Feed-forward block of the workgroup's streamline, split over the HIDDEN units: wave w takes
 // the chunks c = w, w + 4, ... for ALL token tiles (NQT = 4; 1 in the last layer, which only
@@ -513,13 +497,8 @@ __device__ __forceinline__ void attention_tile(f16x &hT, const h8 (&QB)[2],
 template <int NQT>
 __device__ __forceinline__ void ff_hidden_split(f16x &hT, const h8 (*fbuf)[2][64],
                                                 float4 (*pbuf)[4][64], const NetArgs &P,
-                                                int layer, int lane, int hi, int w,
+                                                const LayerWeights &L, int lane, int hi, int w,
                                                 const float *b1s) {
-    const h8 *WH = reinterpret_cast<const h8 *>(P.wh) + (long long)layer * P.wh_stride;
-    const float *WF = P.wf + (long long)layer * P.wf_stride;
-    const h8 *W1 = WH + 8 * 64;
-    const h8 *W2 = W1 + (long long)P.ff_chunks * 2 * 64;
-    const float *b2 = WF + 192, *g2 = WF + 224, *be2 = WF + 256;
     const int C = P.ff_chunks;
 
     h8 fB[NQT][2];
@@ -530,49 +509,19 @@ __device__ __forceinline__ void ff_hidden_split(f16x &hT, const h8 (*fbuf)[2][64
         fB[t][1] = fbuf[t][1][lane];
         D2[t] = zero16();
     }
-    auto load = [&](int c, h8 (&wt)[4]) {
-        wt[0] = W1[(long long)c * 128 + lane];
-        wt[1] = W1[(long long)c * 128 + 64 + lane];
-        wt[2] = W2[(long long)c * 128 + lane];
-        wt[3] = W2[(long long)c * 128 + 64 + lane];
-    };
     h8 wt[4];
-    if (w < C) load(w, wt);
+    if (w < C) load_ff_weights(L.W1, L.W2, w, lane, wt);
     for (int c = w; c < C; c += 4) {
         h8 nw[4];
-        load(c + 4 < C ? c + 4 : c, nw);        // this wave's next chunk, one ahead
+        load_ff_weights(L.W1, L.W2, c + 4 < C ? c + 4 : c, lane, nw);   // this wave's next chunk
         // two token tiles at a time: two independent MFMA chains, half the transient registers
         // (the bias comes from LDS again for each pair: four broadcast reads, no registers held)
+        constexpr int PAIR = NQT > 1 ? 2 : 1;
 #pragma unroll
-        for (int t0 = 0; t0 < NQT; t0 += 2) {
-            constexpr int one = 1;
-            const int t1 = t0 + one < NQT ? t0 + one : t0;
+        for (int t0 = 0; t0 < NQT; t0 += PAIR) {
             float bias[16];
             load_bias(b1s, c, hi, bias);
-            f16x da, db;
-#pragma unroll
-            for (int a = 0; a < 16; ++a) {
-                da[a] = bias[a];
-                db[a] = bias[a];
-            }
-            da = mfma(wt[0], fB[t0][0], da);
-            if (NQT > 1) db = mfma(wt[0], fB[t1][0], db);
-            da = mfma(wt[1], fB[t0][1], da);
-            if (NQT > 1) db = mfma(wt[1], fB[t1][1], db);
-            h8 FA[2], FB2[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    // Linear output in fp16, then ReLU
-                    const _Float16 u = (_Float16)da[8 * s + j], v = (_Float16)db[8 * s + j];
-                    FA[s][j] = u > (_Float16)0.f ? u : (_Float16)0.f;
-                    FB2[s][j] = v > (_Float16)0.f ? v : (_Float16)0.f;
-                }
-            D2[t0] = mfma(wt[2], FA[0], D2[t0]);
-            if (NQT > 1) D2[t1] = mfma(wt[2], FB2[0], D2[t1]);
-            D2[t0] = mfma(wt[3], FA[1], D2[t0]);
-            if (NQT > 1) D2[t1] = mfma(wt[3], FB2[1], D2[t1]);
+            ff_chunk<PAIR>(wt, bias, fB + t0, D2 + t0);
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) wt[k] = nw[k];
@@ -611,11 +560,7 @@ __device__ __forceinline__ void ff_hidden_split(f16x &hT, const h8 (*fbuf)[2][64
                 }
             }
         }
-        add_rows(sum, b2, hi);
-        round_fp16(sum);
-#pragma unroll
-        for (int a = 0; a < 16; ++a) hT[a] += sum[a];
-        layer_norm(hT, g2, be2, hi);
+        add_and_norm(hT, sum, L.b2, L.g2, L.be2, hi);
     }
     __syncthreads();            // the partials' memory is the next layer's keys and values
 }
@@ -662,47 +607,23 @@ __global__ __launch_bounds__(256, 2) void k_oracle_net_wg(NetArgs P) {
         asm volatile("" : "+v"(warm));
     }
 
-    f16x hT;
-    {
-        const float *E = P.embed + hi * 64;
-        const int t = 32 * w + n;
-        float x0, x1, x2;
-        if (t == 0) {
-            x0 = P.cls[0]; x1 = P.cls[1]; x2 = P.cls[2];
-        } else {
-            const float *d = dirs + (t - 1) * 3;
-            x0 = d[0]; x1 = d[1]; x2 = d[2];
-        }
-        x0 = (float)(_Float16)x0; x1 = (float)(_Float16)x1; x2 = (float)(_Float16)x2;
-        const float *pe = P.pe + ((long long)w * 64 + lane) * 16;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) {
-            float e = E[4 * a + 0] * x0 + E[4 * a + 1] * x1 + E[4 * a + 2] * x2 + E[4 * a + 3];
-            e = (float)(_Float16)e;
-            e = e > 0.f ? e : 0.f;
-            e = (float)(_Float16)(e * (float)(_Float16)5.656854249492381f);
-            hT[a] = e + pe[a];
-        }
-    }
+    f16x hT = embed_tile(P, dirs, w, lane);
 
     for (int layer = 0; layer < P.n_layers; ++layer) {
         const bool last = layer == P.n_layers - 1;
         const bool goes_on = !last || w == 0;       // the last layer only feeds token 0's tile
-        const h8 *WH = reinterpret_cast<const h8 *>(P.wh) + (long long)layer * P.wh_stride;
-        const float *WF = P.wf + (long long)layer * P.wf_stride;
-        const h8 *Wqk = WH, *Wv = WH + 4 * 64;
-        const float *bqk = WF, *bv = WF + 64;
+        const LayerWeights L = layer_weights(P, layer);
         h8 hB[2], QB[2];
         to_frags(hT, hB);
         {
-            f16x k = mfma(Wqk[3 * 64 + lane], hB[1], mfma(Wqk[2 * 64 + lane], hB[0], zero16()));
-            add_rows(k, bqk + 32, hi);
+            f16x k = mfma(L.Wqk[3 * 64 + lane], hB[1], mfma(L.Wqk[2 * 64 + lane], hB[0], zero16()));
+            add_rows(k, L.bqk + 32, hi);
             h8 f[2];
             to_frags(k, f);
             kv[0][w][0][lane] = f[0];
             kv[0][w][1][lane] = f[1];
-            f16x v = mfma(hB[1], Wv[64 + lane], mfma(hB[0], Wv[lane], zero16()));
-            const float bvc = bv[n];
+            f16x v = mfma(hB[1], L.Wv[64 + lane], mfma(hB[0], L.Wv[lane], zero16()));
+            const float bvc = L.bv[n];
 #pragma unroll
             for (int a = 0; a < 16; ++a) v[a] += bvc;
             to_frags(v, f);
@@ -710,13 +631,22 @@ __global__ __launch_bounds__(256, 2) void k_oracle_net_wg(NetArgs P) {
             kv[1][w][1][lane] = f[1];
         }
         if (goes_on) {
-            f16x q = mfma(Wqk[64 + lane], hB[1], mfma(Wqk[lane], hB[0], zero16()));
-            add_rows(q, bqk, hi);
+            f16x q = mfma(L.Wqk[64 + lane], hB[1], mfma(L.Wqk[lane], hB[0], zero16()));
+            add_rows(q, L.bqk, hi);
             to_frags(q, QB);
         }
-        const float *b1s = stage_b1(b1_lds, P, layer);      // its barrier also publishes kv
+        const float *b1s = stage_b1(b1_lds, P, L, layer);   // its barrier also publishes kv
         if (goes_on) {
-            attention_tile<NHEAD>(hT, QB, kv, P, layer, lane, n, hi);
+            // keys and values of all tiles, from LDS
+            h8 KA[NT][2], VA[NT][2];
+#pragma unroll
+            for (int mt = 0; mt < NT; ++mt)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    KA[mt][s] = kv[0][mt][s][lane];
+                    VA[mt][s] = kv[1][mt][s][lane];
+                }
+            attention_tile<NHEAD>(hT, QB, KA, VA, L, lane, n, hi);
             // h^T of this tile after LayerNorm 1, as operand fragments, for every wave
             h8 f[2];
             to_frags(hT, f);
@@ -724,21 +654,13 @@ __global__ __launch_bounds__(256, 2) void k_oracle_net_wg(NetArgs P) {
             fbuf[w][1][lane] = f[1];
         }
         __syncthreads();                            // everybody is done with kv as well
-        if (last) ff_hidden_split<1>(hT, fbuf, pbuf, P, layer, lane, hi, w, b1s);
-        else ff_hidden_split<NT>(hT, fbuf, pbuf, P, layer, lane, hi, w, b1s);
+        if (last) ff_hidden_split<1>(hT, fbuf, pbuf, P, L, lane, hi, w, b1s);
+        else ff_hidden_split<NT>(hT, fbuf, pbuf, P, L, lane, hi, w, b1s);
     }
 
     if (w == 0) {
-        float dot = 0.f;
-        const float *wh = P.head + hi * 16;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) dot += (float)(_Float16)hT[a] * (float)(_Float16)wh[a];
-        dot += swap_halves(dot);
-        if (lane == 0) {
-            float y = (float)(_Float16)(dot + (float)(_Float16)P.head[32]);
-            y = 1.f / (1.f + expf(-y));
-            P.out[row] = (float)(_Float16)y;
-        }
+        const float score = cls_score(hT, P, hi);
+        if (lane == 0) P.out[row] = score;
     }
     // (keeps the warming loads alive; weights are finite halves, the pattern cannot occur)
     if (warm == 0xfff1fff2u && P.n < 0) P.out[row] = 0.f;
@@ -821,25 +743,16 @@ int ttl_oracle_net_forward(const float *dirs, int64_t n, const void *packed_half
     // k_oracle_net_wg: pbuf 48 KB + fbuf 8 KB = 56 KB, 72 KB / 120 KB in all; k_oracle_net:
     // none.  The device gives a workgroup 160 KB (gfx950).
     const size_t lds = (size_t)2 * ff_dim * sizeof(float);
+    // [workgroup kernel?][1 / 2 / 4 heads]; slot 3 wg + which is the kernel's entry in reserve_lds
+    static void (*const kernels[2][3])(NetArgs) = {
+        {k_oracle_net<1>, k_oracle_net<2>, k_oracle_net<4>},
+        {k_oracle_net_wg<1>, k_oracle_net_wg<2>, k_oracle_net_wg<4>}};
     const int which = n_head == 1 ? 0 : n_head == 2 ? 1 : 2;
-    const void *kernel = wg ? (which == 0 ? (const void *)k_oracle_net_wg<1>
-                               : which == 1 ? (const void *)k_oracle_net_wg<2>
-                                            : (const void *)k_oracle_net_wg<4>)
-                            : (which == 0 ? (const void *)k_oracle_net<1>
-                               : which == 1 ? (const void *)k_oracle_net<2>
-                                            : (const void *)k_oracle_net<4>);
-    if (int rc = reserve_lds(kernel, (wg ? 3 : 0) + which, lds, ff_dim)) return rc;
-    if (wg) {
-        const dim3 grid((unsigned)n), block(256);
-        if (n_head == 1) k_oracle_net_wg<1><<<grid, block, lds, s>>>(P);
-        else if (n_head == 2) k_oracle_net_wg<2><<<grid, block, lds, s>>>(P);
-        else k_oracle_net_wg<4><<<grid, block, lds, s>>>(P);
-    } else {
-        const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-        if (n_head == 1) k_oracle_net<1><<<grid, block, lds, s>>>(P);
-        else if (n_head == 2) k_oracle_net<2><<<grid, block, lds, s>>>(P);
-        else k_oracle_net<4><<<grid, block, lds, s>>>(P);
-    }
+    const auto kernel = kernels[wg][which];
+    if (int rc = reserve_lds((const void *)kernel, 3 * wg + which, lds, ff_dim)) return rc;
+    // one workgroup of four waves per streamline, or per four streamlines
+    const dim3 grid((unsigned)(wg ? n : (n + 3) / 4)), block(256);
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, P);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         return fail(TTL_ERR_HIP, "k_oracle_net: %s", hipGetErrorString(e));
