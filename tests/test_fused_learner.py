@@ -662,6 +662,81 @@ def test_td3_ddpg_schedule_equals_autograd_in_float64(cls_name, hidden, monkeypa
     assert fused.total_it == ref.total_it == 4
 
 
+# the launch lists of DESIGN 3.6 for two hidden layers, a phase per line (the
+# GEMMs by the torch call that issues them; SACAuto without its two `randn`)
+SACAUTO_LAUNCHES = """
+    build_inputs
+    addmm_activation addmm_activation thin_forward
+    addmm_activation addmm_activation addmm_activation thin_forward
+    addmm_activation addmm_activation addmm_activation thin_forward
+    sac_losses
+    thin_backward mm mm mm mm relu_backward_bias mm colsum_finalize
+    actor_head_backward
+    thin_backward mm mm relu_backward_bias mm colsum_finalize
+    alpha_step adam_polyak adam_polyak
+""".split()
+TD3_LAUNCHES = """
+    build_inputs
+    addmm_activation addmm_activation thin_forward
+    addmm_activation addmm_activation addmm_activation thin_forward
+    addmm_activation addmm_activation addmm_activation thin_forward
+    td3_losses
+    thin_backward mm mm mm mm relu_backward_bias mm colsum_finalize
+    adam_polyak
+    addmm_activation addmm_activation thin_forward
+    addmm_activation addmm_activation thin_forward
+    thin_backward mm actor_head_backward
+    thin_backward mm mm relu_backward_bias mm colsum_finalize
+    adam_polyak polyak
+""".split()
+
+
+class _RecordingOps:
+    """TorchOps that notes the name of every kernel call in ``names``."""
+
+    def __init__(self, names):
+        self._ops, self._names = TorchOps(), names
+
+    def __getattr__(self, name):
+        fn = getattr(self._ops, name)
+
+        def call(*args, **kw):
+            self._names.append(name)
+            return fn(*args, **kw)
+        return call
+
+
+def test_updates_issue_the_documented_launch_sequence(monkeypatch):
+    """One SACAuto update and one TD3 update with an actor step, hidden 32-32:
+    the kernels and GEMMs in the order DESIGN 3.6 lists them (names only:
+    16 GEMMs + 15 kernel calls for SACAuto)."""
+    from tracktolearn_amd.algorithms.sac_auto import SACAuto
+    W, B = 27, 64
+    names = []
+
+    def noting(name, fn):
+        def call(*args, **kw):
+            names.append(name)
+            return fn(*args, **kw)
+        return call
+    monkeypatch.setattr(torch, 'mm', noting('mm', torch.mm))
+    monkeypatch.setattr(torch, '_addmm_activation',
+                        noting('addmm_activation', torch._addmm_activation))
+    (batch, eps), = _batches(1, B, W, torch.float64)
+    _, sac = _pair(SACAuto, '32-32', W, B, torch.float64, ops=_RecordingOps(names))
+    _inject(sac, eps)
+    sac.update(batch)
+    assert sac._fused is not None
+    assert names == SACAUTO_LAUNCHES
+    assert len(names) == 31 and sum(n in ('mm', 'addmm_activation') for n in names) == 16
+    del names[:]
+    _, td3 = _det_pair('TD3', '32-32', W, B, torch.float64, ops=_RecordingOps(names))
+    td3.total_it = 1                                   # the second update steps the actor
+    td3.update(batch)
+    assert td3._fused is not None
+    assert names == TD3_LAUNCHES
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('cls_name,hidden,W,B', [('TD3', '1024-1024', 327, 4096),
                                                  ('TD3', '96-64-48', 45, 500),

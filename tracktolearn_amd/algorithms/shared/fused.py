@@ -1,4 +1,4 @@
-"""The MI355X form of one SAC / SACAuto gradient update.
+"""The MI355X form of one SAC / SACAuto / TD3 / DDPG gradient update.
 
 The reference's update (TrackToLearn/algorithms/sac_auto.py:139-250,
 sac.py:135-232) is PyTorch autograd over three MLPs + three
@@ -31,11 +31,34 @@ hand-scheduled forward/backward:
   actor-loss gradient through the critics' first layer, Adam + Polyak.
   Reductions are deterministic (slab partials, fixed order).
 
+``FusedTD3Update`` is the TD3 update (td3.py:130-230) and, with the single
+critic and an actor step in every update, the DDPG update (ddpg.py:234-319)
+on the same arenas, buffers and kernels.  Its order is the reference's, not
+SAC's: the critic regression first -- target actor on rows [2B,3B) with the
+smoothing noise added (and, for TD3, clamped) in place in ``xs``, target and
+online critics of B rows each, the critics' backward and their Adam step --
+and then, every ``agent_freq``-th update, the actor on rows [B,2B) through the
+UPDATED first critic alone (buffers ``h1`` / ``dz1``, data gradients only), the
+actor's Adam + Polyak and the critics' Polyak as a pass of its own.
+
+Both schedules are made of the same passes, each stated once in
+``_FusedNets``: the hidden stack's forward (``_hidden_forward``), the stacked
+critics' forward and backward (``_critics_forward``, ``_critics_backward``), the
+actor's backward (``_actor_backward``), over buffers laid out by
+``_alloc_shared`` / ``_critic_bufs``.  The backward passes slice the first B
+rows out of their buffers -- SAC's hold 2B, of which [0,B) carry the critic
+loss (critics) or are pi(s) (actor); on TD3's B-row buffers the slice is the
+whole -- and return the slab -> gradient segments, to which each ``update``
+adds its own (entropy partials, loss slab, q(s, pi(s))) before the one
+``colsum_finalize``.  What the two ``update`` methods keep is the schedule:
+which rows of ``xs`` a pass runs on, which loss its rows carry, where the
+data-parallel average starts.
+
 The GEMMs stay on PyTorch-ROCm (hipBLASLt fp32 MFMA, north_star) with the
 bias + ReLU epilogue (``torch._addmm_activation``) and preallocated outputs.
 fp32 throughout.  There is no CPU form of this path: on a CUDA device the
 kernels are required (``_lib.load()`` raises without the library); on the
-CPU (the known-answer tests) SAC keeps the plain autograd update.
+CPU (the known-answer tests) the algorithms keep the plain autograd update.
 """
 import ctypes as C
 import os
@@ -62,6 +85,11 @@ SLAB_ROWS = 128
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def _opt_ptr(t):
+    """An argument the kernel may go without (NULL)."""
+    return None if t is None else _ptr(t)
 
 
 def _rows_per_block(n_rows):
@@ -100,18 +128,15 @@ class HipOps:
         assert w.is_contiguous() and w.numel() == n_out * n_in
         _lib.check(self.lib.ttl_thin_forward(
             _ptr(a), lda, a_bs, _ptr(w), _ptr(b), n_rows, n_in, n_out, int(block_diagonal),
-            head, _ptr(eps) if eps is not None else None, entropy_rows, _ptr(out), ld_out,
-            _ptr(logp) if logp is not None else None,
-            _ptr(ls_raw) if ls_raw is not None else None,
-            _ptr(ent_part) if ent_part is not None else None, self._s()), 'ttl_thin_forward')
+            head, _opt_ptr(eps), entropy_rows, _ptr(out), ld_out, _opt_ptr(logp),
+            _opt_ptr(ls_raw), _opt_ptr(ent_part), self._s()), 'ttl_thin_forward')
 
     def sac_losses(self, q_on, q_tg, logp, reward, not_done, log_alpha, alpha_const, gamma,
                    dq, loss_part, steps, consts, beta_pows, tick_mask, lr):
         n = reward.shape[0]
         _lib.check(self.lib.ttl_sac_losses(
             _ptr(q_on), _ptr(q_tg), _ptr(logp), _ptr(reward), _ptr(not_done), n,
-            _ptr(log_alpha) if log_alpha is not None else None, float(alpha_const),
-            float(gamma), _ptr(dq), _ptr(loss_part) if loss_part is not None else None,
+            _opt_ptr(log_alpha), float(alpha_const), float(gamma), _ptr(dq), _opt_ptr(loss_part),
             _ptr(steps), _ptr(consts), _ptr(beta_pows), steps.numel(), tick_mask, float(lr),
             BETA1, BETA2, self._s()), 'ttl_sac_losses')
 
@@ -156,19 +181,16 @@ class HipOps:
         assert h.shape == dh.shape and wa.is_contiguous() and wa.shape == (n_act, n_cols)
         _lib.check(self.lib.ttl_sac_actor_head_backward(
             _ptr(dh), dh.stride(0), _ptr(h), h.stride(0), _ptr(wa), n_rows, n_cols, n_act,
-            head, _ptr(pi), ld_pi, _ptr(eps) if eps is not None else None,
-            _ptr(ls_raw) if ls_raw is not None else None,
-            _ptr(log_alpha) if log_alpha is not None else None, float(alpha_const),
-            _ptr(d_head), self._s()), 'ttl_sac_actor_head_backward')
+            head, _ptr(pi), ld_pi, _opt_ptr(eps), _opt_ptr(ls_raw), _opt_ptr(log_alpha),
+            float(alpha_const), _ptr(d_head), self._s()), 'ttl_sac_actor_head_backward')
 
     def td3_losses(self, q_on, q_tg, reward, not_done, gamma, dq, loss_part, steps, consts,
                    beta_pows, tick_mask, lr):
         n, n_q = q_on.shape
         _lib.check(self.lib.ttl_td3_losses(
             _ptr(q_on), _ptr(q_tg), _ptr(reward), _ptr(not_done), n, n_q, float(gamma),
-            _ptr(dq), _ptr(loss_part) if loss_part is not None else None, _ptr(steps),
-            _ptr(consts), _ptr(beta_pows), steps.numel(), tick_mask, float(lr), BETA1, BETA2,
-            self._s()), 'ttl_td3_losses')
+            _ptr(dq), _opt_ptr(loss_part), _ptr(steps), _ptr(consts), _ptr(beta_pows),
+            steps.numel(), tick_mask, float(lr), BETA1, BETA2, self._s()), 'ttl_td3_losses')
 
     def polyak(self, target, p, tau):
         _lib.check(self.lib.ttl_polyak_average(_ptr(target), _ptr(p), p.numel(), float(tau),
@@ -176,7 +198,7 @@ class HipOps:
 
     def adam_polyak(self, p, g, m, v, target, consts, tau):
         _lib.check(self.lib.ttl_adam_polyak(
-            _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(target) if target is not None else None,
+            _ptr(p), _ptr(g), _ptr(m), _ptr(v), _opt_ptr(target),
             p.numel(), _ptr(consts), BETA1, BETA2, ADAM_EPS, float(tau), self._s()),
             'ttl_adam_polyak')
 
@@ -233,6 +255,13 @@ class _Arena:
         for d in shape:
             n *= d
         return flat[off:off + n].view(shape)
+
+    def w(self, flat, l):
+        """Layer ``l``'s weights in ``flat`` (one of the five copies)."""
+        return self.view(flat, f'w{l}')
+
+    def b(self, flat, l):
+        return self.view(flat, f'b{l}')
 
 
 class _FusedNets:
@@ -306,21 +335,27 @@ class _FusedNets:
                 (self.arena_q, 'online', self.q_lin, True),
                 (self.arena_q, 'target', self.tq_lin, True))
 
+    @staticmethod
+    def _slots(nets, stacked):
+        """(parameter, slot name, pick) for every weight and bias of ``nets``
+        (one list of Linears per network); ``pick(arena.view(flat, name))`` is
+        that parameter's own part of the slot (network k's plane if stacked)."""
+        for k, lins in enumerate(nets):
+            for l, lin in enumerate(lins):
+                for name, p in ((f'w{l}', lin.weight), (f'b{l}', lin.bias)):
+                    yield p, name, (lambda v, k=k: v[k]) if stacked else (lambda v: v)
+
     def _home(self, arena, which, nets, stacked):
         """Move the parameters of ``nets`` (one list of Linears per network)
         into ``arena.<which>`` and make them views of it; online parameters
         get their ``.grad`` as a view of ``arena.grad``."""
         flat = getattr(arena, which)
-        for k, lins in enumerate(nets):
-            for l, lin in enumerate(lins):
-                for name, p in ((f'w{l}', lin.weight), (f'b{l}', lin.bias)):
-                    v = arena.view(flat, name)
-                    v = v[k] if stacked else v
-                    v.copy_(p.data)
-                    p.data = v
-                    if which == 'online':
-                        g = arena.view(arena.grad, name)
-                        p.grad = g[k] if stacked else g
+        for p, name, pick in self._slots(nets, stacked):
+            v = pick(arena.view(flat, name))
+            v.copy_(p.data)
+            p.data = v
+            if which == 'online':
+                p.grad = pick(arena.view(arena.grad, name))
 
     def _homed(self):
         """Whether the parameters still are views of the arenas (``.to()`` /
@@ -342,12 +377,9 @@ class _FusedNets:
         for arena, which, nets, stacked in self._tables():
             if which != 'online':
                 continue
-            for k, lins in enumerate(nets):
-                for l, lin in enumerate(lins):
-                    for name, p in ((f'w{l}', lin.weight), (f'b{l}', lin.bias)):
-                        if p.grad is None or p.grad.data_ptr() == 0:
-                            g = arena.view(arena.grad, name)
-                            p.grad = g[k] if stacked else g
+            for p, name, pick in self._slots(nets, stacked):
+                if p.grad is None or p.grad.data_ptr() == 0:
+                    p.grad = pick(arena.view(arena.grad, name))
 
     # ------------------------------------------------------------------ #
     # optimizer state as views of the arenas
@@ -356,12 +388,9 @@ class _FusedNets:
         table = [(alg.actor_optimizer, self.arena_a, [self.a_lin], 1, False),
                  (alg.critic_optimizer, self.arena_q, self.q_lin, 2, True)]
         for opt, arena, nets, k_opt, stacked in table:
-            for k, lins in enumerate(nets):
-                for l, lin in enumerate(lins):
-                    for name, p in ((f'w{l}', lin.weight), (f'b{l}', lin.bias)):
-                        self._bind_state(opt, p, k_opt,
-                                         *(arena.view(f, name)[k] if stacked
-                                           else arena.view(f, name) for f in (arena.m, arena.v)))
+            for p, name, pick in self._slots(nets, stacked):
+                self._bind_state(opt, p, k_opt, pick(arena.view(arena.m, name)),
+                                 pick(arena.view(arena.v, name)))
         if getattr(self, 'auto', False):
             if not hasattr(self, 'alpha_m'):
                 self.alpha_m = torch.zeros(1, dtype=self.dtype, device=self.device)
@@ -423,11 +452,12 @@ class _FusedNets:
             self._bind_optimizers()
         self._attach_grads()
 
-    def _all_reduce(self, extra=()):
+    def _all_reduce(self, tensors):
+        """Average ``tensors`` over the replicas, one after the other."""
         import torch.distributed as dist
         group = self.alg._dp_group
         world = dist.get_world_size(group)
-        for t in (self.arena_a.grad, self.arena_q.grad) + tuple(extra):
+        for t in tensors:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
             t /= world
 
@@ -457,6 +487,154 @@ class _FusedNets:
         for t in tensors:
             t /= world
 
+    # ------------------------------------------------------------------ #
+    # workspaces of a batch size
+    def _alloc_shared(self, B, rows_a, rows_q, n_head):
+        """What both updates allocate: the input rows ``xs`` [3B x ld]; the
+        actor's activations (``rows_a`` rows) and its backward (B rows,
+        ``n_head`` head columns); the online critics' activations and backward
+        (``rows_q`` rows, of which the first B carry the critic loss), the
+        target critics' activations (B rows); the loss slab.  Returns the tensor
+        options."""
+        z = dict(dtype=self.dtype, device=self.device)
+        nq, haL, hqL = self.NQ, self.ha[-1], self.hq[-1]
+        self.B, self.ld = B, (self.S + self.A + 3) // 4 * 4
+        self.xs = torch.zeros(3 * B, self.ld, **z)
+        self.act_a = [torch.empty(rows_a, h, **z) for h in self.ha]
+        self.dza = [torch.empty(B, h, **z) for h in self.ha]
+        self.d_head = torch.empty(B, n_head, **z)
+        self.hc, self.dzc = self._critic_bufs(rows_q, z), self._critic_bufs(rows_q, z)
+        self.ht = self._critic_bufs(B, z)
+        self.q_on, self.dq = torch.empty(rows_q, nq, **z), torch.empty(rows_q, nq, **z)
+        self.q_tg = torch.empty(B, nq, **z)
+        self.loss_part = torch.zeros(-(-B // LOSS_BLOCK), 8, **z)
+        # slabs: [db below | dW thin | db thin] of the thin layers, [db] of the
+        # others; one slab row per row block of the rows the kernel is handed
+        # (_critics_backward: layer 0 of the critics gets the B loss rows only)
+        R, Rq = -(-B // _rows_per_block(B)), -(-rows_q // _rows_per_block(rows_q))
+        self.part_a_top = torch.zeros(R, haL + n_head * haL + n_head, **z)
+        self.part_a = [torch.zeros(R, h, **z) for h in self.ha[:-1]]
+        self.part_q_top = torch.zeros(Rq, 2 * nq * hqL + nq, **z)
+        self.part_q = [torch.zeros(R if l == 0 else Rq, nq * h, **z)
+                       for l, h in enumerate(self.hq[:-1])]
+        return z
+
+    def _critic_bufs(self, rows, z):
+        """The critics' activations (or their gradients) for ``rows`` rows:
+        layer 0 side by side [rows x NQ h] (one stacked GEMM), the layers above
+        in planes [NQ x rows x h] -- contiguous GEMM outputs keep the bias + ReLU
+        epilogue (a strided `out` costs torch's addmm a bias broadcast copy and a
+        separate ReLU pass, ~25 us per GEMM here)."""
+        nq = self.NQ
+        return [torch.empty(rows, nq * h, **z) if l == 0 or nq == 1
+                else torch.empty(nq, rows, h, **z) for l, h in enumerate(self.hq)]
+
+    def _critic(self, bufs, l, k):
+        """Critic ``k``'s [rows x h] of layer ``l`` in ``_critic_bufs`` buffers."""
+        if self.NQ == 1:
+            return bufs[l]
+        if l == 0:
+            h = self.hq[0]
+            return bufs[0][:, k * h:(k + 1) * h]
+        return bufs[l][k]
+
+    # ------------------------------------------------------------------ #
+    # the passes both schedules are made of
+    @staticmethod
+    def _hidden_forward(arena, flat, x, bufs, k=None):
+        """The hidden layers (GEMM + bias + ReLU each) of the network in
+        ``arena.<flat>`` -- of critic ``k`` alone, if given -- on the rows ``x``
+        into ``bufs``; returns the last activation."""
+        for l, out in enumerate(bufs):
+            w, b = arena.w(flat, l), arena.b(flat, l)
+            if k is not None:
+                w, b = w[k], b[k]
+            torch._addmm_activation(b, x, w.t(), use_gelu=False, out=out)
+            x = out
+        return x
+
+    def _critics_forward(self, flat, rows, hbuf, qout):
+        """All critics on ``rows`` of ``xs``: layer 0 as one stacked GEMM, the
+        layers above per critic, the heads as one block-diagonal thin layer."""
+        aq, S, A, L, nq = self.arena_q, self.S, self.A, self.L, self.NQ
+        h0 = self.hq[0]
+        torch._addmm_activation(aq.b(flat, 0).view(nq * h0), rows[:, :S + A],
+                                aq.w(flat, 0).view(nq * h0, S + A).t(), use_gelu=False,
+                                out=hbuf[0])
+        for l in range(1, L):
+            for k in range(nq):
+                torch._addmm_activation(aq.b(flat, l)[k], self._critic(hbuf, l - 1, k),
+                                        aq.w(flat, l)[k].t(), use_gelu=False,
+                                        out=self._critic(hbuf, l, k))
+        self.ops.thin_forward(hbuf[L - 1], aq.w(flat, L), aq.b(flat, L).view(nq), nq, nq > 1,
+                              HEAD_PLAIN, qout, nq)
+
+    def _critics_backward(self, B, x):
+        """``dq`` down through the online critics (``hc`` -> ``dzc``).  The
+        first ``B`` rows of the buffers are the critic-loss rows, whose inputs
+        are ``x``: they alone feed the weight and bias gradients, any rows
+        beyond them only carry their data gradient down to layer 0.  Returns
+        the segments that take the slabs to the gradient arena."""
+        aq, ops, L, nq = self.arena_q, self.ops, self.L, self.NQ
+        hc, dzc = self.hc, self.dzc
+        ops.thin_backward(self.dq, hc[L - 1], aq.w(aq.online, L), nq, nq > 1, 0, B, dzc[L - 1],
+                          self.part_q_top)
+        for l in range(L - 1, 0, -1):
+            for k in range(nq):
+                dz = self._critic(dzc, l, k)
+                torch.mm(dz[:B].t(), self._critic(hc, l - 1, k)[:B], out=aq.w(aq.grad, l)[k])
+                torch.mm(dz, aq.w(aq.online, l)[k], out=self._critic(dzc, l - 1, k))
+            # the slab geometry follows the rows handed over: layer 0 runs on
+            # the B loss rows only, the planes above whole with r1 = B
+            if l == 1:
+                ops.relu_backward_bias(dzc[0][:B], hc[0][:B], 0, B, self.part_q[0])
+            else:
+                ops.relu_backward_bias(dzc[l - 1], hc[l - 1], 0, B, self.part_q[l - 1])
+        torch.mm(dzc[0][:B].t(), x, out=aq.w(aq.grad, 0).view(nq * self.hq[0], self.S + self.A))
+        n = nq * self.hq[-1]
+        segs = [(self.part_q_top, 0, n, aq.b(aq.grad, L - 1).view(-1), 1.0),
+                (self.part_q_top, n, n, aq.w(aq.grad, L).view(-1), 1.0),
+                (self.part_q_top, 2 * n, nq, aq.b(aq.grad, L).view(-1), 1.0)]
+        return segs + [(self.part_q[l], 0, nq * self.hq[l], aq.b(aq.grad, l).view(-1), 1.0)
+                       for l in range(L - 1)]
+
+    def _actor_backward(self, n_head, x):
+        """``d_head`` [B x n_head] down through the online actor, whose
+        forward ran on the rows ``x`` (the first B rows of ``act_a``).  Returns
+        the segments that take the slabs to the gradient arena."""
+        aa, ops, L, B = self.arena_a, self.ops, self.L, x.shape[0]
+        act, dza = self.act_a, self.dza
+        ops.thin_backward(self.d_head, act[L - 1][:B], aa.w(aa.online, L), n_head, False, 0, B,
+                          dza[L - 1], self.part_a_top)
+        for l in range(L - 1, 0, -1):
+            torch.mm(dza[l].t(), act[l - 1][:B], out=aa.w(aa.grad, l))
+            torch.mm(dza[l], aa.w(aa.online, l), out=dza[l - 1])
+            ops.relu_backward_bias(dza[l - 1], act[l - 1][:B], 0, B, self.part_a[l - 1])
+        torch.mm(dza[0].t(), x, out=aa.w(aa.grad, 0))
+        haL = self.ha[-1]
+        segs = [(self.part_a_top, 0, haL, aa.b(aa.grad, L - 1), 1.0),
+                (self.part_a_top, haL, n_head * haL, aa.w(aa.grad, L).view(-1), 1.0),
+                (self.part_a_top, haL + n_head * haL, n_head, aa.b(aa.grad, L), 1.0)]
+        return segs + [(self.part_a[l], 0, self.ha[l], aa.b(aa.grad, l), 1.0)
+                       for l in range(L - 1)]
+
+    def _losses(self, want, actor_loss=None, backup="Q'"):
+        """The update's loss entries from ``loss_out`` (``actor_loss``: a
+        one-element buffer or a constant where the actor's loss is not entry 0
+        of it).  Copies: the next update rewrites the buffers while the episode
+        loop still holds this update's entries (device copies, no host sync)."""
+        if not want:
+            return {}
+        lo = self.loss_out.clone()
+        if actor_loss is None:
+            actor_loss = lo[0]
+        elif torch.is_tensor(actor_loss):
+            actor_loss = actor_loss[0].clone()
+        if self.NQ == 2:
+            return {'actor_loss': actor_loss, 'critic_loss': lo[1] + lo[2], 'loss_q1': lo[1],
+                    'loss_q2': lo[2], 'Q1': lo[3], 'Q2': lo[4], backup: lo[5]}
+        return {'actor_loss': actor_loss, 'critic_loss': lo[1], 'Q': lo[3], backup: lo[5]}
+
 
 class FusedSACUpdate(_FusedNets):
     """One SAC / SACAuto update on ``alg``'s networks (see the module
@@ -471,47 +649,17 @@ class FusedSACUpdate(_FusedNets):
             raise ValueError('FusedSACUpdate needs the double critic')
         self.mean_logp = torch.zeros(1, dtype=self.dtype, device=self.device)
 
-    # ------------------------------------------------------------------ #
-    # workspaces of a batch size
     def _alloc(self, B):
-        dev, S, A, L = self.device, self.S, self.A, self.L
-        z = dict(dtype=self.dtype, device=dev)
-        ld = (S + A + 3) // 4 * 4
-        self.B, self.ld = B, ld
-        self.xs = torch.zeros(3 * B, ld, **z)
+        """The actor runs on 2B rows (pi(s), pi(s')), the online critics on 2B
+        ((s, a), (s, pi(s))); the backward of either network's weights on B."""
+        A = self.A
+        z = self._alloc_shared(B, 2 * B, 2 * B, 2 * A)
         self.eps = torch.zeros(2 * B, A, **z)
-        self.act_a = [torch.empty(2 * B, h, **z) for h in self.ha]
         self.logp = torch.empty(2 * B, **z)
         self.ls_raw = torch.empty(2 * B, A, **z)
         self.ent_part = torch.zeros(-(-2 * B // THIN_FWD_ROWS), 1, **z)
-        # the critics' activations: layer 0 side by side [rows x 2h] (one stacked
-        # GEMM), the layers above in planes [2 x rows x h] -- contiguous GEMM outputs
-        # keep the bias + ReLU epilogue (a strided `out` costs torch's addmm a bias
-        # broadcast copy and a separate ReLU pass, ~25 us per GEMM here)
-        def crit(rows):
-            return [torch.empty(rows, 2 * h, **z) if l == 0 else torch.empty(2, rows, h, **z)
-                    for l, h in enumerate(self.hq)]
-        self.hc, self.ht = crit(2 * B), crit(B)
-        self.q_on = torch.empty(2 * B, 2, **z)
-        self.q_tg = torch.empty(B, 2, **z)
-        self.dq = torch.empty(2 * B, 2, **z)
-        self.loss_part = torch.zeros(-(-B // LOSS_BLOCK), 8, **z)
-        self.dzc = crit(2 * B)
-        self.dza = [torch.empty(B, h, **z) for h in self.ha]
-        self.wa = torch.empty(A, 2 * self.hq[0], **z)
-        self.d_head = torch.empty(B, 2 * A, **z)
-        R2, R1 = -(-2 * B // _rows_per_block(2 * B)), -(-B // _rows_per_block(B))
-        hqL, haL = self.hq[-1], self.ha[-1]
-        # slabs: [db below | dW thin | db thin] of the thin layers, [db] of the others
-        self.part_q_top = torch.zeros(R2, 2 * hqL + 2 * hqL + 2, **z)
-        self.part_a_top = torch.zeros(R1, haL + 2 * A * haL + 2 * A, **z)
-        # lower critic layers: rows [0,B) of the slab are the critic-loss rows;
-        # layer 0 runs the ReLU backward on those B rows only
-        self.part_q = [torch.zeros(R1 if l == 0 else R2, 2 * h, **z)
-                       for l, h in enumerate(self.hq[:-1])]
-        self.part_a = [torch.zeros(R1, h, **z) for h in self.ha[:-1]]
+        self.wa = torch.empty(A, 2 * self.hq[0], **z)       # action columns of both W0
 
-    # ------------------------------------------------------------------ #
     def update(self, batch, eps_pi=None, eps_next=None, want_losses=False):
         """One update from ``batch`` = (state, action, next_state, reward,
         not_done).  ``eps_*``: the N(0, 1) draws of the two policy samples
@@ -521,15 +669,13 @@ class FusedSACUpdate(_FusedNets):
         B = state.shape[0]
         self._prepare(B)
         S, A, L, ld = self.S, self.A, self.L, self.ld
-        aa, aq = self.arena_a, self.arena_q
-        W = lambda arena, flat, l: arena.view(flat, f'w{l}')      # noqa: E731
-        Bv = lambda arena, flat, l: arena.view(flat, f'b{l}')     # noqa: E731
-        fused = torch._addmm_activation
+        aa, aq, xs = self.arena_a, self.arena_q, self.xs
+        log_alpha = alg.log_alpha if self.auto else None
+        alpha_const = 0.0 if self.auto else alg.alpha
 
         # ---- inputs
-        xs = self.xs
         ops.build_inputs(state, action, next_state, xs, S, A,
-                         W(aq, aq.online, 0).view(2 * self.hq[0], S + A), self.wa)
+                         aq.w(aq.online, 0).view(2 * self.hq[0], S + A), self.wa)
         if eps_pi is None:
             torch.randn((B, A), out=self.eps[:B])
         else:
@@ -539,93 +685,36 @@ class FusedSACUpdate(_FusedNets):
         else:
             self.eps[B:].copy_(eps_next)
 
-        # ---- actor on rows [B, 3B): pi(s) and pi(s')
-        x = xs[B:, :S]
-        for l in range(L):
-            fused(Bv(aa, aa.online, l), x, W(aa, aa.online, l).t(), use_gelu=False,
-                  out=self.act_a[l])
-            x = self.act_a[l]
-        ops.thin_forward(x, W(aa, aa.online, L), Bv(aa, aa.online, L), 2 * A, False, HEAD_SAC,
+        # ---- actor on rows [B, 3B): pi(s) and pi(s') as one batch of 2B rows; the
+        #      entropy partials are those of its first B rows
+        x = self._hidden_forward(aa, aa.online, xs[B:, :S], self.act_a)
+        ops.thin_forward(x, aa.w(aa.online, L), aa.b(aa.online, L), 2 * A, False, HEAD_SAC,
                          xs[B:, S:], ld, eps=self.eps, entropy_rows=B, logp=self.logp,
                          ls_raw=self.ls_raw, ent_part=self.ent_part)
 
         # ---- critics: online on rows [0, 2B), target on rows [2B, 3B)
-        for flat, rows, hbuf, qout in ((aq.online, xs[:2 * B], self.hc, self.q_on),
-                                       (aq.target, xs[2 * B:], self.ht, self.q_tg)):
-            x = rows[:, :S + A]
-            h0 = self.hq[0]
-            fused(Bv(aq, flat, 0).view(2 * h0), x, W(aq, flat, 0).view(2 * h0, S + A).t(),
-                  use_gelu=False, out=hbuf[0])
-            for l in range(1, L):
-                hp = self.hq[l - 1]
-                for k in range(2):
-                    prev = hbuf[0][:, k * hp:(k + 1) * hp] if l == 1 else hbuf[l - 1][k]
-                    fused(Bv(aq, flat, l)[k], prev, W(aq, flat, l)[k].t(), use_gelu=False,
-                          out=hbuf[l][k])
-            ops.thin_forward(hbuf[L - 1], W(aq, flat, L), Bv(aq, flat, L).view(2), 2, True,
-                             HEAD_PLAIN, qout, 2)
+        self._critics_forward(aq.online, xs[:2 * B], self.hc, self.q_on)
+        self._critics_forward(aq.target, xs[2 * B:], self.ht, self.q_tg)
 
         # ---- per-row losses, d loss / d q, Adam step counters
-        log_alpha = alg.log_alpha if self.auto else None
-        ops.sac_losses(self.q_on, self.q_tg, self.logp, reward, not_done, log_alpha,
-                       0.0 if self.auto else alg.alpha, alg.gamma, self.dq,
-                       self.loss_part if want_losses else None, self.steps, self.consts,
-                       self.beta_pows, 0b111 if self.auto else 0b110, alg.lr)
+        ops.sac_losses(self.q_on, self.q_tg, self.logp, reward, not_done, log_alpha, alpha_const,
+                       alg.gamma, self.dq, self.loss_part if want_losses else None, self.steps,
+                       self.consts, self.beta_pows, 0b111 if self.auto else 0b110, alg.lr)
 
-        # ---- critics backward: rows [0,B) train the critics, rows [B,2B)
-        #      carry the actor loss down to pi(s)
-        ops.thin_backward(self.dq, self.hc[L - 1], W(aq, aq.online, L), 2, True, 0, B,
-                          self.dzc[L - 1], self.part_q_top)
-        for l in range(L - 1, 0, -1):
-            hp = self.hq[l - 1]
-            for k in range(2):
-                dz = self.dzc[l][k]
-                if l == 1:
-                    cols = slice(k * hp, (k + 1) * hp)
-                    a_prev, dz_prev = self.hc[0][:B, cols], self.dzc[0][:, cols]
-                else:
-                    a_prev, dz_prev = self.hc[l - 1][k][:B], self.dzc[l - 1][k]
-                torch.mm(dz[:B].t(), a_prev, out=W(aq, aq.grad, l)[k])
-                torch.mm(dz, W(aq, aq.online, l)[k], out=dz_prev)
-            if l == 1:
-                ops.relu_backward_bias(self.dzc[0][:B], self.hc[0][:B], 0, B, self.part_q[0])
-            else:
-                ops.relu_backward_bias(self.dzc[l - 1], self.hc[l - 1], 0, B,
-                                       self.part_q[l - 1])
-        h0 = self.hq[0]
-        torch.mm(self.dzc[0][:B].t(), xs[:B, :S + A],
-                 out=W(aq, aq.grad, 0).view(2 * h0, S + A))
-        # the critics' gradients are complete: slabs -> arena (fixed order), and with
-        # data-parallel replicas their average starts here, beside the actor's backward
-        haL, hqL = self.ha[-1], self.hq[-1]
-        segs = [(self.part_q_top, 0, 2 * hqL, Bv(aq, aq.grad, L - 1).view(-1), 1.0),
-                (self.part_q_top, 2 * hqL, 2 * hqL, W(aq, aq.grad, L).view(-1), 1.0),
-                (self.part_q_top, 4 * hqL, 2, Bv(aq, aq.grad, L).view(-1), 1.0)]
-        segs += [(self.part_q[l], 0, 2 * self.hq[l], Bv(aq, aq.grad, l).view(-1), 1.0)
-                 for l in range(L - 1)]
-        ops.colsum_finalize(segs)
+        # ---- critics backward: rows [0,B) train the critics, rows [B,2B) carry the
+        #      actor loss down to pi(s).  Then the critics' gradients are complete:
+        #      slabs -> arena (fixed order), and with data-parallel replicas their
+        #      average starts here, beside the actor's backward
+        ops.colsum_finalize(self._critics_backward(B, xs[:B, :S + A]))
         dp = getattr(alg, '_dp', False)
         overlap = dp and self.dp_overlap
         pending_q = self._all_reduce_begin((aq.grad,)) if overlap else None
         ops.actor_head_backward(self.dzc[0][B:], self.hc[0][B:], self.wa, A, xs[B:2 * B, S:],
-                                ld, self.eps, self.ls_raw, log_alpha,
-                                0.0 if self.auto else alg.alpha, self.d_head)
+                                ld, self.eps, self.ls_raw, log_alpha, alpha_const, self.d_head)
 
-        # ---- actor backward (rows [0,B) of its batch = pi(s))
-        ops.thin_backward(self.d_head, self.act_a[L - 1][:B], W(aa, aa.online, L), 2 * A, False,
-                          0, B, self.dza[L - 1], self.part_a_top)
-        for l in range(L - 1, 0, -1):
-            torch.mm(self.dza[l].t(), self.act_a[l - 1][:B], out=W(aa, aa.grad, l))
-            torch.mm(self.dza[l], W(aa, aa.online, l), out=self.dza[l - 1])
-            ops.relu_backward_bias(self.dza[l - 1], self.act_a[l - 1][:B], 0, B,
-                                   self.part_a[l - 1])
-        torch.mm(self.dza[0].t(), xs[B:2 * B, :S], out=W(aa, aa.grad, 0))
-
-        # ---- the actor's slabs -> gradients (fixed order)
-        segs = [(self.part_a_top, 0, haL, Bv(aa, aa.grad, L - 1), 1.0),
-                (self.part_a_top, haL, 2 * A * haL, W(aa, aa.grad, L).view(-1), 1.0),
-                (self.part_a_top, haL + 2 * A * haL, 2 * A, Bv(aa, aa.grad, L), 1.0)]
-        segs += [(self.part_a[l], 0, self.ha[l], Bv(aa, aa.grad, l), 1.0) for l in range(L - 1)]
+        # ---- actor backward (rows [0,B) of its batch = pi(s)); its slabs, the
+        #      entropy partials and the loss slab -> gradients, mean log pi, losses
+        segs = self._actor_backward(2 * A, xs[B:2 * B, :S])
         segs.append((self.ent_part[:B // THIN_FWD_ROWS + (B % THIN_FWD_ROWS > 0)], 0, 1,
                      self.mean_logp, 1.0 / B))
         if want_losses:
@@ -641,7 +730,7 @@ class FusedSACUpdate(_FusedNets):
             ops.adam_polyak(aq.online, aq.grad, aq.m, aq.v, aq.target, self.consts[4:6], alg.tau)
             self._all_reduce_end(pending_a)
         elif dp:
-            self._all_reduce(extra)
+            self._all_reduce((aa.grad, aq.grad) + extra)
 
         # ---- temperature, actor, critics: Adam (+ Polyak)
         if self.auto:
@@ -650,13 +739,7 @@ class FusedSACUpdate(_FusedNets):
         ops.adam_polyak(aa.online, aa.grad, aa.m, aa.v, aa.target, self.consts[2:4], alg.tau)
         if not overlap:
             ops.adam_polyak(aq.online, aq.grad, aq.m, aq.v, aq.target, self.consts[4:6], alg.tau)
-        if want_losses:
-            # a copy: the next update rewrites ``loss_out`` while the episode loop
-            # still holds this update's entries (one device copy, no host sync)
-            lo = self.loss_out.clone()
-            return {'actor_loss': lo[0], 'critic_loss': lo[1] + lo[2], 'loss_q1': lo[1],
-                    'loss_q2': lo[2], 'Q1': lo[3], 'Q2': lo[4], 'backup': lo[5]}
-        return {}
+        return self._losses(want_losses, backup='backup')
 
     def flops_per_update(self, B):
         """FLOP of one update at batch B: ``issued`` = what this schedule runs
@@ -701,54 +784,17 @@ class FusedTD3Update(_FusedNets):
         self.actor_loss = torch.zeros(1, dtype=self.dtype, device=self.device)
 
     def _alloc(self, B):
-        dev, S, A = self.device, self.S, self.A
-        z = dict(dtype=self.dtype, device=dev)
-        ld = (S + A + 3) // 4 * 4
-        self.B, self.ld = B, ld
-        nq = self.NQ
-        self.xs = torch.zeros(3 * B, ld, **z)
-        self.act_a = [torch.empty(B, h, **z) for h in self.ha]
-
-        def crit(rows, nets):
-            return [torch.empty(rows, nets * h, **z) if l == 0 or nets == 1
-                    else torch.empty(nets, rows, h, **z) for l, h in enumerate(self.hq)]
-        self.hc, self.ht, self.dzc = crit(B, nq), crit(B, nq), crit(B, nq)
+        """Every pass has B rows; the actor pass runs the first critic alone,
+        in buffers of its own."""
+        A, hqL = self.A, self.hq[-1]
+        z = self._alloc_shared(B, B, B, A)
         self.h1 = [torch.empty(B, h, **z) for h in self.hq]      # first critic on (s, pi(s))
         self.dz1 = [torch.empty(B, h, **z) for h in self.hq]
-        self.q_on, self.q_tg = torch.empty(B, nq, **z), torch.empty(B, nq, **z)
         self.q_pi = torch.empty(B, 1, **z)
-        self.dq = torch.empty(B, nq, **z)
         self.dq_pi = torch.full((B, 1), -1.0 / B, **z)
-        self.loss_part = torch.zeros(-(-B // LOSS_BLOCK), 8, **z)
-        self.dza = [torch.empty(B, h, **z) for h in self.ha]
-        self.wa = torch.empty(A, self.hq[0], **z)
-        self.d_head = torch.empty(B, A, **z)
+        self.wa = torch.empty(A, self.hq[0], **z)                # action columns of its W0
         R = -(-B // _rows_per_block(B))
-        hqL, haL = self.hq[-1], self.ha[-1]
-        self.part_q_top = torch.zeros(R, 2 * nq * hqL + nq, **z)
-        self.part_q = [torch.zeros(R, nq * h, **z) for h in self.hq[:-1]]
         self.part_1 = torch.zeros(R, max(2 * hqL + 1, max(self.hq)), **z)   # actor-pass scratch
-        self.part_a_top = torch.zeros(R, haL + A * haL + A, **z)
-        self.part_a = [torch.zeros(R, h, **z) for h in self.ha[:-1]]
-
-    def _critics_forward(self, flat, rows, hbuf, qout):
-        aq, S, A, L, nq = self.arena_q, self.S, self.A, self.L, self.NQ
-        fused = torch._addmm_activation
-        h0 = self.hq[0]
-        fused(aq.view(flat, 'b0').view(nq * h0), rows[:, :S + A],
-              aq.view(flat, 'w0').view(nq * h0, S + A).t(), use_gelu=False, out=hbuf[0])
-        for l in range(1, L):
-            hp = self.hq[l - 1]
-            for k in range(nq):
-                if nq == 1:
-                    prev, out = hbuf[l - 1], hbuf[l]
-                else:
-                    prev = hbuf[0][:, k * hp:(k + 1) * hp] if l == 1 else hbuf[l - 1][k]
-                    out = hbuf[l][k]
-                fused(aq.view(flat, f'b{l}')[k], prev, aq.view(flat, f'w{l}')[k].t(),
-                      use_gelu=False, out=out)
-        self.ops.thin_forward(hbuf[L - 1], aq.view(flat, f'w{L}'), aq.view(flat, f'b{L}').view(nq),
-                              nq, nq > 1, HEAD_PLAIN, qout, nq)
 
     def update(self, batch, noise, update_actor, want_losses=True):
         """``noise``: the target-policy smoothing noise (already scaled and, for
@@ -758,27 +804,19 @@ class FusedTD3Update(_FusedNets):
         state, action, next_state, reward, not_done = batch
         B = state.shape[0]
         self._prepare(B)
-        S, A, L, ld, nq = self.S, self.A, self.L, self.ld, self.NQ
-        aa, aq = self.arena_a, self.arena_q
-        W = lambda arena, flat, l: arena.view(flat, f'w{l}')      # noqa: E731
-        Bv = lambda arena, flat, l: arena.view(flat, f'b{l}')     # noqa: E731
-        fused = torch._addmm_activation
-        xs = self.xs
-        h0 = self.hq[0]
-        clip = getattr(alg, 'noise_clip', None) is not None          # TD3 clamps, DDPG does not
+        S, A, L, ld = self.S, self.A, self.L, self.ld
+        aa, aq, xs = self.arena_a, self.arena_q, self.xs
+        dp = getattr(alg, '_dp', False)
 
-        # ---- inputs; target action = target_actor(s') + noise
-        ops.build_inputs(state, action, next_state, xs, S, A, W(aq, aq.online, 0)[0], self.wa)
-        x = xs[2 * B:, :S]
-        for l in range(L):
-            fused(Bv(aa, aa.target, l), x, W(aa, aa.target, l).t(), use_gelu=False,
-                  out=self.act_a[l])
-            x = self.act_a[l]
-        ops.thin_forward(x, W(aa, aa.target, L), Bv(aa, aa.target, L), A, False, HEAD_TANH,
+        # ---- inputs; target action = target_actor(s') + noise, clamped for TD3
+        #      (DDPG does not), in place in rows [2B,3B)
+        ops.build_inputs(state, action, next_state, xs, S, A, aq.w(aq.online, 0)[0], self.wa)
+        x = self._hidden_forward(aa, aa.target, xs[2 * B:, :S], self.act_a)
+        ops.thin_forward(x, aa.w(aa.target, L), aa.b(aa.target, L), A, False, HEAD_TANH,
                          xs[2 * B:, S:], ld)
         nxt = xs[2 * B:, S:S + A]
         nxt.add_(noise)
-        if clip:
+        if getattr(alg, 'noise_clip', None) is not None:
             nxt.clamp_(-alg.max_action, alg.max_action)
 
         # ---- critics: target on (s', a'), online on (s, a); loss and d loss / d q
@@ -788,104 +826,46 @@ class FusedTD3Update(_FusedNets):
                        self.loss_part if want_losses else None, self.steps, self.consts,
                        self.beta_pows, 0b110 if update_actor else 0b100, alg.lr)
 
-        # ---- critics backward
-        ops.thin_backward(self.dq, self.hc[L - 1], W(aq, aq.online, L), nq, nq > 1, 0, B,
-                          self.dzc[L - 1], self.part_q_top)
-        for l in range(L - 1, 0, -1):
-            hp = self.hq[l - 1]
-            for k in range(nq):
-                if nq == 1:
-                    dz, a_prev, dz_prev = self.dzc[l], self.hc[l - 1], self.dzc[l - 1]
-                elif l == 1:
-                    cols = slice(k * hp, (k + 1) * hp)
-                    dz, a_prev, dz_prev = self.dzc[l][k], self.hc[0][:, cols], self.dzc[0][:, cols]
-                else:
-                    dz, a_prev, dz_prev = self.dzc[l][k], self.hc[l - 1][k], self.dzc[l - 1][k]
-                torch.mm(dz.t(), a_prev, out=W(aq, aq.grad, l)[k])
-                torch.mm(dz, W(aq, aq.online, l)[k], out=dz_prev)
-            ops.relu_backward_bias(self.dzc[l - 1], self.hc[l - 1], 0, B, self.part_q[l - 1])
-        torch.mm(self.dzc[0].t(), xs[:B, :S + A], out=W(aq, aq.grad, 0).view(nq * h0, S + A))
-        hqL = self.hq[-1]
-        segs = [(self.part_q_top, 0, nq * hqL, Bv(aq, aq.grad, L - 1).view(-1), 1.0),
-                (self.part_q_top, nq * hqL, nq * hqL, W(aq, aq.grad, L).view(-1), 1.0),
-                (self.part_q_top, 2 * nq * hqL, nq, Bv(aq, aq.grad, L).view(-1), 1.0)]
-        segs += [(self.part_q[l], 0, nq * self.hq[l], Bv(aq, aq.grad, l).view(-1), 1.0)
-                 for l in range(L - 1)]
+        # ---- critics backward; their slabs and the loss slab -> gradients, losses;
+        #      Adam (the targets move after the actor pass)
+        segs = self._critics_backward(B, xs[:B, :S + A])
         if want_losses:
             segs.append((self.loss_part, 0, 8, self.loss_out, 1.0 / B))
         ops.colsum_finalize(segs)
-        dp = getattr(alg, '_dp', False)
-        if dp and not update_actor:
-            self._all_reduce_one(aq.grad)
-        if not update_actor:
-            ops.adam_polyak(aq.online, aq.grad, aq.m, aq.v, None, self.consts[4:6], alg.tau)
-            return self._losses(want_losses, False)
         if dp:
-            self._all_reduce_one(aq.grad)
+            self._all_reduce((aq.grad,))
         ops.adam_polyak(aq.online, aq.grad, aq.m, aq.v, None, self.consts[4:6], alg.tau)
+        if not update_actor:
+            return self._losses(want_losses, 0.0)
 
         # ---- actor pass: pi(s) on rows [B,2B), the UPDATED first critic on (s, pi(s))
-        self.wa.copy_(W(aq, aq.online, 0)[0][:, S:S + A].t())     # its action columns, now
-        x = xs[B:2 * B, :S]
-        for l in range(L):
-            fused(Bv(aa, aa.online, l), x, W(aa, aa.online, l).t(), use_gelu=False,
-                  out=self.act_a[l])
-            x = self.act_a[l]
-        ops.thin_forward(x, W(aa, aa.online, L), Bv(aa, aa.online, L), A, False, HEAD_TANH,
+        self.wa.copy_(aq.w(aq.online, 0)[0][:, S:S + A].t())     # its action columns, now
+        x = self._hidden_forward(aa, aa.online, xs[B:2 * B, :S], self.act_a)
+        ops.thin_forward(x, aa.w(aa.online, L), aa.b(aa.online, L), A, False, HEAD_TANH,
                          xs[B:2 * B, S:], ld)
-        x = xs[B:2 * B, :S + A]
-        for l in range(L):
-            fused(Bv(aq, aq.online, l)[0], x, W(aq, aq.online, l)[0].t(), use_gelu=False,
-                  out=self.h1[l])
-            x = self.h1[l]
-        ops.thin_forward(x, W(aq, aq.online, L)[0], Bv(aq, aq.online, L)[0], 1, False,
-                         HEAD_PLAIN, self.q_pi, 1)
-        # d(-mean q1) / d q1 = -1 / B down to the action columns of the first layer
-        ops.thin_backward(self.dq_pi, self.h1[L - 1], W(aq, aq.online, L)[0], 1, False, 0, 0,
+        x = self._hidden_forward(aq, aq.online, xs[B:2 * B, :S + A], self.h1, k=0)
+        ops.thin_forward(x, aq.w(aq.online, L)[0], aq.b(aq.online, L)[0], 1, False, HEAD_PLAIN,
+                         self.q_pi, 1)
+        # d(-mean q1) / d q1 = -1 / B down to the action columns of the first layer:
+        # data gradients only (r0 = r1 = 0: no row enters the slab ``part_1``)
+        ops.thin_backward(self.dq_pi, self.h1[L - 1], aq.w(aq.online, L)[0], 1, False, 0, 0,
                           self.dz1[L - 1], self.part_1)
         for l in range(L - 1, 0, -1):
-            torch.mm(self.dz1[l], W(aq, aq.online, l)[0], out=self.dz1[l - 1])
+            torch.mm(self.dz1[l], aq.w(aq.online, l)[0], out=self.dz1[l - 1])
             if l > 1:
                 ops.relu_backward_bias(self.dz1[l - 1], self.h1[l - 1], 0, 0,
                                        self.part_1[:, :self.hq[l - 1]])
         ops.actor_head_backward(self.dz1[0], self.h1[0], self.wa, A, xs[B:2 * B, S:], ld, None,
                                 None, None, 0.0, self.d_head, head=HEAD_TANH)
 
-        # ---- actor backward
-        haL = self.ha[-1]
-        ops.thin_backward(self.d_head, self.act_a[L - 1], W(aa, aa.online, L), A, False, 0, B,
-                          self.dza[L - 1], self.part_a_top)
-        for l in range(L - 1, 0, -1):
-            torch.mm(self.dza[l].t(), self.act_a[l - 1], out=W(aa, aa.grad, l))
-            torch.mm(self.dza[l], W(aa, aa.online, l), out=self.dza[l - 1])
-            ops.relu_backward_bias(self.dza[l - 1], self.act_a[l - 1], 0, B, self.part_a[l - 1])
-        torch.mm(self.dza[0].t(), xs[B:2 * B, :S], out=W(aa, aa.grad, 0))
-        segs = [(self.part_a_top, 0, haL, Bv(aa, aa.grad, L - 1), 1.0),
-                (self.part_a_top, haL, A * haL, W(aa, aa.grad, L).view(-1), 1.0),
-                (self.part_a_top, haL + A * haL, A, Bv(aa, aa.grad, L), 1.0)]
-        segs += [(self.part_a[l], 0, self.ha[l], Bv(aa, aa.grad, l), 1.0) for l in range(L - 1)]
+        # ---- actor backward; its slabs -> gradients, q(s, pi(s)) -> actor loss
+        segs = self._actor_backward(A, xs[B:2 * B, :S])
         segs.append((self.q_pi, 0, 1, self.actor_loss, -1.0 / B))
         ops.colsum_finalize(segs)
         if dp:
-            self._all_reduce_one(aa.grad)
+            self._all_reduce((aa.grad,))
+
+        # ---- actor: Adam + Polyak; the critics' Polyak as a pass of its own
         ops.adam_polyak(aa.online, aa.grad, aa.m, aa.v, aa.target, self.consts[2:4], alg.tau)
         ops.polyak(aq.target, aq.online, alg.tau)
-        return self._losses(want_losses, True)
-
-    def _all_reduce_one(self, t):
-        import torch.distributed as dist
-        group = self.alg._dp_group
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        t /= dist.get_world_size(group)
-
-    def _losses(self, want, actor):
-        if not want:
-            return {}
-        # copies: the next update rewrites both buffers while the episode loop
-        # still holds this update's entries (device copies, no host sync)
-        lo = self.loss_out.clone()
-        al = self.actor_loss[0].clone() if actor else 0.0
-        if self.NQ == 2:
-            return {'actor_loss': al, 'critic_loss': lo[1] + lo[2], 'loss_q1': lo[1],
-                    'loss_q2': lo[2], 'Q1': lo[3], 'Q2': lo[4], "Q'": lo[5]}
-        return {'actor_loss': al, 'critic_loss': lo[1], 'Q': lo[3], "Q'": lo[5]}
+        return self._losses(want_losses, self.actor_loss)
