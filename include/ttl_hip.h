@@ -353,6 +353,17 @@ TTL_API int ttl_env_set_processing_order(ttl_env *env, const int32_t *order, int
  * survivor count has been read back. */
 TTL_API int ttl_env_refresh_processing_order(ttl_env *env, void *hip_stream);
 
+/* Slots of the processing order as it stands (0: no order in use): the active
+ * rows plus the holes that stopped streamlines have left since the order was
+ * last rebuilt.  *instep_out (may be NULL) receives the period of the in-step
+ * re-bucket: with TTL_ORDER_INSTEP=P in the environment at ttl_env_create, the
+ * steps that run the one-launch tail rebuild the order by brick themselves on
+ * every P-th step of an episode (half of a counting sort inside that tail, one
+ * short kernel behind it; the order has no holes afterwards), and the caller
+ * need not call ttl_env_refresh_processing_order periodically.  0: off, or the
+ * volume has too many bricks for it. */
+TTL_API int ttl_env_order_slots(ttl_env *env, int32_t *n_slots_out, int32_t *instep_out);
+
 /* Current continue_idx buffer (device, int32 [n_active]) and, after a step,
  * the active-row -> output-row map (device, int32 [n_active]). */
 TTL_API int ttl_env_view(ttl_env *env, const int32_t **continue_idx,

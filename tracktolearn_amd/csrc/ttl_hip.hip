@@ -729,18 +729,32 @@ __global__ __launch_bounds__(BLOCK) void k_proc_scatter(EnvParams P,
 // follows from what k_advance left (stop, in-block rank, per-block counts): every
 // workgroup scans ALL block counts itself (<= 4096 ints through LDS), no
 // workgroup waits for another.
+//
+// REBUCKET (a re-bucket step of TTL_ORDER_INSTEP, local_sort only): the first
+// half of a counting sort of the survivors by 8^3-voxel brick rides along.  The
+// block's live slots are in Morton order of their voxel, so the slots of one
+// brick form a run; the last slot of a run takes the run's offset inside its
+// bin with ONE global atomic on bin_count[bin], and every surviving slot leaves
+// {bin and offset (one word), next row} in ord_rec for k_order_scatter (ttl_order.hip), which
+// writes the next step's order -- proc_next is not written here.  A slot whose
+// streamline stopped gets no bin (and splits the run it sits in, which costs an
+// atomic and nothing else).
 // ---------------------------------------------------------------------------
 constexpr int TTL_TAIL_MAX_BLOCKS = 4096;
 
+template <bool REBUCKET>
 __global__ __launch_bounds__(BLOCK) void k_tail(
     EnvParams P, const int *__restrict__ idx, int *__restrict__ idx_next,
     const int *__restrict__ proc, int *__restrict__ proc_next, int n_active, int n_slots,
-    int nb_rows, int order, int n_pts, int *__restrict__ host_word, int seq, int local_sort) {
+    int nb_rows, int order, int n_pts, int *__restrict__ host_word, int seq, int local_sort,
+    int2 *__restrict__ ord_rec, unsigned *__restrict__ bin_count, int nbx, int nby, int nbz) {
     __shared__ int s_scan[TTL_TAIL_MAX_BLOCKS];
     __shared__ int s_wave[BLOCK / 64];
     __shared__ unsigned s_key[BLOCK];
     __shared__ int s_pos[BLOCK];
     __shared__ int s_rank[BLOCK];
+    __shared__ int s_bin[REBUCKET ? BLOCK : 1];
+    __shared__ unsigned long long s_heads[BLOCK / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- exclusive scan of the per-block survivor counts (rows) ----
     const int per = (nb_rows + BLOCK - 1) / BLOCK;          // <= 16 counts per thread
@@ -817,6 +831,7 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
     // per-block re-sort by the voxel the streamline sits in now (see
     // k_proc_scatter); holes carry the largest key and end up behind the live slots
     unsigned key = 0xFFFFFFFFu;
+    int bin = -1;
     if (live) {
         const unsigned vx = (unsigned)(int)fminf(fmaxf(floorf(hd.x), 0.0f), 1023.0f);
         const unsigned vy = (unsigned)(int)fminf(fmaxf(floorf(hd.y), 0.0f), 1023.0f);
@@ -824,6 +839,10 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
         const unsigned coarse = (((vx >> 6) & 3u) << 4) | (((vy >> 6) & 3u) << 2) | ((vz >> 6) & 3u);
         const unsigned m = (spread3(vx) << 2) | (spread3(vy) << 1) | spread3(vz);
         key = (min(coarse << 18 | m, 0xFFFFFEu) << 8) | (unsigned)tid;
+        // brick of that voxel in the refresh's dense raster, clamped into it
+        if (REBUCKET && next >= 0)
+            bin = (min((int)(vx >> 3), nbx - 1) * nby + min((int)(vy >> 3), nby - 1)) * nbz +
+                  min((int)(vz >> 3), nbz - 1);
     }
     unsigned sk = key;
 #pragma unroll
@@ -839,6 +858,7 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
     }
     s_key[tid] = sk;
     s_pos[tid] = -1;
+    if (REBUCKET) s_bin[tid] = -1;
     const int n_live = __syncthreads_count(live);
     int srank = lane;
 #pragma unroll
@@ -860,12 +880,37 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
         *reinterpret_cast<float4 *>(P.slot_head + 4 * (base + rank)) = hd;
         P.slot_dest[base + rank] = dest;
         s_pos[rank] = next;
+        if (REBUCKET) s_bin[rank] = bin;
     }
     __syncthreads();
-    if (j < n_slots) {
-        if (tid >= n_live) P.slot_dest[j] = -1;        // the holes, behind the live slots
-        proc_next[j] = s_pos[tid];
+    if (j < n_slots && tid >= n_live) P.slot_dest[j] = -1;    // the holes, behind the live slots
+    if (!REBUCKET) {
+        if (j < n_slots) proc_next[j] = s_pos[tid];
+        return;
     }
+    // ---- runs of equal bins among the sorted slots: one atomic per run ----
+    const int b = s_bin[tid];
+    const bool head = tid == 0 || s_bin[tid - 1] != b;
+    const bool last = tid == BLOCK - 1 || s_bin[tid + 1] != b;
+    const unsigned long long hm = __ballot(head);
+    if (lane == 0) s_heads[wave] = hm;
+    __syncthreads();
+    // the head of this slot's run: the nearest head at or below tid (slot 0 is one)
+    int hp = 0;
+    for (int w = wave; w >= 0; --w) {
+        unsigned long long mk = s_heads[w];
+        if (w == wave) mk &= (2ull << lane) - 1ull;
+        if (mk) {
+            hp = 64 * w + 63 - __clzll(mk);
+            break;
+        }
+    }
+    // (s_rank is free: its last reads were in front of the barrier above)
+    if (last && b >= 0) s_rank[hp] = (int)atomicAdd(&bin_count[b], (unsigned)(tid - hp + 1));
+    __syncthreads();
+    if (j < n_slots)
+        ord_rec[j] = int2{b >= 0 ? (int)(((unsigned)b << TTL_INSTEP_OFF_BITS) | (unsigned)(s_rank[hp] + (tid - hp))) : -1,
+                          s_pos[tid]};
 }
 
 // stopping flags of caller-supplied tails (n_pts points per streamline)
@@ -1107,6 +1152,15 @@ struct ttl_env {
                          // the length of its last refresh, stopped streamlines leave holes)
     int tail_fused;      // k_tail instead of k_prefix + k_proc_scatter (TTL_TAIL_FUSED) ...
     int tail_fused_max;  // ... for processing orders of at most this many slots (TTL_TAIL_FUSED_MAX_ROWS)
+    int proc_min_rows;   // batches below this many rows drop the processing order (TTL_ORDER_MIN_ROWS)
+    int instep;          // > 0: k_tail steps re-bucket the order by brick on every instep-th step
+                         // of an episode (TTL_ORDER_INSTEP); 0: only the host-driven refresh
+    int instep_after;    // k_order_scatter behind the gather instead of in front (TTL_ORDER_INSTEP_AFTER)
+    int instep_bins;     // bins of the brick raster, 0: too many for the in-step path
+    int instep_nb[3];    // the raster
+    int2 *ord_rec;       // [n_max] {bin and offset, next row} per slot, k_tail -> k_order_scatter
+    unsigned *ord_count[2];  // bin counts; the scatter of one re-bucket clears the other's
+    int ord_parity;      // which of them the next re-bucket counts into
     // optional per-kernel timing with HIP events on the caller's stream
     int state_kernel; // 0: k_state (all 56 corner fetches), 3: k_state_dd with scalar tail stores, else k_state_dd
     hipStream_t side;      // carries the early device->host copy of the counts
@@ -1176,6 +1230,8 @@ size_t ttl_env_workspace_bytes(int32_t n_max) {
     b += 2 * align_up(nb * sizeof(int), 256); // block_counts, proc_counts
     b += 256;                                 // counts
     b += ttl_detail_order_workspace_bytes(n); // order refresh scratch
+    b += align_up(n * sizeof(int2), 256);     // ord_rec
+    b += 2 * align_up(ttl_detail_order_instep_count_bytes(), 256);  // ord_count x2
     return b;
 }
 
@@ -1425,6 +1481,20 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
     P.counts = (int *)w;          w += 256;
     e->order_ws = w;
     e->order_ws_bytes = ttl_detail_order_workspace_bytes(n);
+    w += e->order_ws_bytes;
+    e->ord_rec = (int2 *)w;       w += align_up(n * sizeof(int2), 256);
+    for (int k = 0; k < 2; ++k) {
+        e->ord_count[k] = (unsigned *)w;
+        w += align_up(ttl_detail_order_instep_count_bytes(), 256);
+    }
+    e->ord_parity = 0;
+    e->proc_min_rows = 8192;     // (the tests lower it to reach the order's kernels with small batches)
+    if (const char *v = getenv("TTL_ORDER_MIN_ROWS")) e->proc_min_rows = atoi(v);
+    e->instep = 2;      // measured best of 1 / 2 / 3 / 4: profiles/r05_instep_ab.log
+    if (const char *v = getenv("TTL_ORDER_INSTEP")) e->instep = atoi(v) > 0 ? atoi(v) : 0;
+    e->instep_after = 0;
+    if (const char *v = getenv("TTL_ORDER_INSTEP_AFTER")) e->instep_after = atoi(v) != 0;
+    e->instep_bins = ttl_detail_order_bins(P, e->instep_nb);
     e->length = 0;
     e->n_active = 0;
     e->cur = 0;
@@ -1584,6 +1654,15 @@ int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
     env->proc_cur = 0;
     env->use_proc = processing_order != nullptr;
     env->n_slots = n;
+    if (env->instep && env->instep_bins) {
+        // the re-bucket steps count into buffers that each of them leaves clear
+        // for the next; an episode starts from both clear (the two lie side by
+        // side; also without an order now: one may be installed later on)
+        HIP_TRY(hipMemsetAsync(env->ord_count[0], 0,
+                               (size_t)((char *)env->ord_count[1] - (char *)env->ord_count[0]) +
+                                   ttl_detail_order_instep_count_bytes(), s));
+        env->ord_parity = 0;
+    }
     if (processing_order == TTL_ORDER_BY_POSITION) {
         // the library's own order: rows sorted by the brick of their seed
         const int rc = ttl_detail_refresh_order(env->P, d.idx_a, n, env->order_ws,
@@ -1656,6 +1735,29 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
     return TTL_OK;
 }
 
+// whether steps over a processing order of `slots` slots re-bucket it themselves:
+// the knob, a brick raster the scatter can scan, and everything that makes
+// ttl_env_step_end take k_tail with the per-block sort
+static bool ttl_order_instep_on(const ttl_env *env, int slots) {
+    return env->instep > 0 && env->instep_bins > 0 && env->local_sort && env->tail_fused &&
+           env->P.slot_rec && ttl_detail_state_dedupes(env->P, env->state_kernel) &&
+           slots <= env->tail_fused_max && slots <= (1 << TTL_INSTEP_OFF_BITS);
+}
+
+// second half of a re-bucket step: the dense order of the survivors goes where
+// the next step reads it (k_tail<true> wrote nothing there); the order has no
+// holes afterwards, so it is as long as the next step's rows
+static int ttl_order_instep_scatter(ttl_env *env, hipStream_t s) {
+    const int rc = ttl_detail_order_scatter(env->ord_rec, env->n_slots,
+                                            env->ord_count[env->ord_parity],
+                                            env->ord_count[env->ord_parity ^ 1], env->instep_bins,
+                                            env->proc[env->proc_cur ^ 1], s);
+    if (rc != TTL_OK) return rc;
+    env->ord_parity ^= 1;
+    env->n_slots = -1;
+    return TTL_OK;
+}
+
 int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
                      float *state_out, int64_t state_pitch, int32_t *host_counts,
                      void *hip_stream) {
@@ -1683,7 +1785,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     // a few thousand streamlines fit the caches in any order: stop paying for
     // the processing order in the episode's tail (from 16 384 rows down the
     // one-launch tail below takes over)
-    if (env->use_proc && (n_active < 8192 ||
+    if (env->use_proc && (n_active < env->proc_min_rows ||
                           (env->fuse_small && ttl_detail_can_fuse_tail(env->P, n_active))))
         env->use_proc = 0;
     const int *proc = env->use_proc ? env->proc[env->proc_cur] : nullptr;
@@ -1736,6 +1838,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     // the order then keeps its length between refreshes (holes), so the gather
     // is launched for n_slots slots
     int n_gather = n_active;
+    bool rebucket = false;
     const bool fused_tail = proc && env->tail_fused && env->P.slot_rec &&
                             ttl_detail_state_dedupes(env->P, env->state_kernel) &&
                             (env->n_slots < 0 ? n_active : env->n_slots) <= env->tail_fused_max;
@@ -1743,13 +1846,28 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
         if (env->n_slots < 0) env->n_slots = n_active;     // the order was dense so far
         const int nbs = (env->n_slots + BLOCK - 1) / BLOCK;
         prof_mark(env, 1, 0, s);
-        hipLaunchKernelGGL(k_tail, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next, proc,
-                           env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb, order,
-                           n_pts, host_word, seq, env->local_sort);
+        // a re-bucket step (TTL_ORDER_INSTEP): k_tail counts the survivors' bricks
+        // on the way, k_order_scatter writes the next step's order from them
+        rebucket = ttl_order_instep_on(env, env->n_slots) && (n_pts - 1) % env->instep == 0;
+        unsigned *cnt = env->ord_count[env->ord_parity];
+        if (rebucket)
+            hipLaunchKernelGGL(k_tail<true>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
+                               proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
+                               order, n_pts, host_word, seq, env->local_sort, env->ord_rec, cnt,
+                               env->instep_nb[0], env->instep_nb[1], env->instep_nb[2]);
+        else
+            hipLaunchKernelGGL(k_tail<false>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
+                               proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
+                               order, n_pts, host_word, seq, env->local_sort, nullptr, nullptr,
+                               0, 0, 0);
         prof_mark(env, 1, 1, s);
         HIP_TRY(hipGetLastError());
         if (host_counts && !host_word) HIP_TRY(ttl_copy_counts(env, host_counts, s));
         n_gather = env->n_slots;
+        if (rebucket && !env->instep_after) {
+            const int rc = ttl_order_instep_scatter(env, s);
+            if (rc != TTL_OK) return rc;
+        }
     } else {
         // the two-kernel tail reads proc[j] for j < n_active without a hole check:
         // an order that still holds holes (left by k_tail) must never reach it.
@@ -1788,6 +1906,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     const int rc = ttl_detail_launch_state(env->P, env->state_kernel, idx, env->P.row_dest,
                                            proc, n_gather, n_pts, state_out, state_pitch, s);
     prof_mark(env, 2, 1, s);
+    if (rc == TTL_OK && rebucket && env->instep_after) return ttl_order_instep_scatter(env, s);
     return rc;
 }
 
@@ -2044,6 +2163,15 @@ int ttl_env_set_processing_order(ttl_env *env, const int32_t *order, int32_t n,
                            hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     env->use_proc = 1;
     env->n_slots = n;
+    return TTL_OK;
+}
+
+int ttl_env_order_slots(ttl_env *env, int32_t *n_slots_out, int32_t *instep_out) {
+    if (!env || !n_slots_out)
+        return fail(TTL_ERR_INVALID, "ttl_env_order_slots: null argument");
+    const int slots = !env->use_proc ? 0 : env->n_slots < 0 ? env->n_active : env->n_slots;
+    *n_slots_out = slots;
+    if (instep_out) *instep_out = ttl_order_instep_on(env, slots) ? env->instep : 0;
     return TTL_OK;
 }
 

@@ -132,4 +132,17 @@ int ttl_detail_launch_fused_tail_fr(const EnvParams &P, int *idx_a, int *idx_b, 
 size_t ttl_detail_order_workspace_bytes(size_t n);
 int ttl_detail_refresh_order(const EnvParams &P, const int *idx, int n, char *ws,
                              size_t ws_bytes, int *order_out, hipStream_t s);
+// ttl_order.hip: the in-step re-bucket (TTL_ORDER_INSTEP).  The brick raster of
+// the refresh above -> nb[3]; returns its bin count, 0 when it exceeds what the
+// scatter's scan holds in LDS (such handles never re-bucket in the step)
+int ttl_detail_order_bins(const EnvParams &P, int nb[3]);
+// bytes of ONE of the two bin-count buffers
+size_t ttl_detail_order_instep_count_bytes();
+// rec[j] = {bin << TTL_INSTEP_OFF_BITS | offset inside the bin, or -1; next row
+// or -1} of slot j as k_tail left it (so: orders of at most 2^18 slots, which
+// is the default ceiling of the one-launch tail, and bins < 2^14), count = the bin counts it accumulated -> the dense order of
+// the survivors in order_out[0 .. n_slots) (-1 behind them); clears count_other
+constexpr int TTL_INSTEP_OFF_BITS = 18;
+int ttl_detail_order_scatter(const int2 *rec, int n_slots, const unsigned *count,
+                             unsigned *count_other, int bins, int *order_out, hipStream_t s);
 #endif

@@ -250,7 +250,10 @@ class TrackingEnvironment(BaseEnv):
     #: the order is rebuilt from the current positions every this many steps
     #: (a streamline crosses an 8-voxel brick in about ten 0.75-voxel steps;
     #: the gather costs 0.72 ns per streamline in fresh order, 1.15 ns once
-    #: the order has decayed; measured best of 2/4/8/16/32); 0 = never
+    #: the order has decayed; measured best of 2/4/8/16/32); 0 = never.
+    #: Only where the library does not re-bucket the order inside its own
+    #: steps (TTL_ORDER_INSTEP, default every 2nd step wherever k_tail runs):
+    #: there this period and the low-fill refresh below are not used
     SPATIAL_ORDER_REFRESH = int(os.environ.get('TTL_ORDER_REFRESH', '16'))
 
     def _refresh_processing_order(self, force=False):
@@ -264,6 +267,10 @@ class TrackingEnvironment(BaseEnv):
         if n < self.SPATIAL_ORDER_MIN or self._pending is not None or \
                 not getattr(self, 'spatial_order', True):
             return
+        if not force and self._order_instep():
+            # the library re-buckets the order inside its own steps
+            # (TTL_ORDER_INSTEP): no periodic and no low-fill refresh from here
+            return
         # between refreshes the order keeps its length (the step's fused tail does
         # not compact it: stopped streamlines leave holes at the end of their
         # 256-slot block): refresh early once a fifth of it is holes
@@ -276,6 +283,17 @@ class TrackingEnvironment(BaseEnv):
         _lib.check(self._lib.ttl_env_refresh_processing_order(
             self._handle, self._stream()), 'ttl_env_refresh_processing_order')
         self._order_slots = n
+
+    def _order_instep(self):
+        """Period of the library's in-step re-bucket on this handle (0: off);
+        also takes ``_order_slots`` from the library, which compacts the order
+        on its re-bucket steps."""
+        slots, period = C.c_int32(0), C.c_int32(0)
+        _lib.check(self._lib.ttl_env_order_slots(
+            self._handle, C.byref(slots), C.byref(period)), 'ttl_env_order_slots')
+        if period.value:
+            self._order_slots = slots.value
+        return period.value
 
     def _order_keeps_holes(self):
         """Whether the library runs the one-launch tail on this handle (only then
