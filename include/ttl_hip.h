@@ -311,8 +311,9 @@ TTL_API int ttl_env_harvest_wait(ttl_env *env, const float *state_in, float *sta
  *   Rows 0..n_active-1 (n_active as the previous step left it) are the active
  *   rows; state rows come out survivors first (stable), then the rows that
  *   stopped in this step; rows that left earlier get done = 1, reward = 0 and
- *   keep their old state row.  No Gaussian action noise (TTL_MODE_F64DIR adds
- *   +0.0).
+ *   keep their old state row.  No Gaussian action noise from the caller
+ *   (TTL_MODE_F64DIR adds +0.0) unless ttl_env_set_noise installed keyed noise,
+ *   which the step then draws itself.
  * end: waits for the stream, reads the device words back into the handle
  *   (which then continues as after a harvest) and returns them. */
 TTL_API int ttl_env_freerun_begin(ttl_env *env, int32_t *host_counts, void *hip_stream);
@@ -321,6 +322,52 @@ TTL_API int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_r
                          uint8_t *done_out, void *hip_stream);
 TTL_API int ttl_env_freerun_end(ttl_env *env, int32_t *n_active_out, int32_t *length_out,
                         int32_t *steps_out, void *hip_stream);
+/* Keyed action noise (TTL_HAS_KEYED_NOISE).  Instead of reading
+ * noise rows from the caller, the step's first kernel draws them: the three
+ * float64 normals of a streamline at a step are a pure function of
+ * (seed, id, step), so a tractogram no longer depends on how its seeds were cut
+ * into batches, shards or loop flavours.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ *              0x9E3779B9 / 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32),
+ *              counter = (id & 0xffffffff, id >> 32, step, j), j = 0, 1;
+ *   uniforms   output words c0..c3 of call j: u1 = ((c1:c0 >> 11) + 0.5) * 2^-53,
+ *              u2 likewise from c3:c2;
+ *   normals    r = sqrt(-2 log u1), z[2j] = r cos(2 pi u2), z[2j+1] = r sin(2 pi u2),
+ *              all in float64; a streamline uses z[0], z[1], z[2];
+ *   id         id_base + g, g = the streamline's row of the history buffer;
+ *   step       the length the step finds (1 at the first step after a reset).
+ * The noise of a row is z * sigma_row: sigma_row = sigma, or with an FA map
+ * max(0, (1 - FA) * sigma) (noisy_tracking_env.py:65-72; the clamp is a stated
+ * deviation: a spline can overshoot FA > 1), FA = map_coordinates(fa_coef,
+ * trunc_int32(p) - 0.5, order=3, mode='constant', prefilter=False) at the
+ * streamline's newest point p before the step.
+ *   fa_coef    device f64 [fa_dim[0]][fa_dim[1]][fa_dim[2]] cubic B-spline
+ *              coefficients (scipy.ndimage.spline_filter(order=3)), or NULL;
+ *   noise_out  device f64 [n_total][3] or NULL: row g receives the noise (sigma_row
+ *              included) streamline g was given in the step that advanced it.
+ * ttl_env_set_noise(env, NULL) switches it off.  TTL_MODE_F64DIR only
+ * (TTL_ERR_INVALID otherwise, as for a negative or non-finite sigma, a negative
+ * id_base or a misaligned table); TTL_ERR_STATE between a step and its harvest
+ * and while free-running.  With keyed noise set, ttl_env_step / ttl_env_step_begin
+ * refuse a non-NULL `noise` (TTL_ERR_INVALID), ttl_env_freerun_step draws as well,
+ * and sigma == 0 adds +0.0.  Host state only: no device work. */
+#define TTL_HAS_KEYED_NOISE 1
+typedef struct ttl_noise_desc {
+    uint64_t seed;
+    int64_t id_base;
+    double sigma;
+    const double *fa_coef;
+    int32_t fa_dim[3];
+    double *noise_out;
+} ttl_noise_desc;
+TTL_API int ttl_env_set_noise(ttl_env *env, const ttl_noise_desc *desc);
+
+/* The standard normals above for arbitrary ids (device int64 [n], >= 0) at one
+ * step (>= 0): out [n][3] f64, device.  The same device function as the step's
+ * draw: callers replay the noise of a finished run with it. */
+TTL_API int ttl_noise_normals(uint64_t seed, const int64_t *ids, int32_t n, int32_t step,
+                              double *out, void *hip_stream);
+
 /* Measurement only: ttl_scripted_actions() for a free-running step -- the row
  * count, the step number (length - 1) and the live continue_idx buffer are
  * read from the device words; rows 0..min(n_active, n_rows)-1 are written. */

@@ -70,6 +70,18 @@ class EnvDesc(C.Structure):
     ]
 
 
+class NoiseDesc(C.Structure):
+    """struct ttl_noise_desc (include/ttl_hip.h): keyed action noise."""
+    _fields_ = [
+        ('seed', C.c_uint64),
+        ('id_base', C.c_int64),
+        ('sigma', C.c_double),
+        ('fa_coef', C.c_void_p),
+        ('fa_dim', C.c_int32 * 3),
+        ('noise_out', C.c_void_p),
+    ]
+
+
 class ColsumSeg(C.Structure):
     """struct ttl_colsum_seg (include/ttl_learner.h)."""
     _fields_ = [
@@ -131,6 +143,9 @@ SYMBOLS = {
     'ttl_env_freerun_end': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.c_void_p]),
+    'ttl_env_set_noise': (C.c_int, [C.c_void_p, C.POINTER(NoiseDesc)]),
+    'ttl_noise_normals': (C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p]),
     'ttl_env_stopping_flags': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32,
                                          C.c_int32, C.c_void_p, C.c_void_p]),
     'ttl_env_set_processing_order': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32,

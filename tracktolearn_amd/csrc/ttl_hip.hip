@@ -163,6 +163,120 @@ __device__ bool outside_mask(const EnvParams &P, float px, float py, float pz) {
     return t < P.mask_thr;
 }
 
+// The same spline as a value, on a coefficient table of its own ([X][Y][Z] f64,
+// dims n[3]): map_coordinates(coef, (cx, cy, cz), order=3, mode='constant',
+// cval=0, prefilter=False).  Shares the weights, the border folding and the tap
+// order (x outermost, sequential accumulation, no FMA) with outside_mask; none
+// of its shortcuts.
+__device__ __forceinline__ double spline3_value(const double *__restrict__ coef, int nx, int ny,
+                                                int nz, double cx, double cy, double cz) {
+    const bool inside = (cx >= 0.0 && cx <= (double)(nx - 1)) &&
+                        (cy >= 0.0 && cy <= (double)(ny - 1)) &&
+                        (cz >= 0.0 && cz <= (double)(nz - 1));
+    if (!inside) return 0.0;
+    const double fx = floor(cx), fy = floor(cy), fz = floor(cz);
+    double wx[4], wy[4], wz[4];
+    cubic_weights(cx, fx, wx);
+    cubic_weights(cy, fy, wy);
+    cubic_weights(cz, fz, wz);
+    const int sx = (int)fx - 1, sy = (int)fy - 1, sz = (int)fz - 1;
+    int ix[4], iy[4], iz[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        ix[j] = mirror_fold(sx + j, nx) * ny;
+        iy[j] = mirror_fold(sy + j, ny);
+        iz[j] = mirror_fold(sz + j, nz);
+    }
+    double t = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const double *line = coef + (size_t)(ix[a] + iy[b]) * nz;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                double v = line[iz[d]];
+                v = v * wx[a];
+                v = v * wy[b];
+                v = v * wz[d];
+                t = t + v;
+            }
+        }
+    }
+    return t;
+}
+
+// ---------------------------------------------------------------------------
+// Keyed action noise (ttl_env_set_noise): the three standard
+// normals of a streamline at a step are a pure function of (seed, id, step).
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), key = the two
+// halves of the seed, counter = (id low, id high, step, j) for j = 0, 1; the
+// four output words of call j make two 53-bit uniforms, Box-Muller in float64
+// turns them into z[2j], z[2j + 1].  tests/ref_noise.py restates it in NumPy.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2,
+                                              uint32_t &c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// ((hi:lo >> 11) + 0.5) * 2^-53
+__device__ __forceinline__ double philox_uniform(uint32_t lo, uint32_t hi) {
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    return ((double)(w >> 11) + 0.5) * 1.1102230246251565e-16;
+}
+
+__device__ __forceinline__ void keyed_normals(unsigned long long seed, long long id, uint32_t step,
+                                              double &z0, double &z1, double &z2) {
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t i0 = (uint32_t)(unsigned long long)id;
+    const uint32_t i1 = (uint32_t)((unsigned long long)id >> 32);
+    uint32_t c0 = i0, c1 = i1, c2 = step, c3 = 0u;
+    philox4x32_10(c0, c1, c2, c3, k0, k1);
+    double r = sqrt(-2.0 * log(philox_uniform(c0, c1)));
+    double sn, cs;
+    sincospi(2.0 * philox_uniform(c2, c3), &sn, &cs);
+    z0 = r * cs;
+    z1 = r * sn;
+    c0 = i0, c1 = i1, c2 = step, c3 = 1u;
+    philox4x32_10(c0, c1, c2, c3, k0, k1);
+    r = sqrt(-2.0 * log(philox_uniform(c0, c1)));
+    z2 = r * cospi(2.0 * philox_uniform(c2, c3));
+}
+
+// what ttl_env_set_noise installed, as the noisy kernels receive it
+struct NoiseParams {
+    unsigned long long seed;
+    long long id_base;
+    double sigma;
+    const double *fa_coef;   // cubic B-spline coefficients of the FA map, or null
+    int fa_dim[3];
+    double *noise_out;       // [n_total][3] per streamline id: the noise it was given, or null
+};
+
+static_assert(sizeof(NoiseParams) <= (64 - TTL_FR_NOISE) * sizeof(int),
+              "the record must fit behind TTL_FR_NOISE in EnvParams::counts");
+
+// where the noise of a step comes from: the caller's rows (or null for +0.0),
+// or a draw inside the kernel
+template <bool KEYED>
+struct NoiseSource {
+    typedef const double *__restrict__ type;
+};
+template <>
+struct NoiseSource<true> {
+    typedef NoiseParams type;
+};
+
 // tracking_env.py:165-178: at the first step all criteria run on the 2-point
 // trial streamline; only LENGTH (2 >= max_nb_steps) and MASK can fire there.
 // NOTE (ROCm 7.2 hipcc): written as `a || outside_mask(..)` followed by
@@ -256,11 +370,11 @@ __device__ __forceinline__ void block_survivor_ranks(const EnvParams &P, int i,
 // One active row of a step: streamline g = idx[i] grows by one point, the
 // stopping criteria are tested on it, reward / done / head records are written.
 // Returns whether the streamline stops.
-template <int MODE>
+template <int MODE, bool KEYED>
 __device__ __forceinline__ bool advance_row(
     const EnvParams &P, int g, int i, const float *__restrict__ actions,
-    const double *__restrict__ noise, int L, double *__restrict__ reward_out,
-    uint8_t *__restrict__ done_out) {
+    const typename NoiseSource<KEYED>::type &noise, int L,
+    double *__restrict__ reward_out, uint8_t *__restrict__ done_out) {
     bool stop = false;
     {
         float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
@@ -307,7 +421,35 @@ __device__ __forceinline__ bool advance_row(
             } else {
                 // (actions + noise) in float64 -> normalise -> * step_size
                 double a0 = (double)ax, a1 = (double)ay, a2 = (double)az;
-                if (noise) {
+                if constexpr (KEYED) {
+                    // sigma of the row: noise, or max(0, (1 - FA) * noise) with FA
+                    // sampled like the mask at trunc(newest point) - 0.5
+                    // (noisy_tracking_env.py:65-72; the clamp is ours)
+                    double sigma = noise.sigma;
+                    if (noise.fa_coef) {
+                        const double fa = spline3_value(
+                            noise.fa_coef, noise.fa_dim[0], noise.fa_dim[1], noise.fa_dim[2],
+                            (double)(int)p1x - 0.5, (double)(int)p1y - 0.5,
+                            (double)(int)p1z - 0.5);
+                        sigma = fmax(0.0, (1.0 - fa) * sigma);
+                    }
+                    double z0, z1, z2;
+                    keyed_normals(noise.seed, noise.id_base + (long long)g, (uint32_t)L, z0, z1,
+                                  z2);
+                    // sigma == 0 (also a row the FA clamp silenced) adds +0.0
+                    z0 = sigma > 0.0 ? z0 * sigma : 0.0;
+                    z1 = sigma > 0.0 ? z1 * sigma : 0.0;
+                    z2 = sigma > 0.0 ? z2 * sigma : 0.0;
+                    if (noise.noise_out) {
+                        double *o = noise.noise_out + (size_t)g * 3;
+                        o[0] = z0;
+                        o[1] = z1;
+                        o[2] = z2;
+                    }
+                    a0 = a0 + z0;
+                    a1 = a1 + z1;
+                    a2 = a2 + z2;
+                } else if (noise) {
                     a0 = a0 + noise[(size_t)i * 3 + 0];
                     a1 = a1 + noise[(size_t)i * 3 + 1];
                     a2 = a2 + noise[(size_t)i * 3 + 2];
@@ -399,16 +541,16 @@ __device__ __forceinline__ bool advance_row(
     return stop;
 }
 
-template <int MODE>
+template <int MODE, bool KEYED = false>
 __global__ __launch_bounds__(BLOCK) void k_advance(
     EnvParams P, const int *__restrict__ idx, const float *__restrict__ actions,
-    const double *__restrict__ noise, int n_active, int L,
+    const typename NoiseSource<KEYED>::type noise, int n_active, int L,
     double *__restrict__ reward_out, uint8_t *__restrict__ done_out) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     const bool active = i < n_active;
     bool stop = false;
     if (active)
-        stop = advance_row<MODE>(P, idx[i], i, actions, noise, L, reward_out, done_out);
+        stop = advance_row<MODE, KEYED>(P, idx[i], i, actions, noise, L, reward_out, done_out);
     block_survivor_ranks(P, i, active, active && !stop);
 }
 
@@ -422,7 +564,10 @@ __global__ __launch_bounds__(BLOCK) void k_advance(
 // P.counts + TTL_FR_SNAP  = the same four words as this step found them:
 // written by k_advance_fr, read by k_prefix_state_fr.
 // ---------------------------------------------------------------------------
-template <int MODE>
+// KEYED: the noise is drawn from the record ttl_env_freerun_begin left at
+// P.counts + TTL_FR_NOISE -- device memory, not a kernel argument, so that a
+// captured step stays valid when the next batch brings another id_base
+template <int MODE, bool KEYED = false>
 __global__ __launch_bounds__(BLOCK) void k_advance_fr(
     EnvParams P, const int *__restrict__ idx_a, const int *__restrict__ idx_b,
     const float *__restrict__ actions, int n_cap, double *__restrict__ reward_out,
@@ -448,12 +593,37 @@ __global__ __launch_bounds__(BLOCK) void k_advance_fr(
     const bool active = i < n_active;
     bool stop = false;
     if (active) {
-        stop = advance_row<MODE>(P, idx[i], i, actions, nullptr, L, reward_out, done_out);
+        if constexpr (KEYED)
+            stop = advance_row<MODE, true>(
+                P, idx[i], i, actions,
+                *reinterpret_cast<const NoiseParams *>(P.counts + TTL_FR_NOISE), L, reward_out,
+                done_out);
+        else
+            stop = advance_row<MODE, false>(P, idx[i], i, actions, nullptr, L, reward_out,
+                                            done_out);
     } else if (i < n_cap) {      // rows that left the episode earlier
         done_out[i] = 1;
         if (reward_out) reward_out[i] = 0.0;
     }
     block_survivor_ranks(P, i, active, active && !stop);
+}
+
+// ttl_noise_normals: the draw of the noisy step for caller-supplied ids
+__global__ __launch_bounds__(BLOCK) void k_noise_normals(unsigned long long seed,
+                                                         const long long *__restrict__ ids, int n,
+                                                         uint32_t step, double *__restrict__ out) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double z0, z1, z2;
+    keyed_normals(seed, ids[i], step, z0, z1, z2);
+    out[(size_t)i * 3 + 0] = z0;
+    out[(size_t)i * 3 + 1] = z1;
+    out[(size_t)i * 3 + 2] = z2;
+}
+
+// the keyed-noise record of a free-running episode (see k_advance_fr)
+__global__ void k_fr_noise(EnvParams P, NoiseParams noise) {
+    *reinterpret_cast<NoiseParams *>(P.counts + TTL_FR_NOISE) = noise;
 }
 
 __global__ void k_fr_init(EnvParams P, int n_active, int length, int cur) {
@@ -1179,6 +1349,8 @@ struct ttl_env {
     int n_exact;           // n_active is the exact survivor count (read back)
     int fr_cap;            // > 0: free-running steps are being enqueued for this many rows
     int *fr_host_word;     // device address of the pinned words a free-running step reports to
+    int keyed;             // ttl_env_set_noise: the steps draw their noise themselves ...
+    NoiseParams noise;     // ... from this
     int prof_on;
     int prof_mask;    // bit k: time kernel class k
     int prof_cap;     // event pairs available per kernel class
@@ -1545,6 +1717,8 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
     e->n_exact = 0;
     e->fr_cap = 0;
     e->fr_host_word = nullptr;
+    e->keyed = 0;
+    memset(&e->noise, 0, sizeof(e->noise));
     e->prof_mask = (1 << TTL_PROFILE_CLASSES) - 1;
     e->prof_on = 0;
     e->prof_cap = 0;
@@ -1714,6 +1888,9 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
         return fail(TTL_ERR_STATE, "ttl_env_step: streamline history is full");
     if (noise && d.mode != TTL_MODE_F64DIR)
         return fail(TTL_ERR_INVALID, "ttl_env_step: noise needs TTL_MODE_F64DIR");
+    if (noise && env->keyed)
+        return fail(TTL_ERR_INVALID, "ttl_env_step: keyed noise is set (ttl_env_set_noise), "
+                                     "the step takes no noise rows");
     hipStream_t s = (hipStream_t)hip_stream;
     const int *idx = env->cur ? d.idx_b : d.idx_a;
     const int L = env->length;
@@ -1722,7 +1899,10 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
 #define TTL_LAUNCH_ADVANCE(M)                                                  \
     hipLaunchKernelGGL((k_advance<M>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx, \
                        actions, noise, n_active, L, reward_out, done_out)
-    if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE(TTL_MODE_F32);
+    if (env->keyed)      // TTL_MODE_F64DIR (ttl_env_set_noise)
+        hipLaunchKernelGGL((k_advance<TTL_MODE_F64DIR, true>), dim3(nb), dim3(BLOCK), 0, s, env->P,
+                           idx, actions, env->noise, n_active, L, reward_out, done_out);
+    else if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE(TTL_MODE_F32);
     else if (d.mode == TTL_MODE_F64DIR) TTL_LAUNCH_ADVANCE(TTL_MODE_F64DIR);
     else TTL_LAUNCH_ADVANCE(TTL_MODE_F32NORM);
 #undef TTL_LAUNCH_ADVANCE
@@ -2065,6 +2245,10 @@ int ttl_env_freerun_begin(ttl_env *env, int32_t *host_counts, void *hip_stream) 
     hipLaunchKernelGGL(k_fr_init, dim3(1), dim3(1), 0, s, env->P, env->n_active, env->length,
                        env->cur);
     HIP_TRY(hipGetLastError());
+    if (env->keyed) {
+        hipLaunchKernelGGL(k_fr_noise, dim3(1), dim3(1), 0, s, env->P, env->noise);
+        HIP_TRY(hipGetLastError());
+    }
     env->use_proc = 0;
     env->counts_pending = 0;
     env->fr_cap = env->n_active;
@@ -2092,7 +2276,10 @@ int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_rows, flo
 #define TTL_LAUNCH_ADVANCE_FR(M)                                                     \
     hipLaunchKernelGGL((k_advance_fr<M>), dim3(nb), dim3(BLOCK), 0, s, env->P, d.idx_a, \
                        d.idx_b, actions, n_cap, reward_out, done_out)
-    if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F32);
+    if (env->keyed)
+        hipLaunchKernelGGL((k_advance_fr<TTL_MODE_F64DIR, true>), dim3(nb), dim3(BLOCK), 0, s,
+                           env->P, d.idx_a, d.idx_b, actions, n_cap, reward_out, done_out);
+    else if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F32);
     else if (d.mode == TTL_MODE_F64DIR) TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F64DIR);
     else TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F32NORM);
 #undef TTL_LAUNCH_ADVANCE_FR
@@ -2134,6 +2321,60 @@ int ttl_env_freerun_end(ttl_env *env, int32_t *n_active_out, int32_t *length_out
     if (n_active_out) *n_active_out = live[0];
     if (length_out) *length_out = live[1];
     if (steps_out) *steps_out = live[3];
+    return TTL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Keyed action noise: host state only, the draw happens in the step's first kernel.
+// ---------------------------------------------------------------------------
+int ttl_env_set_noise(ttl_env *env, const ttl_noise_desc *desc) {
+    if (!env) return fail(TTL_ERR_INVALID, "ttl_env_set_noise: null handle");
+    if (env->d.mode != TTL_MODE_F64DIR)
+        return fail(TTL_ERR_INVALID, "ttl_env_set_noise: needs TTL_MODE_F64DIR");
+    if (desc) {
+        if (!(desc->sigma >= 0.0) || !std::isfinite(desc->sigma))
+            return fail(TTL_ERR_INVALID, "ttl_env_set_noise: sigma must be finite and >= 0");
+        if (desc->id_base < 0)
+            return fail(TTL_ERR_INVALID, "ttl_env_set_noise: id_base must be >= 0");
+        if (desc->fa_coef) {
+            if (((uintptr_t)desc->fa_coef) & 7)
+                return fail(TTL_ERR_INVALID, "ttl_env_set_noise: fa_coef misaligned");
+            for (int a = 0; a < 3; ++a)
+                if (desc->fa_dim[a] < 1)
+                    return fail(TTL_ERR_INVALID, "ttl_env_set_noise: non-positive fa_dim");
+        }
+        if (((uintptr_t)desc->noise_out) & 7)
+            return fail(TTL_ERR_INVALID, "ttl_env_set_noise: noise_out misaligned");
+    }
+    if (env->stepped)
+        return fail(TTL_ERR_STATE, "ttl_env_set_noise: harvest the pending step first");
+    if (env->fr_cap)
+        return fail(TTL_ERR_STATE, "ttl_env_set_noise: free-running steps are enqueued, call "
+                                   "ttl_env_freerun_end first");
+    env->keyed = desc != nullptr;
+    memset(&env->noise, 0, sizeof(env->noise));
+    if (desc) {
+        env->noise.seed = desc->seed;
+        env->noise.id_base = desc->id_base;
+        env->noise.sigma = desc->sigma;
+        env->noise.fa_coef = desc->fa_coef;
+        for (int a = 0; a < 3; ++a) env->noise.fa_dim[a] = desc->fa_coef ? desc->fa_dim[a] : 0;
+        env->noise.noise_out = desc->noise_out;
+    }
+    return TTL_OK;
+}
+
+int ttl_noise_normals(uint64_t seed, const int64_t *ids, int32_t n, int32_t step, double *out,
+                      void *hip_stream) {
+    if (!ids || !out) return fail(TTL_ERR_INVALID, "ttl_noise_normals: null argument");
+    if (n < 0 || step < 0) return fail(TTL_ERR_INVALID, "ttl_noise_normals: negative n or step");
+    if ((((uintptr_t)ids) & 7) || (((uintptr_t)out) & 7))
+        return fail(TTL_ERR_INVALID, "ttl_noise_normals: misaligned pointer");
+    if (n == 0) return TTL_OK;
+    hipLaunchKernelGGL(k_noise_normals, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, (unsigned long long)seed,
+                       (const long long *)ids, n, (uint32_t)step, out);
+    HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
 

@@ -82,6 +82,9 @@ constexpr int TTL_FUSE_MAX_BLOCKS = 256;
 // a step works from
 constexpr int TTL_FR_LIVE = 8;
 constexpr int TTL_FR_SNAP = 16;
+// ... and of the keyed-noise record of a free-running episode (56 bytes, 8-byte
+// aligned: counts is 256-byte aligned), written by ttl_env_freerun_begin
+constexpr int TTL_FR_NOISE = 32;
 
 // Record index of voxel (x, y, z) = vox_x(x) + vox_y(y) + vox_z(z), for both
 // record orders (separable, so the gather keeps per-axis partial offsets).

@@ -5,7 +5,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
     ttl_track.py in_odf in_seed in_mask out_tractogram [--input_wm]
         [--sh_basis B] [--compress T] [-f] [--save_seeds] [--agent DIR]
         [--hyperparameters JSON] [--n_actor N] [--npv N] [--min_length m]
-        [--max_length M] [--noise s] [--fa_map F]
+        [--max_length M] [--noise s] [--keyed_noise] [--fa_map F]
         [--binary_stopping_threshold t] [--rng_seed S]
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
@@ -44,6 +44,17 @@ def per_rank_noise_rng(rng_seed, rank):
     return np.random.RandomState((int(rng_seed) + 1 + int(rank)) % (2 ** 32))
 
 
+def load_fa_map(fa_map_file, in_mask):
+    """The FA volume of ``--fa_map`` (float64), on the tracking mask's grid."""
+    fa = nifti.load(fa_map_file)
+    mask = nifti.load(in_mask)
+    if tuple(fa.shape[:3]) != tuple(mask.shape[:3]) or \
+            not np.allclose(fa.affine, mask.affine, atol=1e-3):
+        raise ValueError('--fa_map {} is not on the grid of the tracking mask {}'.format(
+            fa_map_file, in_mask))
+    return np.asarray(fa.get_fdata(dtype=np.float64)).reshape(fa.shape[:3])
+
+
 #: track_dto keys copied onto the experiment as they are (argparse names)
 _PASS_THROUGH = ('in_odf', 'in_seed', 'in_mask', 'out_tractogram', 'noise',
                  'binary_stopping_threshold', 'n_actor', 'npv', 'min_length',
@@ -71,6 +82,9 @@ class TrackToLearnTrack(object):
         self.compute_reward, self.alignment_weighting = False, 0.0
         self.oracle_checkpoint, self.oracle_bonus = None, 0.0
         self.oracle_stopping_criterion = False
+        # --fa_map implies keyed noise: only the in-kernel draw scales by FA
+        self.fa_map_file = track_dto.get('fa_map')
+        self.keyed_noise = bool(track_dto.get('keyed_noise')) or bool(self.fa_map_file)
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -96,6 +110,10 @@ class TrackToLearnTrack(object):
             'input_wm')}
         env_dto.update(dataset_file=None, scoring_data=None, step_size=self.step_size,
                        reference=self.in_odf)
+        if self.keyed_noise:
+            env_dto.update(device_noise='keyed', noise_seed=self.random_seed)
+        if self.fa_map_file:
+            env_dto['fa_map'] = load_fa_map(self.fa_map_file, self.in_mask)
         return NoisyTrackingEnvironment.from_files(env_dto)
 
     def _step_for_subject(self, subject_voxel_size):
@@ -131,7 +149,9 @@ class TrackToLearnTrack(object):
         # re-derives the step in voxels, the step counts and the neighbourhood
         # radius from the rescaled step (environments/env.py:196-212)
         env.load_subject()
-        if tracker.group_size > 1:
+        if tracker.group_size > 1 and not self.keyed_noise:
+            # (keyed noise needs no generator: every shard resets with its global
+            # start offset, so the streamline ids are those of the one-GPU run)
             env.noise_rng = per_rank_noise_rng(self.random_seed, tracker.rank)
         tractogram = tracker.track(env, detect_format(self.out_tractogram))
         if tracker.rank != 0:
@@ -203,9 +223,15 @@ def add_track_args(parser):
                          help='Add noise ~ N (0, `noise`) to the agent\'s\n'
                               'output to make tracking more probabilistic.'
                               '[%(default)s]')
+    track_g.add_argument('--keyed_noise', action='store_true',
+                         help='Draw the noise on the GPU as a function of '
+                              '(--rng_seed, seed index, step):\nthe tractogram '
+                              'no longer depends on --n_actor or on the number '
+                              'of GPUs.\nNot the NumPy stream of the default.')
     track_g.add_argument('--fa_map', type=str, default=None,
                          help='Scale the added noise according to an FA map '
-                              '(unsupported, see noisy_tracking_env.py).')
+                              '(.nii.gz on the grid of\nin_mask): std = '
+                              '(1 - FA) * `noise`. Implies --keyed_noise.')
     track_g.add_argument('--binary_stopping_threshold', type=float, default=0.1,
                          help='Lower limit for interpolation of tracking mask '
                               'value.\nTracking will stop below this '
