@@ -220,7 +220,8 @@ def oracle_and_coverage(scores, visited, mask):
 
 # ---------------------------------------------------------------- resampler
 def resample_blocked(points, nb_points=128):
-    """k_resample on one streamline (L, 3) float32, L >= 2, in its own order:
+    """k_resample on one streamline (L, 3) float32, L >= 1 (one point: the
+    output is that point, every difference a zero vector), in its own order:
     lane l of 64 sums the float64 segment lengths [l per, (l + 1) per)
     sequentially, a Hillis-Steele scan over the lanes gives the inclusive
     prefix, the exclusive one is that minus the lane's sum, cum[j + 1] =

@@ -91,9 +91,11 @@ def test_hip_peaks_recover_known_fibres():
 @pytest.mark.parametrize('order,shape', [(8, (24, 20, 16)), (6, (9, 7, 11)), (4, (5, 5, 5)),
                                          (12, (6, 5, 4))])
 def test_hip_peaks_match_the_torch_reference(order, shape):
-    """Random smooth fODF-like volumes: the kernel picks the same vertices as
-    the plain PyTorch reference (fp32 GEMM + vectorised selection) except where
-    two SF values are within rounding of each other or of a threshold."""
+    """Random smooth fODF-like volumes: the kernel equals the ordered float32
+    restatement (``ref_peaks.peaks_ordered``) bit for bit on every voxel, and
+    picks the same vertices as the plain PyTorch reference (fp32 GEMM in
+    another summation order + vectorised selection) except where two SF
+    values are within rounding of each other or of a threshold."""
     C = (order + 1) * (order + 2) // 2
     rng = np.random.RandomState(order)
     sh = (rng.standard_normal(shape + (C,)) * 0.2).astype(np.float32)
@@ -105,6 +107,12 @@ def test_hip_peaks_match_the_torch_reference(order, shape):
     got = pk.peaks_from_sh(t).cpu().numpy().reshape(-1, 5, 3)
     want = ref_peaks.peaks_from_sh(t).cpu().numpy().reshape(-1, 5, 3)
     assert np.all(got[0] == 0)
+    verts, nbr = pk.hemisphere(3)
+    B = pk.sh_to_sf_matrix(verts, order).astype(np.float32)
+    _, ordered = ref_peaks.peaks_ordered(
+        sh.reshape(-1, C), B, verts.astype(np.float32), nbr, 5, 0.1, 0.0,
+        np.float32(np.cos(np.deg2rad(25.0))), 16)
+    assert np.array_equal(got.reshape(-1, 15).view(np.uint32), ordered.view(np.uint32))
     same = np.abs(got - want).max(axis=(1, 2)) <= 1e-5
     assert same.mean() >= 0.995, same.mean()
     # where they differ, both still return unit-or-shorter, value-sorted peaks

@@ -9,8 +9,9 @@ stores 15 floats per voxel.  The reference does this voxel by voxel in Python
 (minutes at 145^3); here it is one
 hand-written HIP kernel (``k_peaks`` in csrc/ttl_peaks.hip, C ABI
 ``ttl_peaks_from_sh``): one wavefront per voxel, the SH->SF matrix staged in
-LDS, maxima / thresholds / separation decided wave-wide.  (A plain PyTorch
-fp32 restatement lives in tests/ref_peaks.py as the numerics reference.)
+LDS, maxima / thresholds / separation decided wave-wide.  (tests/ref_peaks.py
+holds its references: an ordered float32 restatement the kernel equals bit
+for bit, the float64 definition, and a plain PyTorch fp32 restatement.)
 
 PARITY UNPINNED: the reference's sphere is dipy's ``repulsion724`` vertex
 table (data that cannot be regenerated offline) and the basis / peak code is
