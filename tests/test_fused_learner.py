@@ -11,9 +11,11 @@ inputs, and the fused update on cuda:0 against the autograd update on cuda:0
 and against float64."""
 import copy
 
+import numpy as np
 import pytest
 import torch
 
+import ref_learner_ordered as ordered
 from ref_learner_ops import TorchOps
 
 CPU = torch.device('cpu')
@@ -163,6 +165,19 @@ def _close(a, b, rtol, atol, what):
     assert bool((err <= tol).all()), (what, float(err.max()), float((err / tol).max()))
 
 
+def _same_bits(hip, restated, what):
+    """The kernel's output equals tests/ref_learner_ordered.py (NumPy float32
+    in the kernel's own order) bit for bit."""
+    got = hip.detach().cpu().contiguous().numpy().reshape(-1)
+    want = np.ascontiguousarray(restated, np.float32).reshape(-1)
+    bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
+    assert bad.size == 0, (what, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+def _np(t):
+    return t.detach().cpu().contiguous().numpy()
+
+
 def _no_worse(hip, ref32, ref64, what, factor=4.0, atol=1e-7):
     """|hip - float64| <= factor * |torch float32 restatement - float64| + atol,
     in the max norm: the kernel is as accurate as the same formula through
@@ -182,7 +197,8 @@ def test_thin_forward_kernels(M, H, A):
     hip, ref = HipOps(DEV), TorchOps()
     g = torch.Generator().manual_seed(M + H)
     # strided rows (ld > H) as the side-by-side critic activations have
-    a = torch.randn(M, H + 8, generator=g).to(DEV)[:, :H]
+    a_full = torch.randn(M, H + 8, generator=g).to(DEV)
+    a = a_full[:, :H]
     w = (torch.randn(2 * A, H, generator=g) / H ** 0.5).to(DEV)
     w[A:] *= 4                                             # some log_std beyond the clamp
     b = torch.randn(2 * A, generator=g).to(DEV)
@@ -203,6 +219,12 @@ def test_thin_forward_kernels(M, H, A):
         _no_worse(outs[0][k], outs[1][k], outs[2][k], what)
     o1 = outs[0][0]
     assert float(o1[:, :2].abs().max()) == 0 and float(o1[:, 2 + A:].abs().max()) == 0
+    # ... and the sums in the kernel's own order: log_std_raw bit for bit (pi, logp
+    # and the partials are behind libm calls: test_learner_kernels_reference.py)
+    V = ordered.vec_width(H, (H + 8,))
+    r = ordered.thin_forward(_np(a_full), H + 8, 0, _np(w), _np(b), M, H, 2 * A, False, HEAD_SAC, V,
+                             eps=_np(eps), entropy_rows=ent_rows)
+    _same_bits(outs[0][2], r['log_std_raw'], 'log_std_raw')
     # plain / tanh heads, dense and block-diagonal
     for n_out, head in ((2 * A, HEAD_PLAIN), (A, HEAD_TANH), (1, HEAD_PLAIN)):
         res = []
@@ -212,6 +234,8 @@ def test_thin_forward_kernels(M, H, A):
                              b[:n_out].contiguous().to(dt), n_out, False, head, out, n_out + 1)
             res.append(out)
         _no_worse(*res, (n_out, head))
+        if head == HEAD_PLAIN:
+            _same_bits(res[0][:, :n_out], r['y'][:, :n_out], (n_out, head))
     a2 = torch.randn(M, 2 * H, generator=g).to(DEV)
     res = []
     for ops, dt in ((hip, torch.float32), (ref, torch.float32), (ref, torch.float64)):
@@ -220,6 +244,9 @@ def test_thin_forward_kernels(M, H, A):
                          HEAD_PLAIN, out, 2)
         res.append(out)
     _no_worse(*res, 'block diagonal')
+    r = ordered.thin_forward(_np(a2), 2 * H, H, _np(w[:2]), _np(b[:2]), M, H, 2, True, HEAD_PLAIN,
+                             ordered.vec_width(H, (2 * H, H)))
+    _same_bits(res[0], r['y'], 'block diagonal')
     # ... and with the two networks in planes of their own [2 x M x H]
     planes = torch.stack([a2[:, :H], a2[:, H:]]).contiguous()
     out_p = torch.zeros(M, 2, device=DEV)
@@ -257,7 +284,14 @@ def test_backward_kernels(M, H):
         part = torch.full((R, H + 6 * H + 6), 7.0, device=DEV, dtype=dt)
         ops.thin_backward(d_out.to(dt), a.to(dt), w.to(dt), 6, False, r0, r1, dz, part)
         return dz, part, part.sum(0)
-    _check_three(_three(dense), ('thin dense dz', 'thin dense slab', 'thin dense sums'))
+    res_dense = _three(dense)
+    _check_three(res_dense, ('thin dense dz', 'thin dense slab', 'thin dense sums'))
+    rpb = _rows_per_block(M)
+    r = ordered.thin_backward(_np(d_out), 6, _np(a), H, 0, _np(w), M, H, 6, False, r0, r1, rpb,
+                              np.zeros(M * H, np.float32), H, 0,
+                              np.full(R * (7 * H + 6), 7.0, np.float32), 7 * H + 6)
+    _same_bits(res_dense[0][0], r['dz'], 'thin dense dz')
+    _same_bits(res_dense[0][1], r['part'], 'thin dense slab')
     # block diagonal (the two critics side by side, ld > 2H)
     a2 = torch.relu(torch.randn(M, 2 * H + 4, generator=g)).to(DEV)
     dq = torch.randn(M, 2, generator=g).to(DEV)
@@ -270,6 +304,11 @@ def test_backward_kernels(M, H):
         return dz, part
     res_bd = _three(blockdiag)
     _check_three(res_bd, ('thin bd dz', 'thin bd slab'))
+    r = ordered.thin_backward(_np(dq), 2, _np(a2), 2 * H + 4, H, _np(w2), M, H, 2, True, r0, r1, rpb,
+                              np.zeros(2 * M * H, np.float32), 2 * H, H,
+                              np.full(R * (4 * H + 2), 7.0, np.float32), 4 * H + 2)
+    _same_bits(res_bd[0][0], r['dz'], 'thin bd dz')
+    _same_bits(res_bd[0][1], r['part'], 'thin bd slab')
     # the same with activations and gradients in planes [2 x M x H]: same bits
     from tracktolearn_amd.algorithms.shared.fused import HipOps
     a_pl = torch.stack([a2[:, :H], a2[:, H:2 * H]]).contiguous()
@@ -289,6 +328,10 @@ def test_backward_kernels(M, H):
     res = _three(relu)
     assert torch.equal(res[0][0], res[1][0])
     _check_three(res, ('relu dz', 'relu slab'))
+    r = ordered.relu_backward_bias(_np(d0), 2 * H, 0, _np(a2), 2 * H + 4, 0, 1, M, 2 * H, r0, r1,
+                                   rpb, np.full(R * 2 * H, 7.0, np.float32), 2 * H)
+    _same_bits(res[0][0], r['dz'], 'relu dz')
+    _same_bits(res[0][1], r['part'], 'relu slab')
     dz_pl = torch.stack([d0[:, :H], d0[:, H:]]).contiguous()
     part_pl = torch.full((R, 2 * H), 7.0, device=DEV)
     HipOps(DEV).relu_backward_bias(dz_pl, a_pl, r0, r1, part_pl)
@@ -303,7 +346,15 @@ def test_backward_kernels(M, H):
         ops.colsum_finalize([(part.to(dt), 0, 2 * H, o1, 1.0), (narrow.to(dt), 0, 8, o2, 0.25),
                              (narrow.to(dt)[:77], 3, 1, o3, 1.0 / 77)])
         return o1, o2, o3
-    _check_three(_three(finalize), ('finalize wide', 'finalize narrow', 'finalize scalar'))
+    res_fin = _three(finalize)
+    _check_three(res_fin, ('finalize wide', 'finalize narrow', 'finalize scalar'))
+    zero = np.zeros(2 * H, np.float32)
+    _same_bits(res_fin[0][0], ordered.colsum_finalize(_np(part), 2 * H, R, 2 * H, zero, 1.0, 0),
+               'finalize wide')
+    _same_bits(res_fin[0][1], ordered.colsum_finalize(_np(narrow), 8, 300, 8, zero, 0.25, 0),
+               'finalize narrow')
+    _same_bits(res_fin[0][2], ordered.colsum_finalize(_np(narrow).reshape(-1)[3:], 8, 77, 1, zero,
+                                                      1.0 / 77, 0), 'finalize scalar')
     # actor-loss gradient through the critics' first layer + head backward
     dh = torch.randn(M, 2 * H, generator=g).to(DEV)
     wa = torch.randn(3, 2 * H, generator=g).to(DEV)
@@ -318,7 +369,15 @@ def test_backward_kernels(M, H):
                                     pi.to(dt)[:, 4:], 9, eps.to(dt), raw.to(dt),
                                     None if log_alpha is None else log_alpha.to(dt), const, d_head)
             return (d_head,)
-        _check_three(_three(head), ('head backward',))
+        res_head = _three(head)
+        _check_three(res_head, ('head backward',))
+        if log_alpha is None:
+            # the mu half is exact arithmetic (the log-std half is behind expf)
+            r = ordered.actor_head_backward(
+                _np(dh), 2 * H, _np(a2), 2 * H + 4, _np(wa), M, 2 * H, 3, 1,
+                ordered.vec_width(2 * H, (2 * H, 2 * H + 4)), _np(pi).reshape(-1)[4:], 9, _np(eps),
+                _np(raw), const, np.zeros(M * 6, np.float32))
+            _same_bits(res_head[0][0][:, :3], r['d_head'].reshape(M, 6)[:, :3], 'head backward, mu')
 
 
 @pytest.mark.gpu
@@ -745,32 +804,74 @@ def test_fused_td3_ddpg_update_on_the_gpu_matches_autograd(cls_name, hidden, W, 
     """cuda:0: the fused TD3 / DDPG update (HIP kernels + GEMMs) against the
     autograd update on the same device, two updates from identical states:
     >= 99.8 % of the parameters within 1e-5, none beyond 2 lr; losses within
-    1e-5 relative."""
+    1e-5 relative.  Gradients as in the SAC test: every ``p.grad`` the fused
+    update leaves within 5e-3 in L2 of a float64 CPU run from the same state
+    (ReLU / min decisions within rounding of their boundary route a row
+    differently; typical tensors 1e-6) -- of the gradient each optimizer
+    stepped with in that run: autograd also adds the actor loss's gradient to
+    the first critic's ``.grad`` after the critics have stepped, which nothing
+    consumes and the fused update does not form."""
+    ref64, _ = _det_pair(cls_name, hidden, W, B, torch.float64)
     plain, fused = _det_pair(cls_name, hidden, W, B, torch.float32, device=DEV)
     plain.use_fused_learner = False
+    for alg in (plain, fused):
+        _sync_det(alg, ref64, torch.float32, DEV)
+    stepped = {}
+    for opt in (ref64.actor_optimizer, ref64.critic_optimizer):
+        _note_gradients_at_step(opt, stepped)
     g = torch.Generator().manual_seed(6)
     lr = 3e-4
     for u, (batch, _) in enumerate(_batches(2, B, W, torch.float32, device=DEV)):
         if u:
             _sync_det(plain, fused)
+            _sync_det(ref64, fused, torch.float64, 'cpu')
         noise = torch.randn(B, 3, generator=g).to(DEV)
-        monkeypatch.setattr(torch, 'randn_like', lambda t, **kw: noise)
+        monkeypatch.setattr(torch, 'randn_like', lambda t, **kw: noise.to(t.device, t.dtype))
+        stepped.clear()
+        ref64.update([t.double().cpu() for t in batch])
         l_plain = plain.update(batch)
         l_fused = fused.update(batch)
-        assert fused._fused is not None and plain._fused is None
-        for (name, pp), (_, pf) in zip(_params(plain), _params(fused)):
+        assert fused._fused is not None and plain._fused is None and ref64._fused is None
+        worst, n_checked = 0.0, 0
+        for (name, p64), (_, pp), (_, pf) in zip(_params(ref64), _params(plain), _params(fused)):
+            if p64 in stepped:
+                e_f = _grad_err(pf.grad, stepped[p64])
+                worst, n_checked = max(worst, e_f), n_checked + 1
+                assert e_f <= 5e-3, (u, name, e_f)
             d = (pf.detach() - pp.detach()).abs()
             assert float(d.max()) <= 2 * lr, (u, name, float(d.max()))
             assert float((d <= 1e-5).float().mean()) >= 0.998, (u, name)
+        # the critics step in every update, the actor in TD3's second and DDPG's both
+        n_critic = len(list(ref64.agent.critic.parameters()))
+        n_actor = len(list(ref64.agent.actor.parameters()))
+        assert n_checked == n_critic + (n_actor if u or cls_name == 'DDPG' else 0)
+        print(f'{cls_name} {hidden} update {u}: worst gradient L2 error vs float64 {worst:.2e}')
         for k in l_plain:
             a, b = float(l_plain[k]), float(l_fused[k])
             assert abs(a - b) <= 1e-5 * max(1.0, abs(a)), (u, k, a, b)
     assert fused.total_it == plain.total_it == 2
 
 
-def _sync_det(dst, src):
+def _note_gradients_at_step(opt, store):
+    """store[p] = the gradient ``opt`` steps with, for each of its parameters."""
+    real = opt.step
+
+    def step(*args, **kw):
+        for group in opt.param_groups:
+            for p in group['params']:
+                store[p] = p.grad.detach().clone()
+        return real(*args, **kw)
+    opt.step = step
+
+
+def _sync_det(dst, src, dtype=None, device=None):
+    """dst <- src: weights, targets and optimizer state (cast when asked)."""
+    def cast(sd):
+        return sd if dtype is None else {k: v.to(device, dtype) for k, v in sd.items()}
     for name in ('agent', 'target'):
-        getattr(dst, name).load_state_dict(getattr(src, name).state_dict())
+        sd = getattr(src, name).state_dict()
+        getattr(dst, name).load_state_dict(tuple(cast(x) for x in sd) if isinstance(sd, tuple)
+                                           else cast(sd))
     for od, os_ in ((dst.actor_optimizer, src.actor_optimizer),
                     (dst.critic_optimizer, src.critic_optimizer)):
         od.load_state_dict(copy.deepcopy(os_.state_dict()))
