@@ -60,7 +60,6 @@ def one(rng, k):
     tail_max = int(knobs3.choice([0, 98304, 1048576]))
     os.environ['TTL_TAIL_FUSED'] = '1' if tail_max else '0'
     os.environ['TTL_TAIL_FUSED_MAX_ROWS'] = str(max(tail_max, 1))
-    TrackingEnvironment.TAIL_FUSED_MAX_ROWS = tail_max
     TrackingEnvironment.ORDER_MIN_FILL = float(knobs3.choice([0.0, 0.5, 0.8, 0.99]))
     if os.environ.get('TTL_STRESS_VERBOSE'):
         print('config', k, dict(shape=shape, C=C, K=K, theta=theta, thr=thr, step=step_mm,

@@ -662,8 +662,6 @@ def test_stopped_rows_list(N, tail_fused, monkeypatch):
     from tracktolearn_amd import _lib
     from tracktolearn_amd.environments import TrackingEnvironment
     monkeypatch.setenv('TTL_TAIL_FUSED', tail_fused)
-    if tail_fused == '0':       # the Python mirror of the knob is read at import
-        monkeypatch.setattr(TrackingEnvironment, 'TAIL_FUSED_MAX_ROWS', 0)
     monkeypatch.setattr(TrackingEnvironment, 'SPATIAL_ORDER_MIN', 1)
     monkeypatch.setattr(TrackingEnvironment, 'SPATIAL_ORDER_REFRESH', 3)
     D = 20
@@ -816,7 +814,6 @@ def test_uncompacted_processing_order_changes_nothing(tail, refresh, local_sort,
     monkeypatch.setenv('TTL_LOCAL_SORT', local_sort)
     from oracle import env_oracle as orc
     from tracktolearn_amd.environments import TrackingEnvironment
-    monkeypatch.setattr(TrackingEnvironment, 'TAIL_FUSED_MAX_ROWS', 1048576 if tail == '1' else 0)
     saved = (TrackingEnvironment.SPATIAL_ORDER_MIN, TrackingEnvironment.SPATIAL_ORDER_REFRESH)
     TrackingEnvironment.SPATIAL_ORDER_MIN, TrackingEnvironment.SPATIAL_ORDER_REFRESH = 1, refresh
     try:

@@ -12,6 +12,8 @@ streamline id), which are asserted to be the GPU's bit for bit on every
 stepped step.  Every step: dones, membership of continue_idx, flags, and the
 sampled state rows within 1e-5; at the end: lengths, flags and every point of
 the sampled streamlines bit-identical."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -98,7 +100,13 @@ def test_config2_whole_episode_follows_the_oracle_to_exhaustion():
     import bench
     N, K, seed = 262144, 4, 1
     env, subject = _make(96, N, K, noisy=False, reward=False, max_length=200.0)
-    assert env.SPATIAL_ORDER_REFRESH == 16 and env.TAIL_FUSED_MAX_ROWS >= N   # bench's defaults
+    assert env.SPATIAL_ORDER_REFRESH == 16                                    # bench's defaults
+    # ... and with them the fused tail at this size: the library re-buckets an
+    # order of N slots inside its own steps (every 2nd), which only k_tail does
+    env.reset(0, N)
+    slots, period = C.c_int32(-1), C.c_int32(-1)
+    assert env._lib.ttl_env_order_slots(env._handle, C.byref(slots), C.byref(period)) == 0
+    assert (slots.value, period.value) == (N, 2)
     rng = np.random.RandomState(41)
     sample = np.sort(rng.choice(N, SAMPLE, replace=False))
     ref = _sampled_oracle(env, subject, sample, noisy=False, K=K)
@@ -149,7 +157,6 @@ def test_one_launch_tail_at_its_cap_of_4096_row_blocks(monkeypatch):
     map, a sample of state rows, flags, lengths and points all equal -- and a
     sample of 4 096 streamlines against the oracle."""
     import bench
-    from tracktolearn_amd.environments import TrackingEnvironment
     N, K, seed, n_steps = 1 << 20, 4, 5, 5
     rng = np.random.RandomState(47)
     sample = np.sort(rng.choice(N, SAMPLE, replace=False))
@@ -158,7 +165,6 @@ def test_one_launch_tail_at_its_cap_of_4096_row_blocks(monkeypatch):
     for tail in ('1', '0'):
         monkeypatch.setenv('TTL_TAIL_FUSED', tail)
         monkeypatch.setenv('TTL_TAIL_FUSED_MAX_ROWS', str(N))
-        monkeypatch.setattr(TrackingEnvironment, 'TAIL_FUSED_MAX_ROWS', N if tail == '1' else 0)
         env, subject = _make(96, N, K, noisy=False, reward=False, max_length=200.0)
         state = env.reset(0, N)
         log = []

@@ -271,6 +271,70 @@ def test_instep_through_the_c_abi_with_the_callers_buffers(monkeypatch):
             assert u.tobytes() == v.tobytes(), s
 
 
+def _expected_refreshes(rows, every, k_tail):
+    """Steps before which the host refreshes the order, from rows[k] = the active
+    rows of step k alone.  The rule: periodically, when (length - 1) % every == 0
+    (length = k + 1 points, never before step 0), or early, when fewer than 0.8 of
+    the rows of the last refresh are left and the step tail keeps holes -- k_tail
+    was asked for (TTL_TAIL_FUSED=1) and the step before ran over the order: the
+    library drops the order at the first step of at most TTL_FUSE_MAX_ROWS = 256
+    rows, which the one-launch tail takes, and a periodic refresh re-installs it
+    for one such step at a time."""
+    out, at_refresh, in_use = [], rows[0], True
+    for k, n in enumerate(rows):
+        periodic = bool(every) and k > 0 and k % every == 0
+        early = bool(every) and k > 0 and k_tail and in_use and n < 0.8 * at_refresh
+        if periodic or early:
+            out.append(k)
+            at_refresh, in_use = n, True
+        if n <= 256:
+            in_use = False
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('tail,every', [('1', 4), ('1', 0), ('0', 4)])
+def test_host_refresh_schedule_follows_the_library(tail, every, monkeypatch):
+    """With in-step off the host class decides when the order is rebuilt, from what
+    the library reports (ttl_env_order_slots).  No output depends on it, so the
+    calls themselves are recorded: k_tail (holes) refreshes periodically and early,
+    never with TTL_ORDER_REFRESH=0, and the two-kernel tail, which compacts the
+    order in every step, only periodically.
+
+    Run once on the commit before the host class asked the library (it kept its own
+    copy of the order's length and of the knobs that choose the tail): the second
+    and third case gave the same schedules; the first gave [4, 7, 8, 11, 12] as
+    here while the order was in use and then seven more early refreshes (before
+    steps 14, 19, 23, 25, 27, 29, 30, at 172 rows and fewer) that its stale copy
+    asked for after the library had dropped the order -- each rebuilt an order
+    that the same step dropped again."""
+    from tracktolearn_amd.environments import TrackingEnvironment
+    monkeypatch.setenv('TTL_TAIL_FUSED', tail)
+    monkeypatch.setattr(TrackingEnvironment, 'SPATIAL_ORDER_REFRESH', every)
+    monkeypatch.setattr(TrackingEnvironment, 'ORDER_MIN_FILL', 0.8)
+    env = _env(monkeypatch, 0, seeds=_seeds())
+    refresh, called, rows = env._lib.ttl_env_refresh_processing_order, [], []
+
+    def recorded(handle, stream):
+        called.append(len(rows) - 1)
+        return refresh(handle, stream)
+    monkeypatch.setattr(env._lib, 'ttl_env_refresh_processing_order', recorded)
+    state = env.reset(0, N)
+    while env._n_active:
+        rows.append(env._n_active)
+        env.step_device(env.scripted_actions(state, len(rows) - 1, 9, 0.2))
+        state, _ = env.harvest()
+    want = _expected_refreshes(rows, every, tail == '1')
+    print('rows per step', rows, 'refreshed before', called, 'expected', want)
+    assert called == want
+    periodic = [k for k in range(1, len(rows)) if every and k % every == 0]
+    if tail == '1' and every:
+        # (the CPU oracle: 557 -> 414 rows over steps 4..7, 376 -> 272 over 8..11)
+        assert set(periodic) < set(called) and any(k % every for k in called)
+    else:
+        assert called == periodic and (every or not called)
+
+
 def test_a_brick_grid_over_the_bin_cap_never_takes_the_instep_path(monkeypatch):
     """ttl_env_create does no device work: a descriptor with made-up (aligned,
     never dereferenced) addresses is enough to ask the handle which path it

@@ -271,10 +271,12 @@ static_assert(sizeof(NoiseParams) <= (64 - TTL_FR_NOISE) * sizeof(int),
 template <bool KEYED>
 struct NoiseSource {
     typedef const double *__restrict__ type;
+    static const double *of(const double *rows, const NoiseParams &) { return rows; }
 };
 template <>
 struct NoiseSource<true> {
     typedef NoiseParams type;
+    static const NoiseParams &of(const double *, const NoiseParams &set) { return set; }
 };
 
 // tracking_env.py:165-178: at the first step all criteria run on the 2-point
@@ -362,6 +364,81 @@ __device__ __forceinline__ void block_ranks(int *__restrict__ rank_out,
 __device__ __forceinline__ void block_survivor_ranks(const EnvParams &P, int i,
                                                      bool active, bool keep) {
     block_ranks(P.rank, P.block_counts, i, active, keep);
+}
+
+// low 6 bits of v spread to every third bit (Morton interleave helper)
+__device__ __forceinline__ unsigned spread3(unsigned v) {
+    v &= 63u;
+    v = (v | (v << 8)) & 0x300Fu;
+    v = (v | (v << 4)) & 0x30C3u;
+    v = (v | (v << 2)) & 0x9249u;
+    return v;
+}
+
+// ---------------------------------------------------------------------------
+// The per-block voxel sort of the processing order (k_proc_scatter, k_tail).
+// The 256 slots of a block are put in Morton order of the voxel their
+// streamline sits in now.  The global order (8^3 bricks, rebuilt every few
+// steps) decays slowly; the order INSIDE a brick decays within two steps (a
+// step is 0.75 voxel) and decides how many of a wave's five streamlines share
+// voxel records.  A block's slots stay the block's (the kept-slot count per
+// block is permutation invariant), so this is a 256-key rank sort in LDS, no
+// extra launch: each wave sorts its 64 keys in registers, the four sorted runs
+// go to LDS, and every key counts the smaller keys of the other three runs by
+// binary search -- 21 exchanges + 21 LDS reads per thread instead of 256
+// comparisons.  Threads without a slot (idle, or a hole of the order) share
+// the key 0xFFFFFFFF and all rank behind the live ones.
+// ---------------------------------------------------------------------------
+// voxel a coordinate sits in, clamped to 0..1023
+__device__ __forceinline__ unsigned sort_voxel(float p) {
+    return (unsigned)(int)fminf(fmaxf(floorf(p), 0.0f), 1023.0f);
+}
+
+// Sort key of the slot whose streamline's newest point is hd: unique inside the
+// block (the thread id sits in the low byte)
+__device__ __forceinline__ unsigned sort_key(const float4 &hd, unsigned tid) {
+    const unsigned vx = sort_voxel(hd.x), vy = sort_voxel(hd.y), vz = sort_voxel(hd.z);
+    // bits above the low 6 per axis first (coarse), then the Morton code
+    const unsigned coarse = (((vx >> 6) & 3u) << 4) | (((vy >> 6) & 3u) << 2) | ((vz >> 6) & 3u);
+    const unsigned m = (spread3(vx) << 2) | (spread3(vy) << 1) | spread3(vz);
+    // (the all-ones code -- voxel 255 / 511 / .. on every axis -- gives way by
+    // one, so that no live key equals the idle threads' 0xFFFFFFFF)
+    return (min(coarse << 18 | m, 0xFFFFFEu) << 8) | tid;
+}
+
+// the wave's 64 keys, ascending over the lanes: bitonic network over cross-lane
+// exchanges, 21 stages
+__device__ __forceinline__ unsigned wave_sort(unsigned sk, int lane) {
+#pragma unroll
+    for (int size = 2; size <= 64; size <<= 1) {
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const unsigned other = (unsigned)__shfl_xor((int)sk, stride);
+            const bool up = (lane & size) == 0;          // this block of `size` lanes ascends
+            const bool low = (lane & stride) == 0;       // the lower lane of the pair
+            const unsigned mn = min(sk, other), mx = max(sk, other);
+            sk = (up == low) ? mn : mx;
+        }
+    }
+    return sk;
+}
+
+// position of the sorted key `sk` (lane `lane` of run `wave`) among the block's
+// keys: its lane + the smaller keys of the other waves' runs in s_key[BLOCK]
+__device__ __forceinline__ int sorted_rank(const unsigned *s_key, unsigned sk, int lane, int wave) {
+    int srank = lane;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        if (w == wave) continue;
+        const unsigned *run = s_key + 64 * w;
+        int c = 0;
+#pragma unroll
+        for (int step = 32; step > 0; step >>= 1)
+            if (run[c + step - 1] < sk) c += step;
+        if (c == 63 && run[63] < sk) c = 64;
+        srank += c;
+    }
+    return srank;
 }
 
 // ---------------------------------------------------------------------------
@@ -707,35 +784,13 @@ __global__ __launch_bounds__(BLOCK) void k_prefix(EnvParams P,
         before += red[0][w];
         total += red[1][w];
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        P.counts[0] = total;
-        P.counts[1] = n_active - total;
-        if (host_word) {
-            // straight into the caller's pinned buffer, sequence number last:
-            // the host polls it (ttl_env_wait_counts) and can queue the next
-            // step while the state gather of this one is still running
-            __hip_atomic_store(host_word + 0, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 1, n_active - total, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        step_publish_counts(P, total, n_active, host_word, seq);
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_active) return;
     const int pos = before + P.rank[i];
     const bool stop = P.stop[i] != 0;
-    const int g = idx[i];
-    if (!stop) idx_next[pos] = g;
-    // ORDER_PARTITION has no separate harvest kernel: record the final length
-    // of the streamlines that just stopped here (tracking_env.py:236)
-    if (stop && order == TTL_ORDER_PARTITION) P.lengths[g] = n_pts;
-    P.surv_pos[i] = stop ? -1 : pos;
-    // the rows that stopped, compacted in row order (ttl_env_stopped: the
-    // oracle reward scores exactly these, oracle_reward.py:78-90)
-    if (stop) *reinterpret_cast<int2 *>(P.stop_list + 2 * (size_t)(i - pos)) = int2{i, g};
-    int dest = i;
-    if (order == TTL_ORDER_PARTITION) dest = stop ? total + (i - pos) : pos;
-    P.row_dest[i] = dest;
+    const int dest = step_map_row(P, i, idx[i], stop, pos, total, order, n_pts, idx_next);
     *reinterpret_cast<int2 *>(P.pos_dest + 2 * (size_t)i) = int2{stop ? -1 : pos, dest};
 }
 
@@ -748,15 +803,6 @@ __global__ __launch_bounds__(BLOCK) void k_prefix(EnvParams P,
 // streamline separately.  Each step proc is compacted (stable, in proc order)
 // and renumbered with the survivors' new row ids.
 // ---------------------------------------------------------------------------
-// low 6 bits of v spread to every third bit (Morton interleave helper)
-__device__ __forceinline__ unsigned spread3(unsigned v) {
-    v &= 63u;
-    v = (v | (v << 8)) & 0x300Fu;
-    v = (v | (v << 4)) & 0x30C3u;
-    v = (v | (v << 2)) & 0x9249u;
-    return v;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_proc_scatter(EnvParams P,
                                                         const int *__restrict__ idx,
                                                         const int *__restrict__ proc,
@@ -797,64 +843,16 @@ __global__ __launch_bounds__(BLOCK) void k_proc_scatter(EnvParams P,
         P.slot_dest[j] = pd.y;
         return;
     }
-    // Local re-sort: the 256 slots of this block are put in Morton order of
-    // the voxel their streamline sits in now.  The global order (8^3 bricks,
-    // rebuilt every few steps) decays slowly; the order INSIDE a brick decays
-    // within two steps (a step is 0.75 voxel) and decides how many of a wave's
-    // five streamlines share voxel records.  A block's slots stay the block's
-    // (the kept-slot count per block is permutation invariant), so this is a
-    // 256-key rank sort in LDS, no extra launch.
-    unsigned key = 0xFFFFFFFFu;
-    if (active) {
-        const unsigned vx = (unsigned)(int)fminf(fmaxf(floorf(hd.x), 0.0f), 1023.0f);
-        const unsigned vy = (unsigned)(int)fminf(fmaxf(floorf(hd.y), 0.0f), 1023.0f);
-        const unsigned vz = (unsigned)(int)fminf(fmaxf(floorf(hd.z), 0.0f), 1023.0f);
-        // bits above the low 6 per axis first (coarse), then the Morton code
-        const unsigned coarse = (((vx >> 6) & 3u) << 4) | (((vy >> 6) & 3u) << 2) | ((vz >> 6) & 3u);
-        const unsigned m = (spread3(vx) << 2) | (spread3(vy) << 1) | spread3(vz);
-        // (the all-ones code -- voxel 255 / 511 / .. on every axis -- gives way by
-        // one, so that no live key equals the idle threads' 0xFFFFFFFF)
-        key = (min(coarse << 18 | m, 0xFFFFFEu) << 8) | threadIdx.x;   // unique inside the block
-    }
-    // Rank of this slot's key among the block's 256 keys (unique: the thread id
-    // sits in the low byte; idle threads of a partly filled last block share
-    // 0xFFFFFFFF and all rank behind the live ones).  Each wave sorts its 64 keys
-    // in registers (bitonic network over cross-lane exchanges, 21 stages), the
-    // four sorted runs go to LDS, and every key counts the smaller keys of the
-    // other three runs by binary search: 21 exchanges + 21 LDS reads per thread
-    // instead of 256 comparisons.
+    // local re-sort (see sort_key): rank of this slot's key among the block's 256
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned sk = key;
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const unsigned other = (unsigned)__shfl_xor((int)sk, stride);
-            const bool up = (lane & size) == 0;          // this block of `size` lanes ascends
-            const bool low = (lane & stride) == 0;       // the lower lane of the pair
-            const unsigned mn = min(sk, other), mx = max(sk, other);
-            sk = (up == low) ? mn : mx;
-        }
-    }
+    const unsigned sk = wave_sort(active ? sort_key(hd, threadIdx.x) : 0xFFFFFFFFu, lane);
     s_key[threadIdx.x] = sk;                 // run `wave`, ascending over the lanes
     // sorted positions nobody ranks into (a partly filled last block: its idle
     // threads all rank to the same position) must read as "no survivor": LDS
     // keeps whatever an earlier workgroup left there
     s_pos[threadIdx.x] = -1;
     __syncthreads();
-    // position of the sorted key `sk`: its lane + the smaller keys of the other runs
-    int srank = lane;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w == wave) continue;
-        const unsigned *run = s_key + 64 * w;
-        int c = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1)
-            if (run[c + step - 1] < sk) c += step;
-        if (c == 63 && run[63] < sk) c = 64;
-        srank += c;
-    }
+    const int srank = sorted_rank(s_key, sk, lane, wave);
     // hand the position to the thread the key came from
     if (sk != 0xFFFFFFFFu) s_rank[sk & 255u] = srank;
     __syncthreads();
@@ -952,29 +950,12 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
             run += P.block_counts[lo + k];
         }
     __syncthreads();
-    if (blockIdx.x == 0 && tid == 0) {
-        P.counts[0] = total;
-        P.counts[1] = n_active - total;
-        if (host_word) {       // see k_prefix
-            __hip_atomic_store(host_word + 0, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 1, n_active - total, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if (blockIdx.x == 0 && tid == 0) step_publish_counts(P, total, n_active, host_word, seq);
     // ---- rows: continue_idx of the next step, lengths, the row maps ----
     const int i = blockIdx.x * BLOCK + tid;
     if (i < n_active) {
         const int pos = s_scan[blockIdx.x] + P.rank[i];
-        const bool stop = P.stop[i] != 0;
-        const int g = idx[i];
-        if (!stop) idx_next[pos] = g;
-        if (stop && order == TTL_ORDER_PARTITION) P.lengths[g] = n_pts;
-        P.surv_pos[i] = stop ? -1 : pos;
-        if (stop) *reinterpret_cast<int2 *>(P.stop_list + 2 * (size_t)(i - pos)) = int2{i, g};
-        int dest = i;
-        if (order == TTL_ORDER_PARTITION) dest = stop ? total + (i - pos) : pos;
-        P.row_dest[i] = dest;
+        step_map_row(P, i, idx[i], P.stop[i] != 0, pos, total, order, n_pts, idx_next);
     }
     // ---- slots: this step's records for the gather, next step's order ----
     const int j = i;
@@ -985,8 +966,7 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
     if (live) {
         const bool stop = P.stop[row] != 0;
         const int pos = s_scan[row / BLOCK] + P.rank[row];
-        dest = row;
-        if (order == TTL_ORDER_PARTITION) dest = stop ? total + (row - pos) : pos;
+        dest = step_row_dest(order, row, stop, pos, total);
         next = stop ? -1 : pos;
         hd = *reinterpret_cast<const float4 *>(P.head + 4 * (size_t)row);
     }
@@ -998,50 +978,24 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
         }
         return;
     }
-    // per-block re-sort by the voxel the streamline sits in now (see
-    // k_proc_scatter); holes carry the largest key and end up behind the live slots
+    // per-block re-sort by the voxel the streamline sits in now (see sort_key);
+    // holes carry the largest key and end up behind the live slots
     unsigned key = 0xFFFFFFFFu;
     int bin = -1;
     if (live) {
-        const unsigned vx = (unsigned)(int)fminf(fmaxf(floorf(hd.x), 0.0f), 1023.0f);
-        const unsigned vy = (unsigned)(int)fminf(fmaxf(floorf(hd.y), 0.0f), 1023.0f);
-        const unsigned vz = (unsigned)(int)fminf(fmaxf(floorf(hd.z), 0.0f), 1023.0f);
-        const unsigned coarse = (((vx >> 6) & 3u) << 4) | (((vy >> 6) & 3u) << 2) | ((vz >> 6) & 3u);
-        const unsigned m = (spread3(vx) << 2) | (spread3(vy) << 1) | spread3(vz);
-        key = (min(coarse << 18 | m, 0xFFFFFEu) << 8) | (unsigned)tid;
+        key = sort_key(hd, (unsigned)tid);
         // brick of that voxel in the refresh's dense raster, clamped into it
         if (REBUCKET && next >= 0)
-            bin = (min((int)(vx >> 3), nbx - 1) * nby + min((int)(vy >> 3), nby - 1)) * nbz +
-                  min((int)(vz >> 3), nbz - 1);
+            bin = (min((int)(sort_voxel(hd.x) >> 3), nbx - 1) * nby +
+                   min((int)(sort_voxel(hd.y) >> 3), nby - 1)) * nbz +
+                  min((int)(sort_voxel(hd.z) >> 3), nbz - 1);
     }
-    unsigned sk = key;
-#pragma unroll
-    for (int size = 2; size <= 64; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const unsigned other = (unsigned)__shfl_xor((int)sk, stride);
-            const bool up = (lane & size) == 0;
-            const bool low = (lane & stride) == 0;
-            const unsigned mn = min(sk, other), mx = max(sk, other);
-            sk = (up == low) ? mn : mx;
-        }
-    }
+    const unsigned sk = wave_sort(key, lane);
     s_key[tid] = sk;
     s_pos[tid] = -1;
     if (REBUCKET) s_bin[tid] = -1;
     const int n_live = __syncthreads_count(live);
-    int srank = lane;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w == wave) continue;
-        const unsigned *srun = s_key + 64 * w;
-        int c = 0;
-#pragma unroll
-        for (int step = 32; step > 0; step >>= 1)
-            if (srun[c + step - 1] < sk) c += step;
-        if (c == 63 && srun[63] < sk) c = 64;
-        srank += c;
-    }
+    const int srank = sorted_rank(s_key, sk, lane, wave);
     if (sk != 0xFFFFFFFFu) s_rank[sk & 255u] = srank;
     __syncthreads();
     const size_t base = (size_t)blockIdx.x * BLOCK;
@@ -1380,6 +1334,18 @@ static void prof_mark(ttl_env *e, int which, int stop, hipStream_t s) {
         return;
     (void)hipEventRecord(e->prof_ev[which][2 * e->prof_n[which] + stop], s);
     if (stop) e->prof_n[which]++;
+}
+
+// The k_advance / k_advance_fr instantiation of a handle: calls f(mode, keyed)
+// with both as std::integral_constant.  Keyed noise (ttl_env_set_noise) exists
+// for TTL_MODE_F64DIR only.
+template <class F>
+static void for_advance_variant(const ttl_env *env, F &&f) {
+    using std::integral_constant;
+    if (env->keyed) f(integral_constant<int, TTL_MODE_F64DIR>{}, std::true_type{});
+    else if (env->d.mode == TTL_MODE_F32) f(integral_constant<int, TTL_MODE_F32>{}, std::false_type{});
+    else if (env->d.mode == TTL_MODE_F64DIR) f(integral_constant<int, TTL_MODE_F64DIR>{}, std::false_type{});
+    else f(integral_constant<int, TTL_MODE_F32NORM>{}, std::false_type{});
 }
 
 extern "C" {
@@ -1896,16 +1862,12 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
     const int L = env->length;
     const int nb = (n_active + BLOCK - 1) / BLOCK;
     prof_mark(env, 0, 0, s);
-#define TTL_LAUNCH_ADVANCE(M)                                                  \
-    hipLaunchKernelGGL((k_advance<M>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx, \
-                       actions, noise, n_active, L, reward_out, done_out)
-    if (env->keyed)      // TTL_MODE_F64DIR (ttl_env_set_noise)
-        hipLaunchKernelGGL((k_advance<TTL_MODE_F64DIR, true>), dim3(nb), dim3(BLOCK), 0, s, env->P,
-                           idx, actions, env->noise, n_active, L, reward_out, done_out);
-    else if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE(TTL_MODE_F32);
-    else if (d.mode == TTL_MODE_F64DIR) TTL_LAUNCH_ADVANCE(TTL_MODE_F64DIR);
-    else TTL_LAUNCH_ADVANCE(TTL_MODE_F32NORM);
-#undef TTL_LAUNCH_ADVANCE
+    for_advance_variant(env, [&](auto mode, auto keyed) {
+        constexpr int M = decltype(mode)::value;
+        constexpr bool K = decltype(keyed)::value;
+        hipLaunchKernelGGL((k_advance<M, K>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx, actions,
+                           NoiseSource<K>::of(noise, env->noise), n_active, L, reward_out, done_out);
+    });
     prof_mark(env, 0, 1, s);
     HIP_TRY(hipGetLastError());
     env->length = L + 1;
@@ -1938,6 +1900,56 @@ static int ttl_order_instep_scatter(ttl_env *env, hipStream_t s) {
     return TTL_OK;
 }
 
+// what a step is asked to write: the row order and the pitch of the state rows
+// (env may be null: ttl_env_step checks before ttl_env_step_begin looks at it)
+static int ttl_check_step_rows(const ttl_env *env, int32_t order, int64_t state_pitch) {
+    if (order != TTL_ORDER_ACTIVE && order != TTL_ORDER_PARTITION)
+        return fail(TTL_ERR_INVALID, "ttl_env_step: bad order %d", order);
+    if (env && state_pitch < 7LL * env->d.n_coef + 3LL * env->d.n_dirs)
+        return fail(TTL_ERR_INVALID, "ttl_env_step: state_pitch too small");
+    return TTL_OK;
+}
+
+// How the survivor count of a step reaches host_counts.  It goes straight into
+// the caller's pinned buffer ({n_continue, n_stopped, sequence number}, written
+// by the kernel that computes it) when that buffer is device-visible: no side
+// stream, no copy kernel waiting for free CUs behind the gather, no API calls
+// between the step's launches; the host polls the sequence word.  Returns the
+// buffer's device address and the step's sequence number for the tail kernel,
+// or null: then ttl_counts_after_tail() ships the count.
+static int *ttl_counts_to_host(ttl_env *env, int32_t *host_counts, hipStream_t s, int *seq) {
+    *seq = 0;
+    if (!host_counts || !env->poll_counts) return nullptr;
+    if (env->host_probe != host_counts) {
+        void *dev = nullptr;
+        env->host_probe = host_counts;
+        env->host_dev = nullptr;
+        if (hipHostGetDevicePointer(&dev, host_counts, 0) == hipSuccess)
+            env->host_dev = static_cast<int *>(dev);
+        else
+            (void)hipGetLastError();      // not pinned: the copy path
+    }
+    // sequence numbers carry bit 30: word [2] of the same pinned buffer is
+    // the "steps done" counter of a free-running episode (small values), and
+    // a leftover count must never read as this step's sequence number
+    static std::atomic<unsigned> g_seq{1};
+    *seq = (int)((g_seq.fetch_add(1, std::memory_order_relaxed) & 0x3fffffffu) | 0x40000000u);
+    if (env->host_dev) {
+        env->counts_pending = 2;
+        env->host_counts = host_counts;
+        env->poll_seq = *seq;
+        env->poll_stream = s;
+    }
+    return env->host_dev;
+}
+
+// the fallback (buffer not device-visible): ship the count on a side stream as
+// soon as the kernel that computes it has run, in front of the gather
+static hipError_t ttl_counts_after_tail(ttl_env *env, int32_t *host_counts, const int *host_word,
+                                        hipStream_t s) {
+    return host_counts && !host_word ? ttl_copy_counts(env, host_counts, s) : hipSuccess;
+}
+
 int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
                      float *state_out, int64_t state_pitch, int32_t *host_counts,
                      void *hip_stream) {
@@ -1945,12 +1957,8 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
         return fail(TTL_ERR_INVALID, "ttl_env_step: null argument");
     if (env->stepped != 2)
         return fail(TTL_ERR_STATE, "ttl_env_step_end: call ttl_env_step_begin first");
-    if (order != TTL_ORDER_ACTIVE && order != TTL_ORDER_PARTITION)
-        return fail(TTL_ERR_INVALID, "ttl_env_step: bad order %d", order);
+    if (const int rc = ttl_check_step_rows(env, order, state_pitch)) return rc;
     const ttl_env_desc &d = env->d;
-    const int64_t width = 7LL * d.n_coef + 3LL * d.n_dirs;
-    if (state_pitch < width)
-        return fail(TTL_ERR_INVALID, "ttl_env_step: state_pitch too small");
     hipStream_t s = (hipStream_t)hip_stream;
     const int *idx = env->cur ? d.idx_b : d.idx_a;
     int *idx_next = env->cur ? d.idx_a : d.idx_b;
@@ -1971,36 +1979,8 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     const int *proc = env->use_proc ? env->proc[env->proc_cur] : nullptr;
     env->stepped = 1;
     env->last_order = order;
-    // The survivor count goes straight into the caller's pinned buffer
-    // ({n_continue, n_stopped, sequence number}, written by the kernel that
-    // computes it) when that buffer is device-visible: no side stream, no copy
-    // kernel waiting for free CUs behind the gather, no API calls between the
-    // step's launches; the host polls the sequence word.
-    int *host_word = nullptr;
     int seq = 0;
-    if (host_counts && env->poll_counts) {
-        if (env->host_probe != host_counts) {
-            void *dev = nullptr;
-            env->host_probe = host_counts;
-            env->host_dev = nullptr;
-            if (hipHostGetDevicePointer(&dev, host_counts, 0) == hipSuccess)
-                env->host_dev = static_cast<int *>(dev);
-            else
-                (void)hipGetLastError();      // not pinned: copy path below
-        }
-        host_word = env->host_dev;
-        // sequence numbers carry bit 30: word [2] of the same pinned buffer is
-        // the "steps done" counter of a free-running episode (small values), and
-        // a leftover count must never read as this step's sequence number
-        static std::atomic<unsigned> g_seq{1};
-        seq = (int)((g_seq.fetch_add(1, std::memory_order_relaxed) & 0x3fffffffu) | 0x40000000u);
-    }
-    if (host_word) {
-        env->counts_pending = 2;
-        env->host_counts = host_counts;
-        env->poll_seq = seq;
-        env->poll_stream = s;
-    }
+    int *host_word = ttl_counts_to_host(env, host_counts, s, &seq);
     if (!proc && env->fuse_small && env->state_kernel != 0 &&
         ttl_detail_can_fuse_tail(env->P, n_active)) {
         // small batch: prefix + compaction + gather in ONE launch
@@ -2010,7 +1990,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
                                                     host_word, seq, s);
         prof_mark(env, 2, 1, s);
         if (rc != TTL_OK) return rc;
-        if (host_counts && !host_word) HIP_TRY(ttl_copy_counts(env, host_counts, s));
+        HIP_TRY(ttl_counts_after_tail(env, host_counts, host_word, s));
         return TTL_OK;
     }
     // batches with a processing order: rows and slots in one launch (k_tail)
@@ -2022,10 +2002,20 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     const bool fused_tail = proc && env->tail_fused && env->P.slot_rec &&
                             ttl_detail_state_dedupes(env->P, env->state_kernel) &&
                             (env->n_slots < 0 ? n_active : env->n_slots) <= env->tail_fused_max;
+    // the two-kernel tail reads proc[j] for j < n_active without a hole check:
+    // an order that still holds holes (left by k_tail) must never reach it.
+    // The knobs that choose the tail are fixed per handle, so this cannot
+    // happen today; a setter that flips one mid-episode fails here instead
+    // of reading stop[-1]
+    if (!fused_tail && proc && env->n_slots > n_active)
+        return fail(TTL_ERR_STATE, "ttl_env_step: the processing order holds %d holes but "
+                                   "the step tail was switched to the two-kernel form; "
+                                   "refresh the order first", env->n_slots - n_active);
+    prof_mark(env, 1, 0, s);
     if (fused_tail) {
         if (env->n_slots < 0) env->n_slots = n_active;     // the order was dense so far
+        n_gather = env->n_slots;
         const int nbs = (env->n_slots + BLOCK - 1) / BLOCK;
-        prof_mark(env, 1, 0, s);
         // a re-bucket step (TTL_ORDER_INSTEP): k_tail counts the survivors' bricks
         // on the way, k_order_scatter writes the next step's order from them
         rebucket = ttl_order_instep_on(env, env->n_slots) && (n_pts - 1) % env->instep == 0;
@@ -2040,46 +2030,29 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
                                proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
                                order, n_pts, host_word, seq, env->local_sort, nullptr, nullptr,
                                0, 0, 0);
-        prof_mark(env, 1, 1, s);
-        HIP_TRY(hipGetLastError());
-        if (host_counts && !host_word) HIP_TRY(ttl_copy_counts(env, host_counts, s));
-        n_gather = env->n_slots;
+    } else {
+        hipLaunchKernelGGL(k_prefix, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, idx_next,
+                           proc, n_active, nb, order, n_pts, host_word, seq);
+    }
+    prof_mark(env, 1, 1, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(ttl_counts_after_tail(env, host_counts, host_word, s));
+    if (fused_tail) {
         if (rebucket && !env->instep_after) {
             const int rc = ttl_order_instep_scatter(env, s);
             if (rc != TTL_OK) return rc;
         }
-    } else {
-        // the two-kernel tail reads proc[j] for j < n_active without a hole check:
-        // an order that still holds holes (left by k_tail) must never reach it.
-        // The knobs that choose the tail are fixed per handle, so this cannot
-        // happen today; a setter that flips one mid-episode fails here instead
-        // of reading stop[-1]
-        if (proc && env->n_slots > n_active)
-            return fail(TTL_ERR_STATE, "ttl_env_step: the processing order holds %d holes but "
-                                       "the step tail was switched to the two-kernel form; "
-                                       "refresh the order first", env->n_slots - n_active);
-        prof_mark(env, 1, 0, s);
-        hipLaunchKernelGGL(k_prefix, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, idx_next,
-                           proc, n_active, nb, order, n_pts, host_word, seq);
-        prof_mark(env, 1, 1, s);
+    } else if (proc) {
+        // next step's processing order: this one, compacted in its own order
+        // (ranks from k_prefix) and renumbered with the survivors' new row
+        // ids; plus this step's per-slot records for the gather
+        prof_mark(env, 3, 0, s);
+        hipLaunchKernelGGL(k_proc_scatter, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, proc,
+                           env->proc[env->proc_cur ^ 1], n_active, nb,
+                           env->local_sort && env->P.slot_rec);
+        prof_mark(env, 3, 1, s);
         HIP_TRY(hipGetLastError());
-        if (host_counts && !host_word) {
-            // fallback (buffer not device-visible): ship the count on a side stream
-            // as soon as k_prefix has run
-            HIP_TRY(ttl_copy_counts(env, host_counts, s));
-        }
-        if (proc) {
-            // next step's processing order: this one, compacted in its own order
-            // (ranks from k_prefix) and renumbered with the survivors' new row
-            // ids; plus this step's per-slot records for the gather
-            prof_mark(env, 3, 0, s);
-            hipLaunchKernelGGL(k_proc_scatter, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, proc,
-                               env->proc[env->proc_cur ^ 1], n_active, nb,
-                               env->local_sort && env->P.slot_rec);
-            prof_mark(env, 3, 1, s);
-            HIP_TRY(hipGetLastError());
-            env->n_slots = -1;         // compacted: as long as the next step's active rows
-        }
+        env->n_slots = -1;         // compacted: as long as the next step's active rows
     }
     prof_mark(env, 2, 0, s);
     log_gather_rows(n_active);
@@ -2094,16 +2067,11 @@ int ttl_env_step(ttl_env *env, const float *actions, const double *noise,
                  int32_t n_active, int32_t order, float *state_out,
                  int64_t state_pitch, double *reward_out, uint8_t *done_out,
                  int32_t *host_counts, void *hip_stream) {
+    // nothing is launched for a step whose output arguments are bad
     if (!state_out) return fail(TTL_ERR_INVALID, "ttl_env_step: null argument");
-    if (order != TTL_ORDER_ACTIVE && order != TTL_ORDER_PARTITION)
-        return fail(TTL_ERR_INVALID, "ttl_env_step: bad order %d", order);
-    if (env) {
-        const int64_t width = 7LL * env->d.n_coef + 3LL * env->d.n_dirs;
-        if (state_pitch < width)
-            return fail(TTL_ERR_INVALID, "ttl_env_step: state_pitch too small");
-    }
-    const int rc = ttl_env_step_begin(env, actions, noise, n_active, reward_out,
-                                      done_out, hip_stream);
+    int rc = ttl_check_step_rows(env, order, state_pitch);
+    if (rc != TTL_OK) return rc;
+    rc = ttl_env_step_begin(env, actions, noise, n_active, reward_out, done_out, hip_stream);
     if (rc != TTL_OK) return rc;
     return ttl_env_step_end(env, nullptr, order, state_out, state_pitch,
                             host_counts, hip_stream);
@@ -2273,16 +2241,11 @@ int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_rows, flo
     const int nb = (n_cap + BLOCK - 1) / BLOCK;
     // launches only: nothing below waits, copies or asks the runtime anything,
     // so the call may run under stream capture
-#define TTL_LAUNCH_ADVANCE_FR(M)                                                     \
-    hipLaunchKernelGGL((k_advance_fr<M>), dim3(nb), dim3(BLOCK), 0, s, env->P, d.idx_a, \
-                       d.idx_b, actions, n_cap, reward_out, done_out)
-    if (env->keyed)
-        hipLaunchKernelGGL((k_advance_fr<TTL_MODE_F64DIR, true>), dim3(nb), dim3(BLOCK), 0, s,
-                           env->P, d.idx_a, d.idx_b, actions, n_cap, reward_out, done_out);
-    else if (d.mode == TTL_MODE_F32) TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F32);
-    else if (d.mode == TTL_MODE_F64DIR) TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F64DIR);
-    else TTL_LAUNCH_ADVANCE_FR(TTL_MODE_F32NORM);
-#undef TTL_LAUNCH_ADVANCE_FR
+    for_advance_variant(env, [&](auto mode, auto keyed) {
+        hipLaunchKernelGGL((k_advance_fr<decltype(mode)::value, decltype(keyed)::value>), dim3(nb),
+                           dim3(BLOCK), 0, s, env->P, d.idx_a, d.idx_b, actions, n_cap, reward_out,
+                           done_out);
+    });
     HIP_TRY(hipGetLastError());
     return ttl_detail_launch_fused_tail_fr(env->P, d.idx_a, d.idx_b, n_cap, state_out,
                                            state_pitch, env->fr_host_word, s);

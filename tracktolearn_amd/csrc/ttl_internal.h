@@ -100,6 +100,56 @@ __device__ __forceinline__ unsigned vox_z(const EnvParams &P, int z) {
     return P.sh_brick ? (unsigned)(z >> 2) * 64u + (unsigned)(z & 3) : (unsigned)z;
 }
 
+// ---------------------------------------------------------------------------
+// What every step tail (k_prefix, k_tail, k_prefix_state[_fr]) does once the
+// scan of the per-block survivor counts has given a row its position `pos`
+// among the `total` survivors.
+// ---------------------------------------------------------------------------
+// State row of active row `row`: its own under TTL_ORDER_ACTIVE; under
+// TTL_ORDER_PARTITION the survivors first, the stopped rows behind them, both
+// in row order
+__device__ __forceinline__ int step_row_dest(int order, int row, bool stop, int pos, int total) {
+    int dest = row;
+    if (order == TTL_ORDER_PARTITION) dest = stop ? total + (row - pos) : pos;
+    return dest;
+}
+
+// The row map of active row `row` (streamline g): continue_idx of the next
+// step and the active-row -> state-row map.  Returns the state row.
+__device__ __forceinline__ int step_map_row(const EnvParams &P, int row, int g, bool stop,
+                                            int pos, int total, int order, int n_pts,
+                                            int *idx_next) {
+    const int dest = step_row_dest(order, row, stop, pos, total);
+    if (!stop) idx_next[pos] = g;
+    // ORDER_PARTITION has no separate harvest kernel: record the final length
+    // of the streamlines that just stopped here (tracking_env.py:236)
+    if (stop && order == TTL_ORDER_PARTITION) P.lengths[g] = n_pts;
+    P.surv_pos[row] = stop ? -1 : pos;
+    // the rows that stopped, compacted in row order (ttl_env_stopped: the
+    // oracle reward scores exactly these, oracle_reward.py:78-90)
+    if (stop) *reinterpret_cast<int2 *>(P.stop_list + 2 * (size_t)(row - pos)) = int2{row, g};
+    P.row_dest[row] = dest;
+    return dest;
+}
+
+// {n_continue, n_stopped} of the step, by one thread of the launch: into device
+// memory and, when the caller's pinned buffer is device-visible (host_word),
+// straight into it with the step's sequence number last -- the host polls that
+// word (await_counts: it reads the counts only after it has seen `seq`, hence
+// the release) and can queue the next step while the state gather of this one
+// is still running
+__device__ __forceinline__ void step_publish_counts(const EnvParams &P, int total, int n_active,
+                                                    int *host_word, int seq) {
+    P.counts[0] = total;
+    P.counts[1] = n_active - total;
+    if (host_word) {
+        __hip_atomic_store(host_word + 0, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_word + 1, n_active - total, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_word + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // records of the packed SH volume (padding records of the bricked order included)
 inline size_t ttl_detail_sh_records(const EnvParams &P) {
     if (!P.sh_brick) return (size_t)P.sh_dim[0] * P.sh_dim[1] * P.sh_dim[2];

@@ -3,6 +3,8 @@
 // k_state_dd (register-deduplicated 7-point stencil, the dominant kernel of a
 // step) and k_state (all 56 corner fetches; radius >= 1 voxel or volumes of
 // 4 GiB and more).  Part of libttl_hip.so.
+#include <type_traits>
+
 #include "ttl_internal.h"
 
 // The state rows are compared with the reference at 1e-5, not bit for bit (the
@@ -537,8 +539,6 @@ __device__ __forceinline__ void prefix_state_body(
     __syncthreads();
     const int total = s_before[TTL_FUSE_MAX_BLOCKS];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        P.counts[0] = total;
-        P.counts[1] = n_active - total;
         if (FR) {
             // the next step's words; a step without active rows changes nothing
             // but the step counter
@@ -548,12 +548,7 @@ __device__ __forceinline__ void prefix_state_body(
             live[2] = n_active > 0 ? cur ^ 1 : cur;
             live[3] = seq;
         }
-        if (host_word) {
-            __hip_atomic_store(host_word + 0, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 1, n_active - total, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_word + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        step_publish_counts(P, total, n_active, host_word, seq);
     }
     const int grp = lane / LPS;
     const int row = blockIdx.x * ROWS + (threadIdx.x >> 6) * GPW + grp;
@@ -563,16 +558,9 @@ __device__ __forceinline__ void prefix_state_body(
     const int g = __float_as_int(hp.w);
     const bool stop = P.stop[row] != 0;
     const int pos = s_before[row >> 8] + P.rank[row];
-    int dest = row;
-    if (order == TTL_ORDER_PARTITION) dest = stop ? total + (row - pos) : pos;
-    if (sub == 0) {
-        if (!stop) idx_next[pos] = g;
-        if (stop && order == TTL_ORDER_PARTITION) P.lengths[g] = n_pts;
-        P.surv_pos[row] = stop ? -1 : pos;
-        P.row_dest[row] = dest;
-        if (stop)       // see k_prefix: the stopped rows in row order, for ttl_env_stopped
-            *reinterpret_cast<int2 *>(P.stop_list + 2 * (size_t)(row - pos)) = int2{row, g};
-    }
+    // every lane of the group needs the state row, one of them writes the row map
+    const int dest = step_row_dest(order, row, stop, pos, total);
+    if (sub == 0) step_map_row(P, row, g, stop, pos, total, order, n_pts, idx_next);
     const float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
     state_row_dd<LPS, false, MERGE_TAIL>(P, hp.x, hp.y, hp.z, h, n_pts, sub,
                                          out + (size_t)dest * (size_t)pitch);
@@ -608,6 +596,27 @@ __global__ __launch_bounds__(BLOCK, 4) void k_prefix_state_fr(
                                              out, pitch, host_word, seq, cur);
 }
 
+// Lanes per streamline of the gather kernels: the smallest lane group that
+// holds a record of coef_pitch / 4 float4s.  Calls f with that LPS as a
+// std::integral_constant; MAX_LPS = 16 for the launches that
+// ttl_detail_can_fuse_tail() admits (records of at most 16 float4s).
+template <int MAX_LPS, class F>
+void for_lanes_per_streamline(const EnvParams &P, F &&f) {
+    const int C4 = P.coef_pitch >> 2;
+    if (C4 <= 4) f(std::integral_constant<int, 4>{});
+    else if (C4 <= 8) f(std::integral_constant<int, 8>{});
+    else if (C4 <= 12) f(std::integral_constant<int, 12>{});
+    else if (MAX_LPS == 16 || C4 <= 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, MAX_LPS>{});
+}
+
+// one lane group per row
+template <int LPS>
+dim3 gather_grid(int n_rows) {
+    constexpr int rows_per_block = (BLOCK / 64) * (64 / LPS);
+    return dim3((n_rows + rows_per_block - 1) / rows_per_block);
+}
+
 }  // namespace
 
 // The fused small-batch tail (k_prefix_state) applies when the deduplicated
@@ -623,21 +632,13 @@ bool ttl_detail_can_fuse_tail(const EnvParams &P, int n_active) {
 int ttl_detail_launch_fused_tail(const EnvParams &P, const int *idx, int *idx_next,
                                  int n_active, int order, int n_pts, float *out,
                                  int64_t pitch, int *host_word, int seq, hipStream_t s) {
-    const int C4 = P.coef_pitch >> 2;
     const int n_blocks = (n_active + BLOCK - 1) / BLOCK;
-#define TTL_LAUNCH_FUSED(LPS)                                                        \
-    do {                                                                             \
-        const int rows_per_block = (BLOCK / 64) * (64 / LPS);                        \
-        const dim3 grid((n_active + rows_per_block - 1) / rows_per_block);           \
-        hipLaunchKernelGGL((k_prefix_state<LPS, true>), grid, dim3(BLOCK), 0, s, P, idx, \
-                           idx_next, n_active, n_blocks, order, n_pts, out,          \
-                           (long long)pitch, host_word, seq);                        \
-    } while (0)
-    if (C4 <= 4) TTL_LAUNCH_FUSED(4);
-    else if (C4 <= 8) TTL_LAUNCH_FUSED(8);
-    else if (C4 <= 12) TTL_LAUNCH_FUSED(12);
-    else TTL_LAUNCH_FUSED(16);
-#undef TTL_LAUNCH_FUSED
+    for_lanes_per_streamline<16>(P, [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        hipLaunchKernelGGL((k_prefix_state<LPS, true>), gather_grid<LPS>(n_active), dim3(BLOCK), 0,
+                           s, P, idx, idx_next, n_active, n_blocks, order, n_pts, out,
+                           (long long)pitch, host_word, seq);
+    });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
@@ -645,20 +646,12 @@ int ttl_detail_launch_fused_tail(const EnvParams &P, const int *idx, int *idx_ne
 int ttl_detail_launch_fused_tail_fr(const EnvParams &P, int *idx_a, int *idx_b, int n_cap,
                                     float *out, int64_t pitch, int *host_word,
                                     hipStream_t s) {
-    const int C4 = P.coef_pitch >> 2;
     const int n_blocks = (n_cap + BLOCK - 1) / BLOCK;
-#define TTL_LAUNCH_FUSED_FR(LPS)                                                     \
-    do {                                                                             \
-        const int rows_per_block = (BLOCK / 64) * (64 / LPS);                        \
-        const dim3 grid((n_cap + rows_per_block - 1) / rows_per_block);              \
-        hipLaunchKernelGGL((k_prefix_state_fr<LPS, true>), grid, dim3(BLOCK), 0, s, P, idx_a, \
-                           idx_b, n_blocks, out, (long long)pitch, host_word);       \
-    } while (0)
-    if (C4 <= 4) TTL_LAUNCH_FUSED_FR(4);
-    else if (C4 <= 8) TTL_LAUNCH_FUSED_FR(8);
-    else if (C4 <= 12) TTL_LAUNCH_FUSED_FR(12);
-    else TTL_LAUNCH_FUSED_FR(16);
-#undef TTL_LAUNCH_FUSED_FR
+    for_lanes_per_streamline<16>(P, [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        hipLaunchKernelGGL((k_prefix_state_fr<LPS, true>), gather_grid<LPS>(n_cap), dim3(BLOCK), 0,
+                           s, P, idx_a, idx_b, n_blocks, out, (long long)pitch, host_word);
+    });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
@@ -674,38 +667,28 @@ bool ttl_detail_state_dedupes(const EnvParams &P, int state_kernel) {
 int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx,
                             const int *row_dest, const int *proc, int n_rows, int L,
                             float *out, int64_t pitch, hipStream_t s) {
-    const int C4 = P.coef_pitch >> 2;
     const bool dedupe = ttl_detail_state_dedupes(P, state_kernel);
-#define TTL_LAUNCH_STATE(LPS)                                                 \
-    do {                                                                      \
-        const int rows_per_block = (BLOCK / 64) * (64 / LPS);                 \
-        const int n_vb = (n_rows + rows_per_block - 1) / rows_per_block;      \
-        /* TTL_GATHER_PERSIST_ROWS (experiment, off by default): batches of at */ \
-        /* most that many rows that need more than one resident round (4       */ \
-        /* workgroups per CU x 256 CUs) run as ONE round of workgroups that    */ \
-        /* walk the blocks with a stride                                       */ \
-        const int resident = 1024;                                            \
-        const bool persist = dedupe && n_rows <= P.persist_rows && n_vb > resident; \
-        const dim3 grid(persist ? resident : n_vb);                           \
-        if (!dedupe)                                                          \
-            hipLaunchKernelGGL((k_state<LPS>), grid, dim3(BLOCK), 0, s, P, \
-                               idx, row_dest, proc, n_rows, L, out,           \
-                               (long long)pitch);                             \
-        else if (LPS < 32 && P.n_coef >= 4 && state_kernel != 3)    \
-            hipLaunchKernelGGL((k_state_dd<LPS, 4, (LPS >= 32), (LPS < 32)>), grid, dim3(BLOCK), 0, s, \
-                               P, idx, row_dest, proc, n_rows, L, out,   \
-                               (long long)pitch, n_vb);                       \
-        else                                                                  \
-            hipLaunchKernelGGL((k_state_dd<LPS, (LPS >= 32 ? 2 : 4), (LPS >= 32), false>), grid, dim3(BLOCK), 0, s, \
-                               P, idx, row_dest, proc, n_rows, L, out,   \
-                               (long long)pitch, n_vb);                       \
-    } while (0)
-    if (C4 <= 4) TTL_LAUNCH_STATE(4);
-    else if (C4 <= 8) TTL_LAUNCH_STATE(8);
-    else if (C4 <= 12) TTL_LAUNCH_STATE(12);
-    else if (C4 <= 16) TTL_LAUNCH_STATE(16);
-    else TTL_LAUNCH_STATE(32);
-#undef TTL_LAUNCH_STATE
+    for_lanes_per_streamline<32>(P, [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        const int n_vb = (int)gather_grid<LPS>(n_rows).x;
+        // TTL_GATHER_PERSIST_ROWS (experiment, off by default): batches of at
+        // most that many rows that need more than one resident round (4
+        // workgroups per CU x 256 CUs) run as ONE round of workgroups that
+        // walk the blocks with a stride
+        const int resident = 1024;
+        const bool persist = dedupe && n_rows <= P.persist_rows && n_vb > resident;
+        const dim3 grid(persist ? resident : n_vb);
+        if (!dedupe)
+            hipLaunchKernelGGL((k_state<LPS>), grid, dim3(BLOCK), 0, s, P, idx, row_dest, proc,
+                               n_rows, L, out, (long long)pitch);
+        else if (LPS < 32 && P.n_coef >= 4 && state_kernel != 3)
+            hipLaunchKernelGGL((k_state_dd<LPS, 4, (LPS >= 32), (LPS < 32)>), grid, dim3(BLOCK), 0,
+                               s, P, idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb);
+        else
+            hipLaunchKernelGGL((k_state_dd<LPS, (LPS >= 32 ? 2 : 4), (LPS >= 32), false>), grid,
+                               dim3(BLOCK), 0, s, P, idx, row_dest, proc, n_rows, L, out,
+                               (long long)pitch, n_vb);
+    });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

@@ -236,7 +236,6 @@ class TrackingEnvironment(BaseEnv):
             self._state_pitch, self._stream()), 'ttl_env_reset')
         self._n_total = n
         self._n_active = n
-        self._order_slots = n if sort_rows else 0
         self._cur = 0
         self.length = 1
         self._pending = None
@@ -267,52 +266,33 @@ class TrackingEnvironment(BaseEnv):
         if n < self.SPATIAL_ORDER_MIN or self._pending is not None or \
                 not getattr(self, 'spatial_order', True):
             return
-        if not force and self._order_instep():
+        slots, instep = self._library_order()
+        if not force and instep:
             # the library re-buckets the order inside its own steps
             # (TTL_ORDER_INSTEP): no periodic and no low-fill refresh from here
             return
-        # between refreshes the order keeps its length (the step's fused tail does
-        # not compact it: stopped streamlines leave holes at the end of their
-        # 256-slot block): refresh early once a fifth of it is holes
-        slots = getattr(self, '_order_slots', 0)
-        sparse = bool(every) and self.length > 1 and slots and n < self.ORDER_MIN_FILL * slots \
-            and slots <= self.TAIL_FUSED_MAX_ROWS and self._order_keeps_holes()
+        # between refreshes the order keeps its length where the step's fused
+        # tail runs (it does not compact the order: stopped streamlines leave
+        # holes at the end of their 256-slot block): refresh early once a fifth
+        # of it is holes.  The library reports more slots than rows only then
+        sparse = bool(every) and self.length > 1 and slots and n < self.ORDER_MIN_FILL * slots
         if not force and not sparse and \
                 (not every or self.length <= 1 or (self.length - 1) % every):
             return
         _lib.check(self._lib.ttl_env_refresh_processing_order(
             self._handle, self._stream()), 'ttl_env_refresh_processing_order')
-        self._order_slots = n
 
-    def _order_instep(self):
-        """Period of the library's in-step re-bucket on this handle (0: off);
-        also takes ``_order_slots`` from the library, which compacts the order
-        on its re-bucket steps."""
+    def _library_order(self):
+        """(length of the processing order -- 0: none --, period of the library's
+        in-step re-bucket on this handle -- 0: off), both as the library has them."""
         slots, period = C.c_int32(0), C.c_int32(0)
         _lib.check(self._lib.ttl_env_order_slots(
             self._handle, C.byref(slots), C.byref(period)), 'ttl_env_order_slots')
-        if period.value:
-            self._order_slots = slots.value
-        return period.value
-
-    def _order_keeps_holes(self):
-        """Whether the library runs the one-launch tail on this handle (only then
-        does the order keep holes between refreshes): the gather must read the
-        per-slot records, i.e. the register-deduplicating kernel (TTL_STATE_KERNEL
-        not 0 or 2) with a neighbourhood radius inside (0, 1) voxel -- the
-        conditions of ``fused_tail`` in ttl_env_step."""
-        return os.environ.get('TTL_STATE_KERNEL', '') not in ('0', '2') and \
-            bool(self.add_neighborhood_vox) and \
-            0.0 < float(np.float32(self.add_neighborhood_vox)) < 1.0
+        return slots.value, period.value
 
     #: refresh the processing order early when fewer than this share of its slots
     #: still hold a streamline
     ORDER_MIN_FILL = float(os.environ.get('TTL_ORDER_MIN_FILL', '0.8'))
-    #: the library's fused tail (and with it the holes) is used for orders of at
-    #: most this many slots (mirrors TTL_TAIL_FUSED / TTL_TAIL_FUSED_MAX_ROWS)
-    TAIL_FUSED_MAX_ROWS = 0 if os.environ.get('TTL_TAIL_FUSED', '1') == '0' else \
-        min(int(os.environ.get('TTL_TAIL_FUSED_MAX_ROWS', '262144')), 4096 * 256)
-
     def nreset(self, n_seeds: int):
         """N random seeds among all seeds (tracking_env.py:47-89; global
         numpy RNG, as the reference)."""
