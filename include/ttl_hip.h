@@ -600,6 +600,56 @@ TTL_API int ttl_tract_emit(const float *history, int64_t row_pitch, int32_t n,
                            const uint64_t *mask, float *points_out, int64_t *counts_out,
                            int32_t *rows_out, void *hip_stream);
 
+/* The file body of a batch, built by the pack (TTL_HAS_TRACT_FILE).  Both
+ * tractogram formats are flat streams of little-endian 4-byte words whose records do not
+ * depend on where they sit in the file, so the bodies of successive batches (or ranks)
+ * concatenate.  ttl_tract_emit_file takes ttl_tract_emit's inputs and writes, for accepted
+ * input row i (output row k = accept_ends[i] - 1, b = count_ends[i] - counts[i] points
+ * before it, P = n_props):
+ *   TTL_TRACT_FILE_TRK  at word k (1 + P) + 3 b: counts[i] as int32, the converted points,
+ *                       then for P == 3 float32(seeds[i][c] - 0.5), c = 0..2, the
+ *                       subtraction in float64;
+ *   TTL_TRACT_FILE_TCK  at word 3 (b + k): the converted points, then three words
+ *                       0x7fc00000 (a float32 NaN triplet).  The format has no
+ *                       properties: n_props is validated and otherwise ignored, and the
+ *                       closing inf triplet belongs to the file, not to a batch.
+ * A point p (float32 x, y, z) is converted by the steps the descriptor switches on, in
+ * this order, each in plain IEEE arithmetic with nothing fused:
+ *   pre     v_c = float32(float64(float32(p_c + 0.5f)) * pre_scale), widened to float64
+ *           (without it v_c = float64(p_c));
+ *   maps    n_maps <= 2 affine maps m, 3 x 4 row-major float64, one after the other:
+ *           out_i = ((x m[i][0] + y m[i][1]) + z m[i][2]) + m[i][3];
+ *   post    v_i = (v_i + 0.5) * post_scale[i];
+ * and v is rounded to float32 once.  seeds is device f64 [n][3], indexed by input row, or
+ * NULL; desc is host memory; words_out holds ttl_tract_file_words(format, n_props,
+ * accept_ends[n-1], count_ends[n-1]) words and is written with 4-byte stores only (record
+ * starts are 4-byte aligned).  One wavefront per row; one lane converts one point.
+ * TTL_ERR_INVALID, before any launch, for an unknown format, n_props other than 0 or 3,
+ * n_props == 3 without seeds, or n_maps outside [0, 2]; ttl_tract_file_words returns -1
+ * for the first two.  n == 0 is a successful no-op, and so is a batch without an accepted
+ * row (words_out may then be NULL). */
+#define TTL_HAS_TRACT_FILE 1
+#define TTL_TRACT_FILE_TRK 0
+#define TTL_TRACT_FILE_TCK 1
+typedef struct ttl_tract_file_desc {
+    int32_t format;       /* TTL_TRACT_FILE_* */
+    int32_t n_props;      /* 0 or 3 (the seed) */
+    int32_t has_pre;
+    int32_t n_maps;
+    int32_t has_post;
+    int32_t reserved;     /* 0 */
+    double pre_scale;
+    double maps[2][12];
+    double post_scale[3];
+} ttl_tract_file_desc;
+TTL_API int64_t ttl_tract_file_words(int32_t format, int32_t n_props, int64_t k, int64_t M);
+TTL_API int ttl_tract_emit_file(const float *history, int64_t row_pitch, int32_t n,
+                                const int32_t *counts, const int32_t *accepted,
+                                const int64_t *count_ends, const int64_t *accept_ends,
+                                const uint64_t *mask, const double *seeds,
+                                const ttl_tract_file_desc *desc, uint32_t *words_out,
+                                void *hip_stream);
+
 TTL_API const char *ttl_last_error(void);
 TTL_API uint32_t ttl_abi_version(void);
 /* sizeof(ttl_env_desc) as compiled: a binding checks its own struct against it */

@@ -1,0 +1,571 @@
+"""File bodies built a batch at a time: `io.streamlines.packed_body`
+-- the specification of `ttl_tract_emit_file` -- and `PackedWriter` against
+`io.streamlines.save` over the `TractogramItem`s the tracker yields today.
+
+Axis-aligned matrices: every row of every map has one non-zero product, so
+neither the summation order nor fusing can change a bit, and the files are
+compared byte for byte.  The golden fixtures' rotated affine: the existing
+writer's float64 products go through the BLAS, whose order and fusing are its
+own; the `.trk` chain maps a float32-representable value there and back, so
+`(v + 0.5) * vs` lands on float32 ties that 1e-14 of float64 noise decides.
+Everything but the point words is compared exactly there, and the point words
+to 1 float32 ulp.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COUNTS = (1, 2, 63, 64, 65, 129)
+FLIP = np.array([[-2.0, 0.0, 0.0, 91.0], [0.0, 2.0, 0.0, -126.0], [0.0, 0.0, 2.0, -72.0],
+                 [0.0, 0.0, 0.0, 1.0]])
+ANISO = np.array([[1.25, 0.0, 0.0, -16.0], [0.0, 1.25, 0.0, -20.0], [0.0, 0.0, 2.5, 5.0],
+                  [0.0, 0.0, 0.0, 1.0]])
+# (the env's vox -> rasmm, the header's vox -> rasmm, the header's voxel sizes)
+AXIS_ALIGNED = {'flip': (FLIP, FLIP, (2.0, 2.0, 2.0)),
+                'identity': (np.eye(4), np.eye(4), (1.0, 1.0, 1.0)),
+                'identity_then_aniso': (np.eye(4), ANISO, (1.25, 1.25, 2.5))}
+
+
+def rotated():
+    with np.load(os.path.join(ROOT, 'tests', 'golden', 'tracker_trk.npz')) as z:
+        return z['affine'].astype(np.float64)
+
+
+def batch(counts, seed):
+    """(points (M, 3) f32 in voxel space, negative coordinates included,
+    counts, seeds (k, 3) f64)."""
+    rng = np.random.RandomState(seed)
+    counts = np.asarray(counts, dtype=np.int64)
+    points = rng.uniform(-20.0, 90.0, (int(counts.sum()), 3)).astype(np.float32)
+    seeds = rng.uniform(0.0, 90.0, (len(counts), 3))
+    return points, counts, seeds
+
+
+def header_of(vox2ras, voxel_sizes):
+    from tracktolearn_amd.io import streamlines as sio
+    return sio.create_tractogram_header(vox2ras, (96, 96, 60), voxel_sizes)
+
+
+def vox_size_of(affine):
+    return np.mean(np.abs(affine)[np.diag_indices(4)][:3])
+
+
+def save_items(path, ext, affine, header, points, counts, seeds):
+    """`sio.save` over the items `Tracker.batch_output` makes of the batch."""
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.tracking import tracker as trk
+    from tracktolearn_amd.tractogram import LazyTractogram, TractogramItem
+    fmt = trk.TrkFile if ext == '.trk' else trk.TckFile
+    offs = np.concatenate(([0], np.cumsum(counts)))
+
+    def items():
+        for k in range(len(counts)):
+            s = trk.to_file_space(points[offs[k]:offs[k + 1]], fmt, affine, vox_size_of(affine))
+            yield TractogramItem(s, {} if seeds is None else {'seeds': seeds[k] - 0.5}, {})
+    tractogram = LazyTractogram.from_data_func(items)
+    tractogram.affine_to_rasmm = affine
+    return sio.save(tractogram, path, header=header)
+
+
+def write_packed(path, ext, affine, header, points, counts, seeds, cuts=()):
+    """`PackedWriter` fed with `packed_body` of the batch cut at rows `cuts`."""
+    from tracktolearn_amd.io import streamlines as sio
+    n_props = 3 if seeds is not None and ext == '.trk' else 0
+    desc = sio.body_desc(ext, affine, vox_size_of(affine), header, n_props)
+    offs = np.concatenate(([0], np.cumsum(counts)))
+    edges = [0] + list(cuts) + [len(counts)]
+    with sio.PackedWriter(path, ext, header, n_props) as w:
+        for a, b in zip(edges[:-1], edges[1:]):
+            words = sio.packed_body(points[offs[a]:offs[b]], counts[a:b],
+                                    None if seeds is None else seeds[a:b], desc)
+            assert words.dtype == np.uint32
+            w.append(words, b - a)
+    return w.close(), desc
+
+
+def ordered(words):
+    """float32 bit patterns -> integers whose difference is the ulp distance."""
+    i = np.asarray(words).view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7fffffff), i)
+
+
+def split_words(raw, ext, n_props):
+    """The file's 4-byte words after the header, and which of them are point
+    words (True) as opposed to counts, properties, NaN and inf words."""
+    if ext == '.trk':
+        start = 1000
+    else:
+        start = int(re.search(rb'file: \. (\d+)', raw).group(1))
+    words = np.frombuffer(raw, '<u4', offset=start)
+    is_point = np.zeros(len(words), dtype=bool)
+    pos = 0
+    if ext == '.trk':
+        while pos < len(words):
+            n = int(words[pos:pos + 1].view(np.int32)[0])
+            is_point[pos + 1:pos + 1 + 3 * n] = True
+            pos += 1 + 3 * n + n_props
+        assert pos == len(words)
+    else:
+        f = words.view(np.float32)
+        is_point = ~(np.isnan(f) | np.isinf(f))
+    return raw[:start], words, is_point
+
+
+# --------------------------------------------------------------------------
+# CPU
+# --------------------------------------------------------------------------
+@pytest.mark.parametrize('chain', sorted(AXIS_ALIGNED))
+@pytest.mark.parametrize('ext,with_seeds', [('.trk', True), ('.trk', False), ('.tck', False)])
+def test_axis_aligned_files_equal_the_existing_writer_byte_for_byte(tmp_path, chain, ext,
+                                                                    with_seeds):
+    affine, vox2ras, voxel_sizes = AXIS_ALIGNED[chain]
+    header = header_of(vox2ras, voxel_sizes)
+    points, counts, seeds = batch(COUNTS + COUNTS[::-1], seed=11)
+    assert (points < 0).any()
+    seeds = seeds if with_seeds else None
+    old, new = str(tmp_path / ('old' + ext)), str(tmp_path / ('new' + ext))
+    assert save_items(old, ext, affine, header, points, counts, seeds) == len(counts)
+    n, desc = write_packed(new, ext, affine, header, points, counts, seeds, cuts=(5, 6))
+    assert n == len(counts)
+    # the identity tractogram affine is skipped, as the writer skips it
+    assert len(desc.maps) == (1 if chain.startswith('identity') else 2)
+    assert open(new, 'rb').read() == open(old, 'rb').read()
+
+
+@pytest.mark.parametrize('ext', ['.trk', '.tck'])
+def test_a_file_without_streamlines_equals_the_existing_writers(tmp_path, ext):
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.tractogram import Tractogram
+    header = header_of(FLIP, (2.0, 2.0, 2.0))
+    old, new = str(tmp_path / ('old' + ext)), str(tmp_path / ('new' + ext))
+    assert sio.save(Tractogram([], {}), old, header=header) == 0
+    w = sio.PackedWriter(new, ext, header, n_props=3)
+    desc = sio.body_desc(ext, FLIP, 2.0, header, 3)
+    empty = sio.packed_body(np.zeros((0, 3), np.float32), np.zeros(0, np.int64),
+                            np.zeros((0, 3)), desc)
+    assert empty.shape == (0,) and empty.dtype == np.uint32
+    w.append(empty, 0)
+    assert w.close() == 0
+    assert open(new, 'rb').read() == open(old, 'rb').read()
+    loaded = (sio.load_trk if ext == '.trk' else sio.load_tck)(new)
+    assert len(loaded[0]) == 0
+
+
+@pytest.mark.parametrize('ext,with_seeds', [('.trk', True), ('.trk', False), ('.tck', False)])
+def test_rotated_files_agree_with_the_existing_writer_to_one_ulp(tmp_path, ext, with_seeds):
+    from tracktolearn_amd.io import streamlines as sio
+    R = rotated()
+    assert np.count_nonzero(R[:3, :3]) > 3          # not axis-aligned
+    header = header_of(R, (2.0, 2.0, 2.0))
+    rng = np.random.RandomState(5)
+    points, counts, seeds = batch(list(COUNTS) + list(rng.randint(1, 200, 300)), seed=12)
+    seeds = seeds if with_seeds else None
+    old, new = str(tmp_path / ('old' + ext)), str(tmp_path / ('new' + ext))
+    save_items(old, ext, R, header, points, counts, seeds)
+    n, desc = write_packed(new, ext, R, header, points, counts, seeds, cuts=(100,))
+    assert n == len(counts) and len(desc.maps) == 2
+    a, b = open(old, 'rb').read(), open(new, 'rb').read()
+    assert len(a) == len(b)
+    head_a, words_a, points_a = split_words(a, ext, desc.n_props if ext == '.trk' else 0)
+    head_b, words_b, points_b = split_words(b, ext, desc.n_props if ext == '.trk' else 0)
+    assert head_a == head_b
+    assert np.array_equal(points_a, points_b) and points_a.sum() == 3 * len(points)
+    # counts, properties, NaN and inf words
+    assert np.array_equal(words_a[~points_a], words_b[~points_b])
+    ulps = np.abs(ordered(words_a[points_a]) - ordered(words_b[points_b]))
+    print(f'{ext}: {int((ulps != 0).sum())} of {len(ulps)} point words differ '
+          f'({100.0 * (ulps != 0).mean():.3f} %), largest distance {int(ulps.max())} ulp')
+    assert ulps.max() <= 1
+    loaded, info = (sio.load_trk if ext == '.trk' else sio.load_tck)(new)
+    assert len(loaded) == len(counts)
+    assert int(info['nb_streamlines'] if ext == '.trk' else info['count']) == len(counts)
+
+
+@pytest.mark.parametrize('fmt', ['.trk', '.tck'])
+@pytest.mark.parametrize('n_props', [0, 3])
+def test_the_body_of_a_batch_is_the_concatenation_of_its_chunks(fmt, n_props):
+    """What the multi-batch and multi-rank paths rest on."""
+    from tracktolearn_amd.io import streamlines as sio
+    R = rotated()
+    desc = sio.body_desc(fmt, R, 2.0, header_of(R, (2.0, 2.0, 2.0)), n_props)
+    rng = np.random.RandomState(8)
+    points, counts, seeds = batch(list(COUNTS) + list(rng.randint(1, 140, 60)), seed=13)
+    seeds = seeds if n_props else None
+    whole = sio.packed_body(points, counts, seeds, desc)
+    assert len(whole) == sio.body_words(desc, len(counts), len(points))
+    offs = np.concatenate(([0], np.cumsum(counts)))
+    for cuts in ([1], [0, 0, 33], [len(counts) - 1], sorted(rng.randint(0, len(counts), 9))):
+        edges = [0] + list(cuts) + [len(counts)]
+        parts = [sio.packed_body(points[offs[a]:offs[b]], counts[a:b],
+                                 None if seeds is None else seeds[a:b], desc)
+                 for a, b in zip(edges[:-1], edges[1:])]
+        assert np.array_equal(np.concatenate(parts), whole)
+
+
+def test_host_select_tracts_file_is_packed_body_of_select_tracts():
+    import torch
+    from test_tract_output import make_rows
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.parallel import select_tracts, select_tracts_file
+    hist, lengths, flags = make_rows(96, 120, seed=5)
+    h, ln, fl = (torch.from_numpy(a) for a in (hist, lengths, flags))
+    seeds = np.random.RandomState(2).uniform(0.0, 90.0, (len(hist), 3))
+    R = rotated()
+    for fmt in ('.trk', '.tck'):
+        desc = sio.body_desc(fmt, R, 2.0, header_of(R, (2.0, 2.0, 2.0)), 3)
+        pts, counts, rows = select_tracts(h, ln, fl, 3.1, 40.1, 0.1)
+        words, k, M = select_tracts_file(h, ln, fl, 3.1, 40.1, desc, seeds, tol_error=0.1)
+        assert words.dtype == torch.int32 and (k, M) == (len(counts), len(pts)) and 0 < k < 96
+        want = sio.packed_body(pts.numpy(), counts.numpy(), seeds[rows.numpy()], desc)
+        assert np.array_equal(words.numpy().view(np.uint32), want)
+        with pytest.raises(ValueError):
+            select_tracts_file(h, ln, fl, 3.1, 40.1, desc, None)
+    empty = select_tracts_file(h[:0], ln[:0], fl[:0], 0.0, 1.0, desc, seeds[:0])
+    assert (tuple(empty[0].shape), empty[1], empty[2]) == ((0,), 0, 0)
+
+
+def test_the_file_entry_points_are_declared_bound_and_refuse_bad_descriptors():
+    from tracktolearn_amd import _lib
+    from tracktolearn_amd.io import streamlines as sio
+    with open(os.path.join(ROOT, 'include', 'ttl_hip.h')) as f:
+        header = f.read()
+    assert '#define TTL_HAS_TRACT_FILE 1' in header
+    assert '#define TTL_ABI_VERSION 13' in header and _lib.ABI_VERSION == 13
+    assert 'TTL_API int ttl_tract_emit_file(' in header
+    assert 'TTL_API int64_t ttl_tract_file_words(' in header
+    struct = header[header.index('typedef struct ttl_tract_file_desc {'):
+                    header.index('} ttl_tract_file_desc;')]
+    fields = [name for name, _ in _lib.TractFileDesc._fields_]
+    assert re.findall(r'\b(\w+)(?:\[\d+\])*;', struct) == fields
+    assert C.sizeof(_lib.TractFileDesc) == 6 * 4 + 8 * (1 + 24 + 3)
+    assert (sio.TRK, sio.TCK) == (_lib.TRACT_FILE_TRK, _lib.TRACT_FILE_TCK) == (0, 1)
+    assert int(re.search(r'#define TTL_TRACT_FILE_TCK (\d)', header).group(1)) == sio.TCK
+    lib = _lib.load()
+    assert lib.ttl_abi_version() == 13
+    for name in ('ttl_tract_emit_file', 'ttl_tract_file_words'):
+        assert getattr(lib, name).argtypes == _lib.SYMBOLS[name][1]
+    words = lib.ttl_tract_file_words
+    assert words(sio.TRK, 0, 5, 100) == 305 and words(sio.TRK, 3, 5, 100) == 320
+    assert words(sio.TCK, 0, 5, 100) == words(sio.TCK, 3, 5, 100) == 315
+    assert words(sio.TRK, 3, 2 ** 29, 2 ** 31) == 4 * 2 ** 29 + 3 * 2 ** 31     # int64
+    assert words(2, 0, 5, 100) == -1 and words(sio.TRK, 2, 5, 100) == -1
+    assert words(sio.TRK, 0, 0, 0) == 0
+    for desc in (sio.BodyDesc(sio.TRK, 3), sio.BodyDesc(sio.TCK, 0)):
+        assert words(desc.format, desc.n_props, 7, 50) == sio.body_words(desc, 7, 50)
+
+    # refused on the host before any launch (n == 0: nothing would be launched anyway)
+    def emit(desc, seeds=None):
+        return lib.ttl_tract_emit_file(None, 3 * 8, 0, None, None, None, None, None, seeds,
+                                       C.byref(desc), None, None)
+    good = sio.BodyDesc(sio.TRK, 0, pre_scale=2.0, maps=[FLIP[:3], FLIP[:3]],
+                        post_scale=(2.0, 2.0, 2.0)).to_c()
+    assert (good.has_pre, good.n_maps, good.has_post, good.pre_scale) == (1, 2, 1, 2.0)
+    assert list(good.maps[1]) == list(FLIP[:3].reshape(-1)) and list(good.post_scale) == [2.0] * 3
+    assert emit(good) == 0
+    bad = []
+    for field, value in (('format', 2), ('format', -1), ('n_props', 1), ('n_props', 4),
+                         ('n_props', 3), ('n_maps', 3), ('n_maps', -1)):
+        d = sio.BodyDesc(sio.TRK, 0, maps=[FLIP[:3]]).to_c()
+        setattr(d, field, value)
+        bad.append(emit(d))
+    assert bad == [_lib.ERR_INVALID] * 7
+    with pytest.raises(ValueError):
+        sio.packed_body(np.zeros((0, 3), np.float32), [], None, sio.BodyDesc(sio.TRK, 3))
+    with pytest.raises(ValueError):
+        sio.packed_body(np.zeros((0, 3), np.float32), [], None, sio.BodyDesc(2, 0))
+    with pytest.raises(ValueError):
+        sio.packed_body(np.zeros((0, 3), np.float32), [], None,
+                        sio.BodyDesc(sio.TCK, 0, maps=[FLIP[:3]] * 3))
+
+
+# --------------------------------------------------------------------------
+# GPU
+# --------------------------------------------------------------------------
+T_ROW, N_ROWS = 267, 2048
+KEPT = (0, 1, 2, 63, 64, 65, 128, 129, T_ROW)
+REJECTED = [0, N_ROWS - 1] + list(range(100, 111)) + list(range(500, 571))
+MAX_ARC = 200.0
+SENTINEL = np.uint32(0xA5A5A5A5).view(np.int32).item()
+_ROWS = {}
+
+
+def file_rows(n=N_ROWS, T=T_ROW, seed=31):
+    """`test_tract_output.make_rows` with the kept counts of KEPT forced (flags
+    0 and with a cut flag) and one full row, and the rows of REJECTED -- the
+    first, the last and two runs, one longer than a block's rows -- given an
+    arc of more than 3000 voxels.  Made once; callers leave it unchanged."""
+    if (n, T, seed) not in _ROWS:
+        from test_tract_output import make_rows
+        hist, lengths, flags = make_rows(n, T, seed)
+        # the forced rows: a walk over the whole row (make_rows leaves junk after a length)
+        rng = np.random.RandomState(seed + 2)
+        d = rng.standard_normal((32, T, 3))
+        d *= 0.375 / np.linalg.norm(d, axis=2, keepdims=True)
+        d[:, 0] = rng.uniform(5.0, 90.0, (32, 3))
+        hist[8:40] = np.cumsum(d, axis=1).astype(np.float32)
+        at = 8
+        for keep in KEPT:
+            lengths[at], flags[at] = max(keep, 1), (1 if keep == 0 else 0)
+            at += 1
+            if 0 < keep < T:
+                lengths[at], flags[at] = keep + 1, 4
+                at += 1
+        lengths[at], flags[at] = T, 0
+        assert at < 40
+        for r in [r for r in REJECTED if r < n - 1] + [n - 1]:
+            lengths[r], flags[r] = max(lengths[r], 3), 0
+            hist[r, 1] = (1e3, -1e3, 1e3)
+        seeds = np.random.RandomState(seed + 1).uniform(0.0, 90.0, (n, 3))
+        _ROWS[(n, T, seed)] = (hist, lengths, flags, seeds)
+    return _ROWS[(n, T, seed)]
+
+
+def chains():
+    R = rotated()
+    return {'trk_rotated': ('.trk', R, R, (2.0, 2.0, 2.0)),
+            'trk_axis_aligned': ('.trk', FLIP, FLIP, (2.0, 2.0, 2.0)),
+            'tck_rotated': ('.tck', R, None, None),
+            'trk_identity_first': ('.trk', np.eye(4), R, (2.0, 2.0, 2.0)),
+            'tck_identity_second': ('.tck', np.eye(4), None, None)}
+
+
+def chain_desc(name, n_props):
+    from tracktolearn_amd.io import streamlines as sio
+    ext, affine, vox2ras, voxel_sizes = chains()[name]
+    header = None if vox2ras is None else header_of(vox2ras, voxel_sizes)
+    return sio.body_desc(ext, affine, vox_size_of(affine), header, n_props)
+
+
+def emit_file_guarded(h, ln, fl, lo, hi, tol, desc, seeds):
+    """`ttl_tract_emit_file` into a buffer filled with SENTINEL that is 64
+    words longer than the body; returns (words, the 64 guard words, k, M)."""
+    import torch
+    from tracktolearn_amd import _lib
+    from tracktolearn_amd.parallel import tract_survivors
+    lib = _lib.load()
+    hist, sel, mask = tract_survivors(h, ln, fl, lo, hi, tol)
+    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64), torch.cumsum(sel[1], 0, dtype=torch.int64))
+    M, k = int(ends[0][-1]), int(ends[1][-1])
+    c_desc = desc.to_c()
+    size = lib.ttl_tract_file_words(c_desc.format, c_desc.n_props, k, M)
+    out = torch.full((size + 64,), SENTINEL, dtype=torch.int32, device=h.device)
+    torch.cuda.synchronize()
+    _lib.check(lib.ttl_tract_emit_file(
+        hist.data_ptr(), hist.stride(0), len(h), sel[0].data_ptr(), sel[1].data_ptr(),
+        ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(),
+        seeds.data_ptr() if seeds is not None else None, C.byref(c_desc), out.data_ptr(),
+        None), 'ttl_tract_emit_file')
+    torch.cuda.synchronize()
+    out = out.cpu().numpy()
+    return out[:size].view(np.uint32), out[size:], k, M
+
+
+def check_against_the_specification(rows, desc, tol, expect_counts=(), max_arc=MAX_ARC):
+    import torch
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.parallel import select_tracts, select_tracts_file
+    hist, lengths, flags, seeds = rows
+    dev = torch.device('cuda:0')
+    h, ln, fl = (torch.from_numpy(a).to(dev) for a in (hist, lengths, flags))
+    sd = torch.from_numpy(seeds).to(dev) if desc.n_props else None
+    pts, counts, sel = select_tracts(h, ln, fl, 0.0, max_arc, tol)
+    sel = sel.cpu().numpy()
+    rejected = sorted(set(range(len(hist))) - set(sel.tolist()))
+    assert rejected == sorted(r for r in set(REJECTED) | {len(hist) - 1} if r < len(hist))
+    if tol == 0.0:
+        assert set(expect_counts) <= set(counts.tolist())
+    else:       # words that are compacted, not copied
+        assert int(counts.sum()) < int((lengths[sel] - ((flags[sel] & 5) != 0)).sum())
+    want = sio.packed_body(pts.cpu().numpy(), counts.cpu().numpy(),
+                           seeds[sel] if desc.n_props else None, desc)
+    words, k, M = select_tracts_file(h, ln, fl, 0.0, max_arc, desc, sd, tol_error=tol)
+    assert words.is_cuda and words.dtype == torch.int32
+    assert (k, M) == (len(counts), len(pts)) and k > 0
+    got = words.cpu().numpy().view(np.uint32)
+    assert got.shape == want.shape
+    assert np.array_equal(got, want), np.nonzero(got != want)[0][:8]
+    guarded, guard, k2, M2 = emit_file_guarded(h, ln, fl, 0.0, max_arc, tol, desc, sd)
+    assert (k2, M2) == (k, M)
+    assert (guard == SENTINEL).all()
+    assert np.array_equal(guarded, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('tol', [0.0, 0.1])
+@pytest.mark.parametrize('n_props', [0, 3])
+@pytest.mark.parametrize('chain', ['trk_rotated', 'trk_axis_aligned', 'tck_rotated',
+                                   'trk_identity_first', 'tck_identity_second'])
+def test_the_kernel_equals_the_specification_bit_for_bit(chain, n_props, tol):
+    check_against_the_specification(file_rows(), chain_desc(chain, n_props), tol,
+                                    expect_counts=KEPT)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('chain,n_props', [('trk_rotated', 3), ('tck_rotated', 0)])
+def test_rows_beyond_the_staging_limit_give_the_same_body(chain, n_props):
+    from tracktolearn_amd import _lib
+    T = 2304
+    assert T > _lib.load().ttl_tract_stage_points()
+    rows = file_rows(n=96, T=T, seed=77)
+    assert rows[1].max() == T
+    # every row but the rejected ones is shorter than 1000 voxels
+    check_against_the_specification(rows, chain_desc(chain, n_props), 0.1, max_arc=1000.0)
+    check_against_the_specification(rows, chain_desc(chain, n_props), 0.0, KEPT + (T,),
+                                    max_arc=1000.0)
+
+
+@pytest.mark.gpu
+def test_degenerate_batches_give_empty_bodies_and_bad_descriptors_are_refused():
+    import torch
+    from tracktolearn_amd import _lib
+    from tracktolearn_amd.parallel import select_tracts_file, tract_survivors
+    hist, lengths, flags, seeds = file_rows()
+    dev = torch.device('cuda:0')
+    h, ln, fl, sd = (torch.from_numpy(a).to(dev) for a in (hist, lengths, flags, seeds))
+    lib = _lib.load()
+    for chain in ('trk_rotated', 'tck_rotated'):
+        desc = chain_desc(chain, 3)
+        # every row rejected
+        words, k, M = select_tracts_file(h, ln, fl, 1e6, 2e6, desc, sd, tol_error=0.1)
+        assert (tuple(words.shape), k, M) == ((0,), 0, 0) and words.is_cuda
+        guarded, guard, k, M = emit_file_guarded(h, ln, fl, 1e6, 2e6, 0.1, desc, sd)
+        assert (len(guarded), k, M) == (0, 0, 0) and (guard == SENTINEL).all()
+        # no row at all
+        words, k, M = select_tracts_file(h[:0], ln[:0], fl[:0], 0.0, MAX_ARC, desc, sd[:0])
+        assert (tuple(words.shape), k, M) == ((0,), 0, 0)
+    # refusals with a real batch behind them: nothing is launched, nothing written
+    hist_d, sel, mask = tract_survivors(h, ln, fl, 0.0, MAX_ARC, 0.0)
+    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64), torch.cumsum(sel[1], 0, dtype=torch.int64))
+    size = lib.ttl_tract_file_words(0, 3, int(ends[1][-1]), int(ends[0][-1]))
+    out = torch.full((size,), SENTINEL, dtype=torch.int32, device=dev)
+
+    def emit(c_desc, seeds_ptr):
+        return lib.ttl_tract_emit_file(
+            hist_d.data_ptr(), hist_d.stride(0), len(h), sel[0].data_ptr(), sel[1].data_ptr(),
+            ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(), seeds_ptr,
+            C.byref(c_desc), out.data_ptr(), None)
+    for field, value, seeds_ptr in (('format', 2, sd.data_ptr()), ('n_props', 2, sd.data_ptr()),
+                                    ('n_props', 3, None), ('n_maps', 3, sd.data_ptr())):
+        c_desc = chain_desc('trk_rotated', 0).to_c()
+        setattr(c_desc, field, value)
+        assert emit(c_desc, seeds_ptr) == _lib.ERR_INVALID
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all())
+
+
+def _tracker(name, compress):
+    import torch
+    from helpers import load_trace
+    from test_tracker_golden import ReplayAgent, _Alg, _gpu_env
+    from tracktolearn_amd.tracking import tracker as trk
+    z = load_trace(name)
+    env = _gpu_env(z, noisy=True, reward=False)
+    env.seeds = z['seeds_before_shuffle'].copy()
+    agent = ReplayAgent(z, torch.device('cuda:0'))
+    tracker = trk.Tracker(_Alg(agent), n_actor=int(z['n_actor']), prob=0.0, compress=compress,
+                          min_length=float(z['min_length']), max_length=float(z['max_length']),
+                          save_seeds=True)
+    np.random.seed(int(z['shuffle_seed']))
+    return z, env, agent, tracker
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', ['tracker_trk', 'tracker_tck'])
+@pytest.mark.parametrize('compress', [0.0, 0.2])
+def test_track_to_file_on_the_golden_traces(tmp_path, name, compress):
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.tracking import tracker as trk
+    ext = '.trk' if name == 'tracker_trk' else '.tck'
+    fmt = trk.TrkFile if ext == '.trk' else trk.TckFile
+    direct, spec, old = (str(tmp_path / (n + ext)) for n in ('direct', 'spec', 'old'))
+
+    z, env, agent, tracker = _tracker(name, compress)
+    assert (len(env.seeds), tracker.n_actor) == (150, 64)      # batches of 64, 64 and 22
+    header = sio.create_tractogram_header(z['affine'], (int(z['D']),) * 3, (2.0, 2.0, 2.0))
+    count = tracker.track_to_file(env, direct, header)
+    assert agent.i == len(agent.batches)
+    assert np.array_equal(env.seeds, z['seeds_after_shuffle'])
+
+    # the specification: packed_body of each batch's select_tracts output
+    z, env, agent, tracker = _tracker(name, compress)
+    vox_size = vox_size_of(env.affine_vox2rasmm)
+    n_props = 3 if ext == '.trk' else 0
+    desc = sio.body_desc(ext, env.affine_vox2rasmm, vox_size, header, n_props)
+    np.random.shuffle(env.seeds)
+    batches = 0
+    with sio.PackedWriter(spec, ext, header, n_props) as w:
+        for _ in tracker._tracked_batches(env):
+            pts, counts, seeds = tracker._batch_arrays(
+                env, tracker.min_length / vox_size, tracker.max_length / vox_size,
+                compress / vox_size)
+            w.append(sio.packed_body(pts.cpu().numpy(), counts.cpu().numpy(), seeds.numpy(),
+                                     desc), len(counts))
+            batches += 1
+    assert batches == 3 and w.close() == count > 0
+    raw = open(direct, 'rb').read()
+    assert raw == open(spec, 'rb').read()
+
+    # the existing path
+    z, env, agent, tracker = _tracker(name, compress)
+    assert sio.save(tracker.track(env, fmt), old, header=header) == count
+    a = open(old, 'rb').read()
+    assert len(a) == len(raw)
+    head_a, words_a, points_a = split_words(a, ext, n_props)
+    head_b, words_b, points_b = split_words(raw, ext, n_props)
+    assert head_a == head_b and np.array_equal(points_a, points_b)
+    assert np.array_equal(words_a[~points_a], words_b[~points_b])     # counts, seeds, NaN, inf
+    ulps = np.abs(ordered(words_a[points_a]) - ordered(words_b[points_b]))
+    print(f'{name} compress {compress}: {count} streamlines, {int((ulps != 0).sum())} of '
+          f'{len(ulps)} point words differ from the existing path, largest {int(ulps.max())} ulp')
+    assert ulps.max() <= 1
+    if ext == '.trk':
+        loaded, info = sio.load_trk(direct)
+        assert info['nb_streamlines'] == len(loaded) == count
+        assert loaded.data_per_streamline['seeds'].shape == (count, 3)
+    else:
+        loaded, info = sio.load_tck(direct)
+        assert int(info['count']) == len(loaded) == count
+    if compress == 0.0:
+        assert [len(s) for s in loaded.streamlines] == list(z['out_lengths'])
+
+
+@pytest.mark.gpu
+def test_ttl_track_direct_output_writes_the_files_of_the_default_run(tmp_path, monkeypatch):
+    from test_runners import _write_agent, _write_inputs
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.runners import ttl_track
+    from tracktolearn_amd.tracking.tracker import Tracker
+    paths, aff = _write_inputs(tmp_path, D=24)
+    agent_dir, hp = _write_agent(tmp_path, 7 * 45 + 3 * 4)
+    calls = []
+    real_track, real_to_file = Tracker.track, Tracker.track_to_file
+    monkeypatch.setattr(Tracker, 'track',
+                        lambda self, *a: calls.append('track') or real_track(self, *a))
+    monkeypatch.setattr(Tracker, 'track_to_file',
+                        lambda self, *a: calls.append('file') or real_to_file(self, *a))
+    for ext in ('.trk', '.tck'):
+        files = {}
+        for flag in ([], ['--direct_output']):
+            out = str(tmp_path / ('direct' if flag else 'default')) + ext
+            del calls[:]
+            ttl_track.main([paths['odf'], paths['seed'], paths['mask'], out, '--agent',
+                            agent_dir, '--hyperparameters', hp, '--n_actor', '2000',
+                            '--min_length', '2', '--max_length', '30', '--rng_seed', '3',
+                            '--save_seeds', '--compress', '0.1'] + flag)
+            assert calls == (['file'] if flag else ['track'])
+            files[bool(flag)] = open(out, 'rb').read()
+            loaded, info = (sio.load_trk if ext == '.trk' else sio.load_tck)(out)
+            n = int(info['nb_streamlines'] if ext == '.trk' else info['count'])
+            assert n == len(loaded) > 50
+        assert len(files[True]) == len(files[False])
+        n_props = 3 if ext == '.trk' else 0
+        head_a, words_a, points_a = split_words(files[False], ext, n_props)
+        head_b, words_b, points_b = split_words(files[True], ext, n_props)
+        assert head_a == head_b and np.array_equal(points_a, points_b)
+        assert np.array_equal(words_a[~points_a], words_b[~points_b])
+        ulps = np.abs(ordered(words_a[points_a]) - ordered(words_b[points_b]))
+        assert ulps.max() <= 1

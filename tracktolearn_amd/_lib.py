@@ -26,6 +26,7 @@ MODE_F32NORM = 2
 ORDER_ACTIVE = 0
 ORDER_PARTITION = 1
 ORDER_BY_POSITION = C.c_void_p(1)      # TTL_ORDER_BY_POSITION (ttl_env_reset)
+TRACT_FILE_TRK, TRACT_FILE_TCK = 0, 1
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4
 
 
@@ -92,6 +93,22 @@ class ColsumSeg(C.Structure):
         ('out', C.c_void_p),
         ('scale', C.c_float),
         ('accumulate', C.c_int32),
+    ]
+
+
+class TractFileDesc(C.Structure):
+    """struct ttl_tract_file_desc (include/ttl_hip.h): a file body's layout
+    and point arithmetic."""
+    _fields_ = [
+        ('format', C.c_int32),
+        ('n_props', C.c_int32),
+        ('has_pre', C.c_int32),
+        ('n_maps', C.c_int32),
+        ('has_post', C.c_int32),
+        ('reserved', C.c_int32),
+        ('pre_scale', C.c_double),
+        ('maps', (C.c_double * 12) * 2),
+        ('post_scale', C.c_double * 3),
     ]
 
 
@@ -182,6 +199,10 @@ SYMBOLS = {
     'ttl_tract_emit': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    'ttl_tract_file_words': (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int64]),
+    'ttl_tract_emit_file': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(TractFileDesc), C.c_void_p, C.c_void_p]),
     # ---- include/ttl_learner.h
     'ttl_thin_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

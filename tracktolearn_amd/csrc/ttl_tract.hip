@@ -1,11 +1,12 @@
 // ttl_tract.hip -- the tracker's output stage on the device: the
 // arc-length filter of TrackToLearn/tracking/tracker.py:120-121, the greedy
 // linearisation of tractogram.compress_streamline and the ragged pack of what
-// survives; part of libttl_hip.so.  Two kernels over the env's history buffer,
+// survives; part of libttl_hip.so.  Kernels over the env's history buffer,
 // one wavefront per streamline each, with an exclusive prefix sum (the
-// caller's) between them:
-//   k_tract_select  kept length, float64 arc, accept, survivor bitmask + count
-//   k_tract_emit    survivors -> packed points, compacted counts and rows
+// caller's) between select and emit:
+//   k_tract_select     kept length, float64 arc, accept, survivor bitmask + count
+//   k_tract_emit       survivors -> packed points, compacted counts and rows
+//   k_tract_emit_file  survivors -> the .trk / .tck records of the batch
 // All float64 arithmetic is plain IEEE (no fused multiply-add), in the order
 // include/ttl_hip.h states.
 #include "ttl_internal.h"
@@ -191,6 +192,89 @@ __global__ __launch_bounds__(BLOCK) void k_tract_emit(
         dst += 3 * c;
     }
 }
+// One point through the descriptor's steps (include/ttl_hip.h); d is uniform over the grid.
+__device__ __forceinline__ void file_point(const ttl_tract_file_desc &d, float x, float y,
+                                           float z, unsigned int out[3]) {
+    double v[3];
+    if (d.has_pre) {
+        const float t[3] = {x + 0.5f, y + 0.5f, z + 0.5f};
+        for (int c = 0; c < 3; ++c) v[c] = (double)(float)((double)t[c] * d.pre_scale);
+    } else {
+        v[0] = (double)x, v[1] = (double)y, v[2] = (double)z;
+    }
+    for (int m = 0; m < d.n_maps; ++m) {
+        const double *a = d.maps[m];
+        double o[3];
+        for (int i = 0; i < 3; ++i)
+            o[i] = ((v[0] * a[4 * i] + v[1] * a[4 * i + 1]) + v[2] * a[4 * i + 2]) + a[4 * i + 3];
+        v[0] = o[0], v[1] = o[1], v[2] = o[2];
+    }
+    if (d.has_post)
+        for (int c = 0; c < 3; ++c) v[c] = (v[c] + 0.5) * d.post_scale[c];
+    for (int c = 0; c < 3; ++c) out[c] = __float_as_uint((float)v[c]);
+}
+
+// k_tract_emit writing file records (TTL_HAS_TRACT_FILE).  Per 64-point word of the mask
+// the survivors are staged in the LDS (a straight copy word with loads along the row, any
+// other by the survivors themselves), lane r converts survivor r in place, and the stores
+// run along the body one dword per lane.
+__global__ __launch_bounds__(BLOCK) void k_tract_emit_file(
+    const float *__restrict__ hist, long long row_pitch, int n, const int *__restrict__ counts,
+    const int *__restrict__ accepted, const long long *__restrict__ count_ends,
+    const long long *__restrict__ accept_ends, const unsigned long long *__restrict__ mask,
+    int nwords, const double *__restrict__ seeds, const ttl_tract_file_desc d,
+    unsigned int *__restrict__ words_out) {
+    __shared__ unsigned int pack[WAVES * 192];
+    const int i = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (i >= n || !accepted[i]) return;
+    const int lane = threadIdx.x & 63;
+    const int count = counts[i];
+    const long long k = accept_ends[i] - 1;
+    const long long b = count_ends[i] - count;
+    const bool trk = d.format == TTL_TRACT_FILE_TRK;
+    const int P = trk ? d.n_props : 0;
+    unsigned int *dst = words_out + (trk ? k * (1 + P) + 3 * b : 3 * (b + k));
+    if (trk) {
+        if (lane == 0) dst[0] = (unsigned int)count;
+        ++dst;
+    }
+    const unsigned int *src = (const unsigned int *)hist + (size_t)i * (size_t)row_pitch;
+    const unsigned long long *mrow = mask + (size_t)i * (size_t)nwords;
+    unsigned int *s = pack + (threadIdx.x >> 6) * 192;
+    for (int w = 0; w < nwords; ++w) {
+        const unsigned long long word = mrow[w];
+        if (word == 0ull) continue;
+        const int c = __popcll(word);
+        const unsigned int *from = src + (size_t)w * 192;
+        if ((word & (word + 1ull)) == 0ull) {
+            for (int f = lane; f < 3 * c; f += 64) s[f] = from[f];
+        } else if ((word >> lane) & 1ull) {
+            const int r = __popcll(word & ((1ull << lane) - 1ull));
+            s[3 * r] = from[3 * lane];
+            s[3 * r + 1] = from[3 * lane + 1];
+            s[3 * r + 2] = from[3 * lane + 2];
+        }
+        wave_sync();
+        if (lane < c) {          // a lane reads and writes its own three words only
+            unsigned int q[3];
+            file_point(d, __uint_as_float(s[3 * lane]), __uint_as_float(s[3 * lane + 1]),
+                       __uint_as_float(s[3 * lane + 2]), q);
+            s[3 * lane] = q[0];
+            s[3 * lane + 1] = q[1];
+            s[3 * lane + 2] = q[2];
+        }
+        wave_sync();
+        for (int f = lane; f < 3 * c; f += 64) dst[f] = s[f];
+        wave_sync();
+        dst += 3 * c;
+    }
+    if (lane < 3) {
+        if (!trk)
+            dst[lane] = 0x7fc00000u;
+        else if (P == 3)
+            dst[lane] = __float_as_uint((float)(seeds[3 * (size_t)i + lane] - 0.5));
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -248,6 +332,42 @@ int ttl_tract_emit(const float *history, int64_t row_pitch, int32_t n, const int
                        (const unsigned long long *)mask,
                        ttl_tract_mask_words(row_pitch), points_out, (long long *)counts_out,
                        rows_out);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+int64_t ttl_tract_file_words(int32_t format, int32_t n_props, int64_t k, int64_t M) {
+    if ((n_props != 0 && n_props != 3) || k < 0 || M < 0) return -1;
+    if (format == TTL_TRACT_FILE_TRK) return k * (1 + n_props) + 3 * M;
+    if (format == TTL_TRACT_FILE_TCK) return 3 * (M + k);
+    return -1;
+}
+
+int ttl_tract_emit_file(const float *history, int64_t row_pitch, int32_t n, const int32_t *counts,
+                        const int32_t *accepted, const int64_t *count_ends,
+                        const int64_t *accept_ends, const uint64_t *mask, const double *seeds,
+                        const ttl_tract_file_desc *desc, uint32_t *words_out, void *hip_stream) {
+    if (n < 0 || row_pitch < 3 || row_pitch / 3 > INT32_MAX / 4)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: n=%d, row_pitch=%lld", n,
+                    (long long)row_pitch);
+    if (!desc) return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: null descriptor");
+    if (desc->format != TTL_TRACT_FILE_TRK && desc->format != TTL_TRACT_FILE_TCK)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: unknown format %d", desc->format);
+    if (desc->n_props != 0 && desc->n_props != 3)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: n_props=%d (0 or 3)", desc->n_props);
+    if (desc->n_props == 3 && !seeds)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: n_props=3 without seeds");
+    if (desc->n_maps < 0 || desc->n_maps > 2)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: n_maps=%d (at most 2)", desc->n_maps);
+    if (n == 0) return TTL_OK;
+    // words_out may be null when no row is accepted; the kernel then stores nothing
+    if (!history || !counts || !accepted || !count_ends || !accept_ends || !mask)
+        return fail(TTL_ERR_INVALID, "ttl_tract_emit_file: null argument");
+    hipLaunchKernelGGL(k_tract_emit_file, dim3((n + WAVES - 1) / WAVES), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, history, (long long)row_pitch, n, counts, accepted,
+                       (const long long *)count_ends, (const long long *)accept_ends,
+                       (const unsigned long long *)mask, ttl_tract_mask_words(row_pitch), seeds,
+                       *desc, words_out);
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

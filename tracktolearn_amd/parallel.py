@@ -142,6 +142,57 @@ def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     return points, counts, rows.to(torch.int64)
 
 
+def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=None,
+                       tol_error=0.0, max_segment_length=10.0):
+    """``select_tracts`` whose pack writes the batch's file body instead of the
+    packed points: ``desc`` is an ``io.streamlines.BodyDesc``, ``seeds`` the
+    (n, 3) float64 seeds by input row (needed when ``desc.n_props == 3``).
+    Returns (words int32 -- the 4-byte words of the body, on the input's
+    device --, accepted rows k, points M).  On the GPU the same
+    ``ttl_tract_select``, scans and synchronising copy, then
+    ``ttl_tract_emit_file``; host tensors take ``_select_tracts_host`` and
+    ``io.streamlines.packed_body``, the kernel's specification."""
+    from tracktolearn_amd.io.streamlines import packed_body
+    n = int(history.shape[0])
+    dev = history.device
+    if desc.n_props == 3 and seeds is None:
+        raise ValueError('n_props == 3 needs the seeds')
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int32, device=dev), 0, 0
+    if not history.is_cuda:
+        points, counts, rows = _select_tracts_host(history, lengths, flags, min_arc, max_arc,
+                                                   tol_error, max_segment_length)
+        kept = None if seeds is None else \
+            np.asarray(seeds, dtype=np.float64).reshape(-1, 3)[rows.numpy()]
+        words = packed_body(points.numpy(), counts.numpy(), kept, desc)
+        return torch.from_numpy(words.view(np.int32)), len(counts), len(points)
+    import ctypes as C
+    from tracktolearn_amd import _lib
+    from tracktolearn_amd.environments.env import _raw_stream
+    lib = _lib.load()
+    stream = C.c_void_p(_raw_stream(dev.index or 0))
+    hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
+                                      tol_error, max_segment_length)
+    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64),
+            torch.cumsum(sel[1], 0, dtype=torch.int64))
+    total, k = torch.stack((ends[0][-1], ends[1][-1])).tolist()   # the one synchronising copy
+    c_desc = desc.to_c()
+    size = lib.ttl_tract_file_words(c_desc.format, c_desc.n_props, k, total)
+    if size < 0:
+        raise ValueError('format {} with {} properties is not a file body'.format(
+            c_desc.format, c_desc.n_props))
+    words = torch.empty(size, dtype=torch.int32, device=dev)
+    if seeds is not None:
+        seeds = torch.as_tensor(seeds, dtype=torch.float64).to(dev).reshape(n, 3).contiguous()
+    if k:
+        _lib.check(lib.ttl_tract_emit_file(
+            hist.data_ptr(), hist.stride(0), n, sel[0].data_ptr(), sel[1].data_ptr(),
+            ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(),
+            seeds.data_ptr() if seeds is not None else None, C.byref(c_desc),
+            words.data_ptr(), stream), 'ttl_tract_emit_file')
+    return words, k, total
+
+
 def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
                         max_segment_length):
     from tracktolearn_amd.tractogram import compress_streamline

@@ -6,7 +6,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--sh_basis B] [--compress T] [-f] [--save_seeds] [--agent DIR]
         [--hyperparameters JSON] [--n_actor N] [--npv N] [--min_length m]
         [--max_length M] [--noise s] [--keyed_noise] [--fa_map F]
-        [--binary_stopping_threshold t] [--rng_seed S]
+        [--binary_stopping_threshold t] [--rng_seed S] [--direct_output]
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -76,6 +76,7 @@ class TrackToLearnTrack(object):
         for key in _PASS_THROUGH:
             setattr(self, key, track_dto[key])
         self.input_wm = track_dto.get('input_wm', False)
+        self.direct_output = bool(track_dto.get('direct_output', False))
         self.reference_file = self.in_mask
         self.compress = track_dto['compress'] or 0.0
         # tracking never computes rewards and never consults the oracle
@@ -153,14 +154,20 @@ class TrackToLearnTrack(object):
             # (keyed noise needs no generator: every shard resets with its global
             # start offset, so the streamline ids are those of the one-GPU run)
             env.noise_rng = per_rank_noise_rng(self.random_seed, tracker.rank)
-        tractogram = tracker.track(env, detect_format(self.out_tractogram))
-        if tracker.rank != 0:
-            for _ in tractogram:        # take part in the collectives only
-                pass
-            return
         header = sio.create_tractogram_header(
             ref_img.affine, ref_img.shape[:3], ref_img.get_zooms()[:3])
-        n = sio.save(tractogram, self.out_tractogram, header=header)
+        if self.direct_output:
+            # the output stage writes the file's records: no per-streamline Python
+            n = tracker.track_to_file(env, self.out_tractogram, header)
+            if tracker.rank != 0:
+                return
+        else:
+            tractogram = tracker.track(env, detect_format(self.out_tractogram))
+            if tracker.rank != 0:
+                for _ in tractogram:        # take part in the collectives only
+                    pass
+                return
+            n = sio.save(tractogram, self.out_tractogram, header=header)
         print('Saved {} streamlines to {}'.format(n, self.out_tractogram))
 
 
@@ -188,6 +195,11 @@ def add_out_options(p):
     out_g.add_argument('--save_seeds', action='store_true',
                        help='If set, save the seeds used for the tracking \n '
                             'in the data_per_streamline property.')
+    out_g.add_argument('--direct_output', action='store_true',
+                       help='Build the file records on the GPU and write each '
+                            'seed batch with one write,\ninstead of one Python '
+                            'object per streamline. Points may differ from the\n'
+                            'default in the last float32 bit.')
     return out_g
 
 

@@ -49,6 +49,7 @@ class TrackToLearnValidation(object):
         # --fa_map implies keyed noise: only the in-kernel draw scales by FA
         self.fa_map_file = g.get('fa_map')
         self.keyed_noise = bool(g.get('keyed_noise')) or bool(self.fa_map_file)
+        self.direct_output = bool(g.get('direct_output', False))
         with open(g['hyperparameters'], 'r') as json_file:
             hp = json.load(json_file)
         self.algorithm = hp['algorithm']
@@ -126,13 +127,16 @@ class TrackToLearnValidation(object):
         os.makedirs(self.experiment_path, exist_ok=True)
         out = join(self.experiment_path, 'tractogram_{}_{}_{}.tck'.format(
             self.experiment, self.id, env.subject_id))
-        tractogram = tracker.track(env, detect_format(out))
         ref = env.reference if isinstance(env.reference, dict) else {}
         shape = ref.get('shape', env.tracking_mask.data.shape[:3])
         zooms = (float(tracking_voxel_size),) * 3
         header = sio.create_tractogram_header(
             ref.get('affine', env.affine_vox2rasmm), shape, zooms)
-        n = sio.save(tractogram, out, header=header)
+        if self.direct_output:
+            n = tracker.track_to_file(env, out, header)
+        else:
+            tractogram = tracker.track(env, detect_format(out))
+            n = sio.save(tractogram, out, header=header)
         print('Saved {} streamlines to {}'.format(n, out))
         return out
 
@@ -154,6 +158,9 @@ def add_valid_args(parser):
                         help='FA map (.nii.gz on the subject\'s grid) to '
                              'influence STD for probabilistic tracking: '
                              'std = (1 - FA) * noise. Implies --keyed_noise.')
+    parser.add_argument('--direct_output', action='store_true',
+                        help='Build the file records on the GPU and write each '
+                             'seed batch with one write.')
 
 
 def parse_args(argv=None):

@@ -6,7 +6,9 @@ generator (length filter, optional compression, voxel->file space) runs on the
 GPU over the whole finished batch (``parallel.select_tracts``): only the points
 that end up in the file are downloaded.  ``device_output=False`` keeps the
 earlier path (torch length filter on the device, compression per streamline on
-the host) as the comparison baseline.
+the host) as the comparison baseline.  ``track_to_file`` goes one step
+further: the output stage writes the file's records and no per-streamline
+object is made at all.
 """
 from collections import defaultdict
 
@@ -189,36 +191,108 @@ class Tracker(object):
                 seed_dict = {'seeds': seed - 0.5}
             yield TractogramItem(streamline, seed_dict, {})
 
+    def _tracked_batches(self, env):
+        """Tracks the seeds a batch (this rank's shard of it) at a time; yields
+        once per batch, the finished batch in the env's buffers."""
+        batch_size = self.n_actor
+        for start in tqdm(range(0, len(env.seeds), batch_size),
+                          disable=self.rank != 0):
+            end = min(start + batch_size, len(env.seeds))
+            if self.group_size > 1:
+                from tracktolearn_amd.parallel import shard_bounds
+                lo, hi = shard_bounds(end - start, self.rank, self.group_size)
+                start, end = start + lo, start + hi
+            if end > start:
+                state = env.reset(start, end)
+                self.alg.validation_episode(state, env, self.prob)
+            else:           # an empty shard still joins the collectives
+                env._n_total = 0
+            yield
+
     def track(self, env, tracts_format):
         """Tracking only; a lazy tractogram whose iteration does the work
         (tracker.py:62-150).  Streamlines come out in the space the format
         expects: voxmm with corner origin for .trk ((s + 0.5) * voxel size),
         world space for .tck (``s @ A[:3,:3] + A[:3,3]`` as the reference
         writes it)."""
-        batch_size = self.n_actor
         self.alg.agent.eval()
         affine = env.affine_vox2rasmm
         # shuffle so that partial displays of huge tractograms look uniform
         np.random.shuffle(env.seeds)
 
         def tracking_generator():
-            for start in tqdm(range(0, len(env.seeds), batch_size),
-                              disable=self.rank != 0):
-                end = min(start + batch_size, len(env.seeds))
-                if self.group_size > 1:
-                    from tracktolearn_amd.parallel import shard_bounds
-                    lo, hi = shard_bounds(end - start, self.rank, self.group_size)
-                    start, end = start + lo, start + hi
-                if end > start:
-                    state = env.reset(start, end)
-                    self.alg.validation_episode(state, env, self.prob)
-                else:           # an empty shard still joins the collectives
-                    env._n_total = 0
+            for _ in self._tracked_batches(env):
                 yield from self.batch_output(env, tracts_format)
 
         tractogram = LazyTractogram.from_data_func(tracking_generator)
         tractogram.affine_to_rasmm = affine
         return tractogram
+
+    def track_to_file(self, env, path, header=None):
+        """``track`` and ``io.streamlines.save`` in one: the output stage
+        builds each batch's file body on the device (``select_tracts_file``),
+        which is downloaded once and appended with one write -- no
+        per-streamline Python.  With a process group every rank builds its
+        chunk and rank 0 appends them in rank order, the order ``track``
+        yields.  Returns the number of streamlines written (None off rank
+        0).  Seeds are saved (``save_seeds``) in .trk files only; .tck has no
+        properties."""
+        from tracktolearn_amd.io import streamlines as sio
+        fmt = detect_format(path)
+        if fmt is None:
+            raise ValueError('output must be .trk or .tck')
+        self.alg.agent.eval()
+        desc = self.file_desc(env, fmt, header)
+        np.random.shuffle(env.seeds)
+        writer = sio.PackedWriter(path, fmt.EXT, header, desc.n_props) \
+            if self.rank == 0 else None
+        try:
+            for _ in self._tracked_batches(env):
+                words, k = self.batch_body(env, desc)
+                if writer is not None:
+                    writer.append(words, k)
+        finally:
+            if writer is not None:
+                writer.close()
+        return writer.count if writer is not None else None
+
+    def file_desc(self, env, tracts_format, header=None):
+        """The ``io.streamlines.BodyDesc`` of the file ``track`` + ``save``
+        write for this env: the seeds as properties with ``save_seeds``, in
+        .trk only."""
+        from tracktolearn_amd.io import streamlines as sio
+        affine = env.affine_vox2rasmm
+        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
+        n_props = 3 if self.save_seeds and tracts_format is TrkFile else 0
+        return sio.body_desc(tracts_format.EXT, affine, vox_size, header, n_props)
+
+    def batch_body(self, env, desc):
+        """The output stage of ``track_to_file`` over the env's finished
+        batch: (the body's words as a host array, streamlines in it); with a
+        process group every rank's, in rank order, on rank 0 and (None, the
+        count) elsewhere.  One download."""
+        import torch
+        from tracktolearn_amd.parallel import select_tracts_file
+        affine = env.affine_vox2rasmm
+        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
+        n = env._n_total
+        seeds = None
+        if desc.n_props:        # the batch's seeds, uploaded once
+            seeds = torch.from_numpy(np.ascontiguousarray(
+                np.asarray(env.initial_points)[:n], dtype=np.float64).reshape(-1, 3)).to(
+                    env._buf_streamlines.device)
+        words, k, _ = select_tracts_file(
+            env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
+            self.min_length / vox_size, self.max_length / vox_size, desc, seeds,
+            tol_error=self.compress / vox_size if self.compress else 0.0)
+        if self.group_size > 1:
+            from tracktolearn_amd.parallel import (all_gather_counts,
+                                                   gather_ragged_to_root)
+            words, _ = gather_ragged_to_root(words)
+            k = sum(all_gather_counts(k))
+            if self.rank != 0:
+                return None, k
+        return words.cpu().numpy(), k
 
     def track_and_train(self, env):
         """One training "epoch": n_actor random seeds tracked while learning
