@@ -176,6 +176,42 @@ __device__ __forceinline__ f4 lerp4(f4 lo, f4 hi, float d) {
 __device__ __forceinline__ f4 sel4(bool c, f4 a, f4 b) {
     return f4{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w};
 }
+// PINNED: the blends with every fused operation stated.  The file leaves
+// contraction to the compiler, which is free to fuse `x * a + y * b` either way
+// and does so differently per instantiation: the separate-tail kernels
+// (TTL_STATE_KERNEL=3) came out a last bit away from the merged-tail ones in
+// the fourth float of a column.  These state the order the merged-tail kernels
+// are compiled to (found by matching their rows bit for bit at C = 8, 28, 45
+// and 64; tests/test_state_gather_reference.py holds the two kernels to equal
+// bits, so a compiler that fuses the merged-tail kernels otherwise is noticed):
+//   blend of a centre slice (f, f+1):  fma(v11, fma(v10, fma(v01, v00 w00)))
+//   blend of an outer slice (f-1, f+2): fma(v11, fma(v10, fma(v00, v01 w01)))
+//   centre and plus lerp: fma(lo, 1 - d, hi d);  minus lerp: fma(hi, d, lo (1 - d))
+// The merged-tail kernels themselves (PINNED = false) keep the plain source.
+// To re-derive the order after a compiler update (the test above then fails):
+// benchmarks/micro/fusion_order_probe.py prints, per stencil point, the order
+// that reproduces the merged-tail kernels' rows; restate it here.
+// k_state_dd<4, 4, false, false> is also what the default knob launches for
+// C = 1..3 (the merged tail needs 4 coefficients): before it was pinned only the
+// fourth float of a column differed, which those records never store.
+__device__ __forceinline__ f4 fma4(f4 a, float w, f4 c) {   // a*w + c, one rounding
+    return f4{__builtin_fmaf(a.x, w, c.x), __builtin_fmaf(a.y, w, c.y),
+              __builtin_fmaf(a.z, w, c.z), __builtin_fmaf(a.w, w, c.w)};
+}
+template <bool PINNED, bool OUTER>
+__device__ __forceinline__ f4 blend(f4 v00, f4 v01, f4 v10, f4 v11, float a0, float a1,
+                                    float b0, float b1) {
+    if (!PINNED) return blend4(v00, v01, v10, v11, a0, a1, b0, b1);
+    f4 r = OUTER ? fma4(v00, a0 * b0, scale4(v01, a0 * b1))
+                 : fma4(v01, a0 * b1, scale4(v00, a0 * b0));
+    r = fma4(v10, a1 * b0, r);
+    return fma4(v11, a1 * b1, r);
+}
+template <bool PINNED, bool MINUS>
+__device__ __forceinline__ f4 lerp(f4 lo, f4 hi, float d) {
+    if (!PINNED) return lerp4(lo, hi, d);
+    return MINUS ? fma4(hi, d, scale4(lo, 1.0f - d)) : fma4(lo, 1.0f - d, scale4(hi, d));
+}
 __device__ __forceinline__ int clipi(int v, int n) { return min(max(v, 0), n - 1); }
 // store the float4 column c..c+3 of one point's C coefficients (the last
 // column of a padded record may be partial).  State rows are only 4-byte
@@ -185,9 +221,15 @@ __device__ __forceinline__ int clipi(int v, int n) { return min(max(v, 0), n - 1
 // store-issue bound otherwise.
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef v4f v4f_dword_aligned __attribute__((aligned(4)));
-// the value lane-1 holds (DPP row_shr:1).  Only used between the last two
-// lanes of one lane group, which never straddle a 16-lane DPP row for group
-// sizes 4, 8, 12, 16; both lanes are active together.
+// the value lane-1 holds (DPP row_shr:1; the first lane of a 16-lane DPP row
+// gets 0, the shift does not cross rows).  Only used between the last two
+// lanes of one lane group, both active together.  Groups of 4, 8 and 16 lanes
+// never straddle a DPP row.  Groups of 12 do: group 2 of a wave is lanes
+// 24..35, and with 9 float4 columns its last lane is lane 32, the first of a
+// row.  for_lanes_per_streamline() therefore gives records of 9 float4s with
+// a partial last column (C = 33, 34, 35) groups of 16; with 10..12 columns
+// the last lane of every group of 12 has its neighbour in its own row
+// (lanes 9..11, 21..23, 33..35, 45..47, 57..59).
 __device__ __forceinline__ float from_prev_lane(float v) {
     return __int_as_float(
         __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false));
@@ -265,7 +307,7 @@ __device__ __forceinline__ void put4(int flavour, float *o, f4 a, int c, int C) 
 // float4 column of the 7 stencil points + this lane's share of the direction
 // block.  (px, py, pz) = newest point, h = the streamline's history, orow = the
 // output row.  Shared by k_state_dd and the fused small-batch kernel.
-template <int LPS, bool LOOP, bool MERGE_TAIL>
+template <int LPS, bool LOOP, bool MERGE_TAIL, bool PINNED = false>
 __device__ __forceinline__ void state_row_dd(const EnvParams &P, float px, float py,
                                              float pz, const float *__restrict__ h, int L,
                                              int sub, float *__restrict__ orow) {
@@ -344,50 +386,50 @@ __device__ __forceinline__ void state_row_dd(const EnvParams &P, float px, float
         {
             f4 b0 = zero, b3 = zero;
             if (xdn)
-                b0 = blend4(ld4(vol, TTL_VOX(x0, y1, z1) + cb), ld4(vol, TTL_VOX(x0, y1, z2) + cb),
+                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x0, y1, z1) + cb), ld4(vol, TTL_VOX(x0, y1, z2) + cb),
                             ld4(vol, TTL_VOX(x0, y2, z1) + cb), ld4(vol, TTL_VOX(x0, y2, z2) + cb),
                             ey, dy, ez, dz);
             if (xup)
-                b3 = blend4(ld4(vol, TTL_VOX(x3, y1, z1) + cb), ld4(vol, TTL_VOX(x3, y1, z2) + cb),
+                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x3, y1, z1) + cb), ld4(vol, TTL_VOX(x3, y1, z2) + cb),
                             ld4(vol, TTL_VOX(x3, y2, z1) + cb), ld4(vol, TTL_VOX(x3, y2, z2) + cb),
                             ey, dy, ez, dz);
-            const f4 b1 = blend4(v000, v001, v010, v011, ey, dy, ez, dz);
-            const f4 b2 = blend4(v100, v101, v110, v111, ey, dy, ez, dz);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 0 * C + c, lerp4(b1, b2, dx), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 1 * C + c, lerp4(sel4(xup, b2, b1), sel4(xup, b3, b2), dxp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 4 * C + c, lerp4(sel4(xdn, b0, b1), sel4(xdn, b1, b2), dxm), c, C);
+            const f4 b1 = blend<PINNED, false>(v000, v001, v010, v011, ey, dy, ez, dz);
+            const f4 b2 = blend<PINNED, false>(v100, v101, v110, v111, ey, dy, ez, dz);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 0 * C + c, lerp<PINNED, false>(b1, b2, dx), c, C);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 1 * C + c, lerp<PINNED, false>(sel4(xup, b2, b1), sel4(xup, b3, b2), dxp), c, C);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 4 * C + c, lerp<PINNED, true>(sel4(xdn, b0, b1), sel4(xdn, b1, b2), dxm), c, C);
         }
         // --- y axis: slices blended over (x, z) ---
         {
             f4 b0 = zero, b3 = zero;
             if (ydn)
-                b0 = blend4(ld4(vol, TTL_VOX(x1, y0, z1) + cb), ld4(vol, TTL_VOX(x1, y0, z2) + cb),
+                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y0, z1) + cb), ld4(vol, TTL_VOX(x1, y0, z2) + cb),
                             ld4(vol, TTL_VOX(x2, y0, z1) + cb), ld4(vol, TTL_VOX(x2, y0, z2) + cb),
                             ex, dx, ez, dz);
             if (yup)
-                b3 = blend4(ld4(vol, TTL_VOX(x1, y3, z1) + cb), ld4(vol, TTL_VOX(x1, y3, z2) + cb),
+                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y3, z1) + cb), ld4(vol, TTL_VOX(x1, y3, z2) + cb),
                             ld4(vol, TTL_VOX(x2, y3, z1) + cb), ld4(vol, TTL_VOX(x2, y3, z2) + cb),
                             ex, dx, ez, dz);
-            const f4 b1 = blend4(v000, v001, v100, v101, ex, dx, ez, dz);
-            const f4 b2 = blend4(v010, v011, v110, v111, ex, dx, ez, dz);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 2 * C + c, lerp4(sel4(yup, b2, b1), sel4(yup, b3, b2), dyp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 5 * C + c, lerp4(sel4(ydn, b0, b1), sel4(ydn, b1, b2), dym), c, C);
+            const f4 b1 = blend<PINNED, false>(v000, v001, v100, v101, ex, dx, ez, dz);
+            const f4 b2 = blend<PINNED, false>(v010, v011, v110, v111, ex, dx, ez, dz);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 2 * C + c, lerp<PINNED, false>(sel4(yup, b2, b1), sel4(yup, b3, b2), dyp), c, C);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 5 * C + c, lerp<PINNED, true>(sel4(ydn, b0, b1), sel4(ydn, b1, b2), dym), c, C);
         }
         // --- z axis: slices blended over (x, y) ---
         {
             f4 b0 = zero, b3 = zero;
             if (zdn)
-                b0 = blend4(ld4(vol, TTL_VOX(x1, y1, z0) + cb), ld4(vol, TTL_VOX(x1, y2, z0) + cb),
+                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y1, z0) + cb), ld4(vol, TTL_VOX(x1, y2, z0) + cb),
                             ld4(vol, TTL_VOX(x2, y1, z0) + cb), ld4(vol, TTL_VOX(x2, y2, z0) + cb),
                             ex, dx, ey, dy);
             if (zup)
-                b3 = blend4(ld4(vol, TTL_VOX(x1, y1, z3) + cb), ld4(vol, TTL_VOX(x1, y2, z3) + cb),
+                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y1, z3) + cb), ld4(vol, TTL_VOX(x1, y2, z3) + cb),
                             ld4(vol, TTL_VOX(x2, y1, z3) + cb), ld4(vol, TTL_VOX(x2, y2, z3) + cb),
                             ex, dx, ey, dy);
-            const f4 b1 = blend4(v000, v010, v100, v110, ex, dx, ey, dy);
-            const f4 b2 = blend4(v001, v011, v101, v111, ex, dx, ey, dy);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 3 * C + c, lerp4(sel4(zup, b2, b1), sel4(zup, b3, b2), dzp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 6 * C + c, lerp4(sel4(zdn, b0, b1), sel4(zdn, b1, b2), dzm), c, C);
+            const f4 b1 = blend<PINNED, false>(v000, v010, v100, v110, ex, dx, ey, dy);
+            const f4 b2 = blend<PINNED, false>(v001, v011, v101, v111, ex, dx, ey, dy);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 3 * C + c, lerp<PINNED, false>(sel4(zup, b2, b1), sel4(zup, b3, b2), dzp), c, C);
+            put4<MERGE_TAIL>(P.store_flavour, orow + 6 * C + c, lerp<PINNED, true>(sel4(zdn, b0, b1), sel4(zdn, b1, b2), dzm), c, C);
         }
         if (!LOOP) break;
     }
@@ -488,8 +530,10 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_state_dd(
             py = h[(L - 1) * 3 + 1];
             pz = h[(L - 1) * 3 + 2];
         }
-        state_row_dd<LPS, LOOP, MERGE_TAIL>(P, px, py, pz, h, L, sub,
-                                            out + (size_t)r * (size_t)pitch);
+        // the separate-tail kernels of one-column-per-lane records state their fused
+        // operations (see blend<>): the same bits as the merged-tail kernels
+        state_row_dd<LPS, LOOP, MERGE_TAIL, !MERGE_TAIL && !LOOP>(
+            P, px, py, pz, h, L, sub, out + (size_t)r * (size_t)pitch);
     }
 }
 
@@ -603,9 +647,12 @@ __global__ __launch_bounds__(BLOCK, 4) void k_prefix_state_fr(
 template <int MAX_LPS, class F>
 void for_lanes_per_streamline(const EnvParams &P, F &&f) {
     const int C4 = P.coef_pitch >> 2;
+    // 9 columns, the last one partial: the merged tail store of a group of 12
+    // would reach across a DPP row (from_prev_lane), so such records take 16
+    const bool tail_straddles = C4 == 9 && (P.n_coef & 3);
     if (C4 <= 4) f(std::integral_constant<int, 4>{});
     else if (C4 <= 8) f(std::integral_constant<int, 8>{});
-    else if (C4 <= 12) f(std::integral_constant<int, 12>{});
+    else if (C4 <= 12 && !tail_straddles) f(std::integral_constant<int, 12>{});
     else if (MAX_LPS == 16 || C4 <= 16) f(std::integral_constant<int, 16>{});
     else f(std::integral_constant<int, MAX_LPS>{});
 }
