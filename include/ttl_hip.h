@@ -411,6 +411,25 @@ TTL_API int ttl_env_refresh_processing_order(ttl_env *env, void *hip_stream);
  * volume has too many bricks for it. */
 TTL_API int ttl_env_order_slots(ttl_env *env, int32_t *n_slots_out, int32_t *instep_out);
 
+/* Riders of the gather launch (TTL_HAS_TAIL_RIDERS).  Two parts of a step
+ * with the one-launch tail are needed by nothing before the next step: the order
+ * scatter of an in-step re-bucket and the row maps (continue_idx of the next step,
+ * row_dest, lengths, the stopped list).  They run as extra workgroups behind the state
+ * gather's own, inside its launch, and are complete when the step's launches are.
+ * TTL_TAIL_RIDERS in the environment at ttl_env_create: 1 (default) both, 0 none (the
+ * separate launches), 2 / 3 the order scatter / the row maps alone.  *kinds_out: bit 0
+ * the order scatter, bit 1 the row maps, as the knob asks; *last_step_out (may be
+ * NULL): the same bits for what rode in the last ttl_env_step / ttl_env_step_end (0
+ * where that step took another tail, a persistent gather grid, or, for bit 0, was no
+ * re-bucket step or has a brick raster whose scan needs more than 16 KB of LDS).
+ * *order_out (may be NULL; for the tests): the processing order the next step will
+ * read, device int32 [n_slots of ttl_env_order_slots] of active rows with -1 for a
+ * hole, owned by the handle and final once the stream has run the last step; NULL
+ * where no order is in use.  Host state only. */
+#define TTL_HAS_TAIL_RIDERS 1
+TTL_API int ttl_env_tail_riders(ttl_env *env, int32_t *kinds_out, int32_t *last_step_out,
+                                const int32_t **order_out);
+
 /* Current continue_idx buffer (device, int32 [n_active]) and, after a step,
  * the active-row -> output-row map (device, int32 [n_active]). */
 TTL_API int ttl_env_view(ttl_env *env, const int32_t **continue_idx,

@@ -907,6 +907,11 @@ __global__ __launch_bounds__(BLOCK) void k_proc_scatter(EnvParams P,
 // writes the next step's order -- proc_next is not written here.  A slot whose
 // streamline stopped gets no bin (and splits the run it sits in, which costs an
 // atomic and nothing else).
+//
+// row_base != null (TTL_TAIL_RIDERS): the row half -- step_map_row, which nothing
+// reads before the next step -- is left to the row-map riders of the gather
+// launch (TailRiders, ttl_internal.h); workgroup 0 stores the scanned block bases
+// for them.  The scan, the count publication and the slot half stay here.
 // ---------------------------------------------------------------------------
 constexpr int TTL_TAIL_MAX_BLOCKS = 4096;
 
@@ -915,7 +920,8 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
     EnvParams P, const int *__restrict__ idx, int *__restrict__ idx_next,
     const int *__restrict__ proc, int *__restrict__ proc_next, int n_active, int n_slots,
     int nb_rows, int order, int n_pts, int *__restrict__ host_word, int seq, int local_sort,
-    int2 *__restrict__ ord_rec, unsigned *__restrict__ bin_count, int nbx, int nby, int nbz) {
+    int2 *__restrict__ ord_rec, unsigned *__restrict__ bin_count, int nbx, int nby, int nbz,
+    int *__restrict__ row_base) {
     __shared__ int s_scan[TTL_TAIL_MAX_BLOCKS];
     __shared__ int s_wave[BLOCK / 64];
     __shared__ unsigned s_key[BLOCK];
@@ -952,8 +958,14 @@ __global__ __launch_bounds__(BLOCK) void k_tail(
     __syncthreads();
     if (blockIdx.x == 0 && tid == 0) step_publish_counts(P, total, n_active, host_word, seq);
     // ---- rows: continue_idx of the next step, lengths, the row maps ----
+    // (row_base: the row-map riders of the gather launch do them, see TailRiders;
+    // they need the scanned bases, which workgroup 0 hands over)
     const int i = blockIdx.x * BLOCK + tid;
-    if (i < n_active) {
+    if (row_base) {
+        if (blockIdx.x == 0)
+            for (int k = 0; k < per; ++k)
+                if (lo + k < nb_rows) row_base[lo + k] = s_scan[lo + k];
+    } else if (i < n_active) {
         const int pos = s_scan[blockIdx.x] + P.rank[i];
         step_map_row(P, i, idx[i], P.stop[i] != 0, pos, total, order, n_pts, idx_next);
     }
@@ -1280,6 +1292,9 @@ struct ttl_env {
     int instep;          // > 0: k_tail steps re-bucket the order by brick on every instep-th step
                          // of an episode (TTL_ORDER_INSTEP); 0: only the host-driven refresh
     int instep_after;    // k_order_scatter behind the gather instead of in front (TTL_ORDER_INSTEP_AFTER)
+    int tail_riders;     // bit 0: the order scatter, bit 1: the row maps of a k_tail step run as
+                         // riders of the gather launch (TTL_TAIL_RIDERS, see TailRiders)
+    int last_riders;     // the same bits: what rode in the last step's gather launch
     int instep_bins;     // bins of the brick raster, 0: too many for the in-step path
     int instep_nb[3];    // the raster
     int2 *ord_rec;       // [n_max] {bin and offset, next row} per slot, k_tail -> k_order_scatter
@@ -1633,6 +1648,12 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
     e->instep_after = 0;
     if (const char *v = getenv("TTL_ORDER_INSTEP_AFTER")) e->instep_after = atoi(v) != 0;
     e->instep_bins = ttl_detail_order_bins(P, e->instep_nb);
+    e->tail_riders = 3;
+    if (const char *v = getenv("TTL_TAIL_RIDERS")) {      // 0: none, 1: both, 2 / 3: one kind (measurement)
+        const int kinds[4] = {0, 3, 1, 2};
+        e->tail_riders = kinds[atoi(v) & 3];
+    }
+    e->last_riders = 0;
     e->length = 0;
     e->n_active = 0;
     e->cur = 0;
@@ -1979,6 +2000,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     const int *proc = env->use_proc ? env->proc[env->proc_cur] : nullptr;
     env->stepped = 1;
     env->last_order = order;
+    env->last_riders = 0;
     int seq = 0;
     int *host_word = ttl_counts_to_host(env, host_counts, s, &seq);
     if (!proc && env->fuse_small && env->state_kernel != 0 &&
@@ -1999,6 +2021,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     // is launched for n_slots slots
     int n_gather = n_active;
     bool rebucket = false;
+    TailRiders riders{};
     const bool fused_tail = proc && env->tail_fused && env->P.slot_rec &&
                             ttl_detail_state_dedupes(env->P, env->state_kernel) &&
                             (env->n_slots < 0 ? n_active : env->n_slots) <= env->tail_fused_max;
@@ -2020,16 +2043,42 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
         // on the way, k_order_scatter writes the next step's order from them
         rebucket = ttl_order_instep_on(env, env->n_slots) && (n_pts - 1) % env->instep == 0;
         unsigned *cnt = env->ord_count[env->ord_parity];
+        // what the gather launch can carry behind its own workgroups (TTL_TAIL_RIDERS):
+        // a grid of one workgroup per block, and LDS that leaves its occupancy alone
+        const int ride = env->P.persist_rows > 0 ? 0 : env->tail_riders;
+        if ((ride & 1) && rebucket && !env->instep_after &&
+            ttl_detail_order_scatter_lds(env->instep_bins) <= TTL_RIDER_MAX_LDS) {
+            riders.n_scatter = (env->n_slots + TTL_INSTEP_CHUNK - 1) / TTL_INSTEP_CHUNK;
+            riders.rec = env->ord_rec;
+            riders.count = cnt;
+            riders.count_other = env->ord_count[env->ord_parity ^ 1];
+            riders.order_out = env->proc[env->proc_cur ^ 1];
+            riders.n_slots = env->n_slots;
+            riders.bins = env->instep_bins;
+        }
+        // (the scanned bases go where the two-kernel tail keeps its slot counts:
+        // a k_tail step has no use for them)
+        int *row_base = nullptr;
+        if (ride & 2) {
+            row_base = env->P.proc_counts;
+            riders.n_row_blocks = nb;
+            riders.row_base = row_base;
+            riders.idx = idx;
+            riders.idx_next = idx_next;
+            riders.n_active = n_active;
+            riders.order = order;
+            riders.n_pts = n_pts;
+        }
         if (rebucket)
             hipLaunchKernelGGL(k_tail<true>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
                                proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
                                order, n_pts, host_word, seq, env->local_sort, env->ord_rec, cnt,
-                               env->instep_nb[0], env->instep_nb[1], env->instep_nb[2]);
+                               env->instep_nb[0], env->instep_nb[1], env->instep_nb[2], row_base);
         else
             hipLaunchKernelGGL(k_tail<false>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
                                proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
                                order, n_pts, host_word, seq, env->local_sort, nullptr, nullptr,
-                               0, 0, 0);
+                               0, 0, 0, row_base);
     } else {
         hipLaunchKernelGGL(k_prefix, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, idx_next,
                            proc, n_active, nb, order, n_pts, host_word, seq);
@@ -2038,7 +2087,7 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     HIP_TRY(hipGetLastError());
     HIP_TRY(ttl_counts_after_tail(env, host_counts, host_word, s));
     if (fused_tail) {
-        if (rebucket && !env->instep_after) {
+        if (rebucket && !env->instep_after && !riders.n_scatter) {
             const int rc = ttl_order_instep_scatter(env, s);
             if (rc != TTL_OK) return rc;
         }
@@ -2056,10 +2105,18 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     }
     prof_mark(env, 2, 0, s);
     log_gather_rows(n_active);
-    const int rc = ttl_detail_launch_state(env->P, env->state_kernel, idx, env->P.row_dest,
-                                           proc, n_gather, n_pts, state_out, state_pitch, s);
+    const bool ride = riders.n_scatter || riders.n_row_blocks;
+    const int rc = ttl_detail_launch_state(env->P, env->state_kernel, idx, env->P.row_dest, proc,
+                                           n_gather, n_pts, state_out, state_pitch, s,
+                                           ride ? &riders : nullptr);
     prof_mark(env, 2, 1, s);
-    if (rc == TTL_OK && rebucket && env->instep_after) return ttl_order_instep_scatter(env, s);
+    if (rc != TTL_OK) return rc;
+    env->last_riders = (riders.n_scatter ? 1 : 0) | (riders.n_row_blocks ? 2 : 0);
+    if (riders.n_scatter) {     // the order is rebuilt: what ttl_order_instep_scatter notes
+        env->ord_parity ^= 1;
+        env->n_slots = -1;
+    }
+    if (rebucket && env->instep_after) return ttl_order_instep_scatter(env, s);
     return rc;
 }
 
@@ -2376,6 +2433,17 @@ int ttl_env_order_slots(ttl_env *env, int32_t *n_slots_out, int32_t *instep_out)
     const int slots = !env->use_proc ? 0 : env->n_slots < 0 ? env->n_active : env->n_slots;
     *n_slots_out = slots;
     if (instep_out) *instep_out = ttl_order_instep_on(env, slots) ? env->instep : 0;
+    return TTL_OK;
+}
+
+int ttl_env_tail_riders(ttl_env *env, int32_t *kinds_out, int32_t *last_step_out,
+                        const int32_t **order_out) {
+    if (!env || !kinds_out) return fail(TTL_ERR_INVALID, "ttl_env_tail_riders: null argument");
+    *kinds_out = env->tail_riders;
+    if (last_step_out) *last_step_out = env->last_riders;
+    // (a step leaves the next order in the other buffer; the harvest swaps them)
+    if (order_out)
+        *order_out = !env->use_proc ? nullptr : env->proc[env->proc_cur ^ (env->stepped ? 1 : 0)];
     return TTL_OK;
 }
 

@@ -157,11 +157,131 @@ inline size_t ttl_detail_sh_records(const EnvParams &P) {
            ((P.sh_dim[2] + 3) / 4) * 64;
 }
 
+// ---------------------------------------------------------------------------
+// Second half of the in-step re-bucket (TTL_ORDER_INSTEP), one workgroup of
+// TTL_BLOCK threads for TTL_INSTEP_CHUNK slots; stated once for k_order_scatter
+// (ttl_order.hip) and for the order-scatter rider of the gather launch
+// (ttl_state.hip).  k_tail<true> has counted the bricks and left per slot
+// rec[j] = {bin << TTL_INSTEP_OFF_BITS | offset inside the bin, or -1; next row
+// or -1} (so: orders of at most 2^18 slots, which is the default ceiling of the
+// one-launch tail, and bins < 2^14).  Workgroup `wg` of `n_wg` scans the bin
+// counts itself through LDS (nobody waits for anybody) and drops its slots'
+// rows at cursor[bin] + offset: the dense order of the survivors in
+// out[0 .. n_slots), -1 behind them.  The workgroups also share the clearing of
+// the OTHER count buffer, which the next re-bucket counts into.
+// s_bin = (bins + TTL_BLOCK / 64) words of LDS: counts -> cursors, wave totals.
+// ---------------------------------------------------------------------------
+constexpr int TTL_INSTEP_OFF_BITS = 18;
+constexpr int TTL_INSTEP_ITEMS = 4;     // slots per thread: a quarter of the workgroups scan
+constexpr int TTL_INSTEP_CHUNK = TTL_BLOCK * TTL_INSTEP_ITEMS;
+inline size_t ttl_detail_order_scatter_lds(int bins) {
+    return ((size_t)bins + TTL_BLOCK / 64) * sizeof(unsigned);
+}
+__device__ __forceinline__ void order_scatter_block(unsigned *s_bin, int wg, int n_wg,
+                                                    const int2 *__restrict__ rec, int n_slots,
+                                                    const unsigned *__restrict__ gcount,
+                                                    unsigned *__restrict__ gcount_other,
+                                                    int bins, int *__restrict__ out) {
+    constexpr int BLOCK = TTL_BLOCK, ITEMS = TTL_INSTEP_ITEMS;
+    unsigned *s_wave = s_bin + bins;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the slots' records first: their latency hides behind the scan
+    const int base = wg * TTL_INSTEP_CHUNK + tid;
+    int2 r[ITEMS];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = base + k * BLOCK;
+        r[k] = j < n_slots ? rec[j] : int2{-1, -1};
+    }
+    for (int b = tid; b < bins; b += BLOCK) s_bin[b] = gcount[b];
+    for (int b = wg * BLOCK + tid; b < bins; b += n_wg * BLOCK) gcount_other[b] = 0;
+    __syncthreads();
+    // exclusive scan: ceil(bins / BLOCK) consecutive bins per thread
+    const int per = (bins + BLOCK - 1) / BLOCK;
+    const int lo = tid * per;
+    unsigned sum = 0;
+    for (int k = 0; k < per; ++k)
+        if (lo + k < bins) sum += s_bin[lo + k];
+    unsigned incl = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned v = __shfl_up(incl, off);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    unsigned run = incl - sum, total = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) {
+        if (w < wave) run += s_wave[w];
+        total += s_wave[w];
+    }
+    for (int k = 0; k < per; ++k)
+        if (lo + k < bins) {
+            const unsigned c = s_bin[lo + k];
+            s_bin[lo + k] = run;
+            run += c;
+        }
+    __syncthreads();
+    // positions [0, total) are written by the survivors (every bin's offsets
+    // are 0 .. count - 1, each taken once), [total, n_slots) by the threads of
+    // those slots: every position exactly once
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const int j = base + k * BLOCK;
+        if (j >= n_slots) continue;
+        if ((unsigned)j >= total) out[j] = -1;
+        if (r[k].x != -1) {      // (bin << 18 | offset never is all ones: bins < 16 380)
+            const unsigned p = s_bin[(unsigned)r[k].x >> TTL_INSTEP_OFF_BITS] +
+                               ((unsigned)r[k].x & ((1u << TTL_INSTEP_OFF_BITS) - 1u));
+            if (p < (unsigned)n_slots) out[p] = r[k].y;   // (always, unless the counts were not this step's)
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Riders of the gather launch (TTL_TAIL_RIDERS).  Two parts of a k_tail step
+// are needed by nothing before the next step: the order scatter of a re-bucket
+// step and the row maps (step_map_row).  Both are short and latency-bound, so
+// they run as extra workgroups BEHIND the gather's own (blockIdx.x >=
+// n_vblocks), which are dispatched while the gather's grid drains: no launch of
+// their own on the step's dependency chain, no second stream, no event, and
+// nothing pending when the step's launches are done.
+//   [n_vblocks, + n_scatter)  order_scatter_block(), TTL_INSTEP_CHUNK slots each;
+//   [.., + n_row_blocks)      step_map_row() of TTL_BLOCK active rows each, from
+//                             the scanned block bases k_tail's workgroup 0 left
+//                             in row_base and the survivor count in P.counts[0].
+// ---------------------------------------------------------------------------
+struct TailRiders {
+    int n_scatter;             // order-scatter workgroups, 0: none
+    int n_row_blocks;          // row-map workgroups, 0: none
+    // order scatter (see order_scatter_block)
+    const int2 *rec;
+    const unsigned *count;
+    unsigned *count_other;
+    int *order_out;
+    int n_slots;
+    int bins;
+    // row maps
+    const int *row_base;       // [n_row_blocks] survivors in front of each block of rows
+    const int *idx;
+    int *idx_next;
+    int n_active;
+    int order;
+    int n_pts;
+};
+// the most dynamic LDS the riders may ask of the gather launch: with four
+// workgroups per CU it leaves the gather's occupancy alone
+constexpr size_t TTL_RIDER_MAX_LDS = 16384;
+
 // ttl_state.hip: gathers the state rows of `n_rows` active rows (a step when
-// idx != nullptr, the reset otherwise) on stream s
+// idx != nullptr, the reset otherwise) on stream s; riders (or null): extra
+// workgroups of a k_state_dd launch with one workgroup per block of slots --
+// TTL_ERR_INVALID for any other launch
 int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx,
                             const int *row_dest, const int *proc, int n_rows, int L,
-                            float *out, int64_t pitch, hipStream_t s);
+                            float *out, int64_t pitch, hipStream_t s,
+                            const TailRiders *riders = nullptr);
 // ttl_state.hip: whether ttl_detail_launch_state() takes the register-deduplicated
 // gather (k_state_dd: reads the per-slot records of a processing order)
 bool ttl_detail_state_dedupes(const EnvParams &P, int state_kernel);
@@ -191,11 +311,7 @@ int ttl_detail_refresh_order(const EnvParams &P, const int *idx, int n, char *ws
 int ttl_detail_order_bins(const EnvParams &P, int nb[3]);
 // bytes of ONE of the two bin-count buffers
 size_t ttl_detail_order_instep_count_bytes();
-// rec[j] = {bin << TTL_INSTEP_OFF_BITS | offset inside the bin, or -1; next row
-// or -1} of slot j as k_tail left it (so: orders of at most 2^18 slots, which
-// is the default ceiling of the one-launch tail, and bins < 2^14), count = the bin counts it accumulated -> the dense order of
-// the survivors in order_out[0 .. n_slots) (-1 behind them); clears count_other
-constexpr int TTL_INSTEP_OFF_BITS = 18;
+// the stand-alone launch of order_scatter_block() (see there); clears count_other
 int ttl_detail_order_scatter(const int2 *rec, int n_slots, const unsigned *count,
                              unsigned *count_other, int bins, int *order_out, hipStream_t s);
 #endif

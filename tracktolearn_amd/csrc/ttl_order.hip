@@ -153,7 +153,8 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(const unsigned *__restrict__ 
 // In-step re-bucket (TTL_ORDER_INSTEP): k_tail has already counted the bricks
 // -- one global atomic per run of equal bricks of its sorted block -- and left
 // per slot {bin and offset inside the bin in one word, next row}.  What remains of the
-// counting sort is this one launch, one thread per slot: every workgroup scans
+// counting sort is order_scatter_block() (ttl_internal.h; this launch, or extra
+// workgroups of the gather launch: TTL_TAIL_RIDERS), one thread per slot: every workgroup scans
 // the bin counts itself through LDS (as k_tail scans the block counts; nobody
 // waits for anybody) and drops its slots' rows at cursor[bin] + offset.  The
 // result is dense: exactly the survivors, then -1 up to the old length.  Each
@@ -161,67 +162,13 @@ __global__ __launch_bounds__(BLOCK) void k_scatter(const unsigned *__restrict__ 
 // re-bucket step counts into, so no memset is launched.
 // ---------------------------------------------------------------------------
 constexpr int INSTEP_MAX_BINS = SORT_MAX_BINS - BLOCK / 64;   // the scan's wave totals share the 64 KB
-constexpr int INSTEP_ITEMS = 4;                 // slots per thread: a quarter of the workgroups scan
 
 __global__ __launch_bounds__(BLOCK) void k_order_scatter(const int2 *__restrict__ rec, int n_slots,
                                                          const unsigned *__restrict__ gcount,
                                                          unsigned *__restrict__ gcount_other,
                                                          int bins, int *__restrict__ out) {
     extern __shared__ unsigned s_bin[];          // [bins] counts -> cursors, [BLOCK / 64] wave totals
-    unsigned *s_wave = s_bin + bins;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the slots' records first: their latency hides behind the scan
-    const int base = blockIdx.x * (BLOCK * INSTEP_ITEMS) + tid;
-    int2 r[INSTEP_ITEMS];
-#pragma unroll
-    for (int k = 0; k < INSTEP_ITEMS; ++k) {
-        const int j = base + k * BLOCK;
-        r[k] = j < n_slots ? rec[j] : int2{-1, -1};
-    }
-    for (int b = tid; b < bins; b += BLOCK) s_bin[b] = gcount[b];
-    for (int b = blockIdx.x * BLOCK + tid; b < bins; b += gridDim.x * BLOCK) gcount_other[b] = 0;
-    __syncthreads();
-    // exclusive scan: ceil(bins / BLOCK) consecutive bins per thread
-    const int per = (bins + BLOCK - 1) / BLOCK;
-    const int lo = tid * per;
-    unsigned sum = 0;
-    for (int k = 0; k < per; ++k)
-        if (lo + k < bins) sum += s_bin[lo + k];
-    unsigned incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned v = __shfl_up(incl, off);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    unsigned run = incl - sum, total = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) {
-        if (w < wave) run += s_wave[w];
-        total += s_wave[w];
-    }
-    for (int k = 0; k < per; ++k)
-        if (lo + k < bins) {
-            const unsigned c = s_bin[lo + k];
-            s_bin[lo + k] = run;
-            run += c;
-        }
-    __syncthreads();
-    // positions [0, total) are written by the survivors (every bin's offsets
-    // are 0 .. count - 1, each taken once), [total, n_slots) by the threads of
-    // those slots: every position exactly once
-#pragma unroll
-    for (int k = 0; k < INSTEP_ITEMS; ++k) {
-        const int j = base + k * BLOCK;
-        if (j >= n_slots) continue;
-        if ((unsigned)j >= total) out[j] = -1;
-        if (r[k].x != -1) {      // (bin << 18 | offset never is all ones: bins < 16 380)
-            const unsigned p = s_bin[(unsigned)r[k].x >> TTL_INSTEP_OFF_BITS] +
-                               ((unsigned)r[k].x & ((1u << TTL_INSTEP_OFF_BITS) - 1u));
-            if (p < (unsigned)n_slots) out[p] = r[k].y;   // (always, unless the counts were not this step's)
-        }
-    }
+    order_scatter_block(s_bin, blockIdx.x, gridDim.x, rec, n_slots, gcount, gcount_other, bins, out);
 }
 }  // namespace
 
@@ -241,9 +188,9 @@ int ttl_detail_order_scatter(const int2 *rec, int n_slots, const unsigned *count
                              unsigned *count_other, int bins, int *order_out, hipStream_t s) {
     if (bins < 1 || bins > INSTEP_MAX_BINS || n_slots < 1 || n_slots > (1 << TTL_INSTEP_OFF_BITS))
         return fail(TTL_ERR_INVALID, "order scatter: %d bins, %d slots", bins, n_slots);
-    const size_t lds = ((size_t)bins + BLOCK / 64) * sizeof(unsigned);
-    const int chunk = BLOCK * INSTEP_ITEMS;
-    hipLaunchKernelGGL(k_order_scatter, dim3((n_slots + chunk - 1) / chunk), dim3(BLOCK), lds, s,
+    const int chunk = TTL_INSTEP_CHUNK;
+    hipLaunchKernelGGL(k_order_scatter, dim3((n_slots + chunk - 1) / chunk), dim3(BLOCK),
+                       ttl_detail_order_scatter_lds(bins), s,
                        rec, n_slots, count, count_other, bins, order_out);
     HIP_TRY(hipGetLastError());
     return TTL_OK;

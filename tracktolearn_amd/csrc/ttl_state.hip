@@ -459,11 +459,33 @@ __device__ __forceinline__ void state_row_dd(const EnvParams &P, float px, float
     }
 }
 
+// A rider workgroup of the gather launch (see TailRiders): `wg` counts from the
+// first workgroup behind the gather's own.
+__device__ __forceinline__ void tail_rider(const EnvParams &P, const TailRiders &R, int wg) {
+    if (wg < R.n_scatter) {
+        extern __shared__ unsigned s_rider[];   // the launch's dynamic LDS
+        order_scatter_block(s_rider, wg, R.n_scatter, R.rec, R.n_slots, R.count, R.count_other,
+                            R.bins, R.order_out);
+        return;
+    }
+    wg -= R.n_scatter;
+    const int i = wg * BLOCK + threadIdx.x;
+    if (wg >= R.n_row_blocks || i >= R.n_active) return;
+    step_map_row(P, i, R.idx[i], P.stop[i] != 0, R.row_base[wg] + P.rank[i], P.counts[0],
+                 R.order, R.n_pts, R.idx_next);
+}
+
 template <int LPS, int MINW, bool LOOP, bool MERGE_TAIL>
 __global__ __launch_bounds__(BLOCK, MINW) void k_state_dd(
     EnvParams P, const int *__restrict__ idx, const int *__restrict__ row_dest,
     const int *__restrict__ proc, int n_rows, int L, float *__restrict__ out,
-    long long pitch, int n_vblocks) {
+    long long pitch, int n_vblocks, TailRiders riders) {
+    // the riders first (whole workgroups, wave-uniform: they use barriers, so
+    // no lane may have left)
+    if ((int)blockIdx.x >= n_vblocks) {
+        tail_rider(P, riders, (int)blockIdx.x - n_vblocks);
+        return;
+    }
     // LPS lanes per streamline, 64 / LPS streamlines per wave (LPS need not be
     // a power of two: with 12 float4 columns per record a wave serves 5
     // streamlines on 60 lanes instead of 4 on 48)
@@ -713,8 +735,15 @@ bool ttl_detail_state_dedupes(const EnvParams &P, int state_kernel) {
 
 int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx,
                             const int *row_dest, const int *proc, int n_rows, int L,
-                            float *out, int64_t pitch, hipStream_t s) {
+                            float *out, int64_t pitch, hipStream_t s,
+                            const TailRiders *riders) {
     const bool dedupe = ttl_detail_state_dedupes(P, state_kernel);
+    const TailRiders R = riders ? *riders : TailRiders{};
+    const int n_riders = R.n_scatter + R.n_row_blocks;
+    const size_t lds = R.n_scatter ? ttl_detail_order_scatter_lds(R.bins) : 0;
+    // the riders sit behind a grid of one workgroup per block of slots
+    if (n_riders && (!dedupe || P.persist_rows > 0 || lds > TTL_RIDER_MAX_LDS))
+        return fail(TTL_ERR_INVALID, "state gather: this launch cannot carry riders");
     for_lanes_per_streamline<32>(P, [&](auto lps) {
         constexpr int LPS = decltype(lps)::value;
         const int n_vb = (int)gather_grid<LPS>(n_rows).x;
@@ -724,19 +753,18 @@ int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx
         // walk the blocks with a stride
         const int resident = 1024;
         const bool persist = dedupe && n_rows <= P.persist_rows && n_vb > resident;
-        const dim3 grid(persist ? resident : n_vb);
+        const dim3 grid(persist ? resident : n_vb + n_riders);
         if (!dedupe)
             hipLaunchKernelGGL((k_state<LPS>), grid, dim3(BLOCK), 0, s, P, idx, row_dest, proc,
                                n_rows, L, out, (long long)pitch);
         else if (LPS < 32 && P.n_coef >= 4 && state_kernel != 3)
-            hipLaunchKernelGGL((k_state_dd<LPS, 4, (LPS >= 32), (LPS < 32)>), grid, dim3(BLOCK), 0,
-                               s, P, idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb);
+            hipLaunchKernelGGL((k_state_dd<LPS, 4, (LPS >= 32), (LPS < 32)>), grid, dim3(BLOCK), lds,
+                               s, P, idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb, R);
         else
             hipLaunchKernelGGL((k_state_dd<LPS, (LPS >= 32 ? 2 : 4), (LPS >= 32), false>), grid,
-                               dim3(BLOCK), 0, s, P, idx, row_dest, proc, n_rows, L, out,
-                               (long long)pitch, n_vb);
+                               dim3(BLOCK), lds, s, P, idx, row_dest, proc, n_rows, L, out,
+                               (long long)pitch, n_vb, R);
     });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
-
