@@ -204,6 +204,41 @@ TTL_API int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
                   const int32_t *processing_order, float *state_out,
                   int64_t state_pitch, void *hip_stream);
 
+/* Bidirectional tracking (TTL_HAS_RETRACK).  The reference tracks one
+ * way from the seed (Tracker.track: reset -> validation_episode -> get_streamlines);
+ * this call turns a finished batch round so that the ordinary step loop grows the
+ * other half.  For every streamline g of the last ttl_env_reset, with f = lengths[g],
+ * minus the point a CURVATURE / MASK stop drops (the rule of get_streamlines,
+ * tracking_env.py:263-284; f >= 1):
+ *   - the first f points of its history row are reversed in place (one wavefront
+ *     per row), so that it reads forward end .. seed; init_len[g] = f;
+ *   - flags 0, lengths 1, dones 0, continue_idx = arange(n), length 1, as after a
+ *     reset; the first state rows ([n][state_pitch] f32) are those of the forward
+ *     ends.  processing_order as for ttl_env_reset.
+ * Until the next ttl_env_reset the handle is in retrack mode: a step that finds a
+ * row at a length L < init_len[g] REPLAYS it -- the new point is hist[g][L] as it
+ * stands, nothing is written to the history, action, noise (none is drawn, noise_out
+ * keeps its row) and first-step flip are ignored, only the LENGTH criterion is
+ * evaluated, the reward is 0; done_out, the survivor counts and the state rows are
+ * written as always.  The stored points passed CURVATURE and MASK on the way out
+ * (reversed, the curvature test multiplies the same numbers), except the seed, which
+ * no criterion has seen and which may lie outside the mask: stopping there would
+ * cost the streamline its seed.  From L >= init_len[g] on the row is an ordinary
+ * row; one with f == 1 never replays and takes the ordinary first step, flip
+ * included.  The batch stays in lock-step (one length for all rows) and ends with
+ * whole streamlines, forward end .. seed .. backward end, the seed at point
+ * init_len[g] - 1, of at most max_nb_steps points.
+ *   init_len  device int32 [n], written here, BORROWED until the next ttl_env_reset.
+ * TTL_ERR_INVALID for a null handle or buffer or a state_pitch too small;
+ * TTL_ERR_STATE unless every row of the last reset has stopped and been harvested
+ * and the count read (so: also before the first reset, between a step and its
+ * harvest, and while free-running).  In retrack mode ttl_env_freerun_begin returns
+ * TTL_ERR_UNSUPPORTED (a captured graph carries the kernel variant). */
+#define TTL_HAS_RETRACK 1
+TTL_API int ttl_env_reset_backward(ttl_env *env, int32_t *init_len,
+                                   const int32_t *processing_order, float *state_out,
+                                   int64_t state_pitch, void *hip_stream);
+
 /* TrackingEnvironment.step (tracking_env.py:135-221) for the n_active
  * streamlines of continue_idx (n_active must equal the count the last
  * reset/harvest reported):

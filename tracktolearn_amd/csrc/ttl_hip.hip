@@ -444,14 +444,49 @@ __device__ __forceinline__ int sorted_rank(const unsigned *s_key, unsigned sk, i
 // ---------------------------------------------------------------------------
 // k_advance: one thread per active streamline.
 // ---------------------------------------------------------------------------
+// One replayed step of a backward pass (ttl_env_reset_backward; advance_row
+// with RETRACK): the new point is the one the history already holds at
+// hist[g][L]; nothing is written there, the action (noise, first-step flip) is
+// not looked at, of the stopping criteria only LENGTH is evaluated (the points
+// passed CURVATURE and MASK in the forward pass -- reversed, the curvature dot
+// product has the same bits -- except the seed, which no criterion ever tested
+// and which must not stop its own streamline), the reward is 0.  The records
+// the rest of the step reads are written as by an ordinary row.
+__device__ __forceinline__ bool replay_row(const EnvParams &P, int g, int i, int L,
+                                           double *__restrict__ reward_out,
+                                           uint8_t *__restrict__ done_out) {
+    const float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
+    float4 *l2 = reinterpret_cast<float4 *>(P.last2 + 8 * (size_t)g);
+    const float4 q1 = l2[1];
+    const float p2x = h[L * 3 + 0], p2y = h[L * 3 + 1], p2z = h[L * 3 + 2];
+    l2[0] = q1;
+    l2[1] = float4{p2x, p2y, p2z, 0.0f};
+    const bool stop = L + 1 >= P.max_nb_steps;
+    if (stop) {
+        P.flags[g] = TTL_FLAG_LENGTH;
+        P.dones[g] = 1;
+    }
+    done_out[i] = stop ? 1 : 0;
+    if (reward_out) reward_out[i] = 0.0;
+    P.stop[i] = stop ? 1 : 0;
+    *reinterpret_cast<float4 *>(P.head + 4 * (size_t)i) =
+        float4{p2x, p2y, p2z, __int_as_float(g)};
+    return stop;
+}
+
 // One active row of a step: streamline g = idx[i] grows by one point, the
 // stopping criteria are tested on it, reward / done / head records are written.
-// Returns whether the streamline stops.
-template <int MODE, bool KEYED>
+// Returns whether the streamline stops.  RETRACK: while L < init_len[g] the row
+// replays its reversed forward half (replay_row) instead.
+template <int MODE, bool KEYED, bool RETRACK = false>
 __device__ __forceinline__ bool advance_row(
     const EnvParams &P, int g, int i, const float *__restrict__ actions,
     const typename NoiseSource<KEYED>::type &noise, int L,
-    double *__restrict__ reward_out, uint8_t *__restrict__ done_out) {
+    double *__restrict__ reward_out, uint8_t *__restrict__ done_out,
+    const int *__restrict__ init_len = nullptr) {
+    if constexpr (RETRACK) {
+        if (L < init_len[g]) return replay_row(P, g, i, L, reward_out, done_out);
+    }
     bool stop = false;
     {
         float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
@@ -628,6 +663,22 @@ __global__ __launch_bounds__(BLOCK) void k_advance(
     bool stop = false;
     if (active)
         stop = advance_row<MODE, KEYED>(P, idx[i], i, actions, noise, L, reward_out, done_out);
+    block_survivor_ranks(P, i, active, active && !stop);
+}
+
+// k_advance of a backward pass: rows with L < init_len[g] replay (replay_row)
+template <int MODE, bool KEYED = false>
+__global__ __launch_bounds__(BLOCK) void k_advance_retrack(
+    EnvParams P, const int *__restrict__ idx, const float *__restrict__ actions,
+    const typename NoiseSource<KEYED>::type noise, int n_active, int L,
+    double *__restrict__ reward_out, uint8_t *__restrict__ done_out,
+    const int *__restrict__ init_len) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    const bool active = i < n_active;
+    bool stop = false;
+    if (active)
+        stop = advance_row<MODE, KEYED, true>(P, idx[i], i, actions, noise, L, reward_out,
+                                              done_out, init_len);
     block_survivor_ranks(P, i, active, active && !stop);
 }
 
@@ -1124,6 +1175,43 @@ __global__ __launch_bounds__(BLOCK) void k_reset(EnvParams P, int *idx,
     idx[i] = i;
 }
 
+// ttl_env_reset_backward: one wavefront per streamline of a finished batch.  Its
+// valid points (f = lengths, minus the point a CURVATURE / MASK stop drops) are
+// reversed in place -- lane j swaps points j and f-1-j, 64 pairs a round -- so
+// that the row reads forward end .. seed; init_len[g] = f; then the per-row
+// records of k_reset, the forward end standing in for the seed.
+__global__ __launch_bounds__(BLOCK) void k_retrack_reset(EnvParams P, int *idx,
+                                                         int *__restrict__ init_len, int n) {
+    const int g = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (g >= n) return;
+    const int lane = threadIdx.x & 63;
+    const int cut = (P.flags[g] & (TTL_FLAG_CURVATURE | TTL_FLAG_MASK)) ? 1 : 0;
+    // (1 <= f <= max_nb_steps for a batch the step loop finished; the clamp keeps
+    // the swaps inside the row whatever the buffers hold)
+    const int f = min(max(P.lengths[g] - cut, 1), P.max_nb_steps + 1);
+    float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
+    const float ex = h[(f - 1) * 3 + 0], ey = h[(f - 1) * 3 + 1], ez = h[(f - 1) * 3 + 2];
+    for (int j = lane; j < f / 2; j += 64) {
+        float *a = h + 3 * j, *b = h + 3 * (f - 1 - j);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = a[c];
+            a[c] = b[c];
+            b[c] = t;
+        }
+    }
+    if (lane == 0) {
+        float4 *l2 = reinterpret_cast<float4 *>(P.last2 + 8 * (size_t)g);
+        l2[0] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+        l2[1] = float4{ex, ey, ez, 0.0f};
+        P.flags[g] = 0;
+        P.lengths[g] = 1;
+        P.dones[g] = 0;
+        idx[g] = g;
+        init_len[g] = f;
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_pack_sh(const float *__restrict__ src,
                                                    float *__restrict__ dst, int X, int Y,
                                                    int Z, int C, int pitch, int brick,
@@ -1320,6 +1408,9 @@ struct ttl_env {
     int *fr_host_word;     // device address of the pinned words a free-running step reports to
     int keyed;             // ttl_env_set_noise: the steps draw their noise themselves ...
     NoiseParams noise;     // ... from this
+    int n_total;           // rows of the last reset
+    const int *init_len;   // ttl_env_reset_backward: a backward pass is on, rows replay while the
+                           // length is below init_len[g]; null otherwise
     int prof_on;
     int prof_mask;    // bit k: time kernel class k
     int prof_cap;     // event pairs available per kernel class
@@ -1351,16 +1442,21 @@ static void prof_mark(ttl_env *e, int which, int stop, hipStream_t s) {
     if (stop) e->prof_n[which]++;
 }
 
-// The k_advance / k_advance_fr instantiation of a handle: calls f(mode, keyed)
-// with both as std::integral_constant.  Keyed noise (ttl_env_set_noise) exists
-// for TTL_MODE_F64DIR only.
+// The k_advance / k_advance_fr instantiation of a handle: calls f(mode, keyed,
+// retrack) with all three as std::integral_constant.  Keyed noise
+// (ttl_env_set_noise) exists for TTL_MODE_F64DIR only; retrack (a backward pass,
+// ttl_env_reset_backward) for k_advance only: free-running steps are refused then.
 template <class F>
 static void for_advance_variant(const ttl_env *env, F &&f) {
     using std::integral_constant;
-    if (env->keyed) f(integral_constant<int, TTL_MODE_F64DIR>{}, std::true_type{});
-    else if (env->d.mode == TTL_MODE_F32) f(integral_constant<int, TTL_MODE_F32>{}, std::false_type{});
-    else if (env->d.mode == TTL_MODE_F64DIR) f(integral_constant<int, TTL_MODE_F64DIR>{}, std::false_type{});
-    else f(integral_constant<int, TTL_MODE_F32NORM>{}, std::false_type{});
+    const auto with_retrack = [&](auto mode, auto keyed) {
+        if (env->init_len) f(mode, keyed, std::true_type{});
+        else f(mode, keyed, std::false_type{});
+    };
+    if (env->keyed) with_retrack(integral_constant<int, TTL_MODE_F64DIR>{}, std::true_type{});
+    else if (env->d.mode == TTL_MODE_F32) with_retrack(integral_constant<int, TTL_MODE_F32>{}, std::false_type{});
+    else if (env->d.mode == TTL_MODE_F64DIR) with_retrack(integral_constant<int, TTL_MODE_F64DIR>{}, std::false_type{});
+    else with_retrack(integral_constant<int, TTL_MODE_F32NORM>{}, std::false_type{});
 }
 
 extern "C" {
@@ -1706,6 +1802,8 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
     e->fr_host_word = nullptr;
     e->keyed = 0;
     memset(&e->noise, 0, sizeof(e->noise));
+    e->n_total = 0;
+    e->init_len = nullptr;
     e->prof_mask = (1 << TTL_PROFILE_CLASSES) - 1;
     e->prof_on = 0;
     e->prof_cap = 0;
@@ -1788,6 +1886,9 @@ int ttl_scripted_actions(const float *state, int64_t state_pitch, int32_t dir_of
     return TTL_OK;
 }
 
+static int ttl_env_rearm(ttl_env *env, int32_t n, const int32_t *processing_order,
+                         float *state_out, int64_t state_pitch, hipStream_t s);
+
 int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
                   const int32_t *processing_order, float *state_out,
                   int64_t state_pitch, void *hip_stream) {
@@ -1806,6 +1907,17 @@ int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
     hipLaunchKernelGGL(k_reset, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s,
                        env->P, d.idx_a, seeds, n);
     HIP_TRY(hipGetLastError());
+    env->n_total = n;
+    env->init_len = nullptr;
+    return ttl_env_rearm(env, n, processing_order, state_out, state_pitch, s);
+}
+
+// What a reset does once the per-row records are written (k_reset,
+// k_retrack_reset): the handle's host state, the processing order and the first
+// state rows.
+static int ttl_env_rearm(ttl_env *env, int32_t n, const int32_t *processing_order,
+                         float *state_out, int64_t state_pitch, hipStream_t s) {
+    const ttl_env_desc &d = env->d;
     env->cur = 0;
     env->length = 1;
     env->n_active = n;
@@ -1837,6 +1949,34 @@ int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
     return ttl_detail_launch_state(env->P, env->state_kernel, nullptr, nullptr,
                                    env->use_proc ? env->proc[0] : nullptr, n, 1, state_out,
                                    state_pitch, s);
+}
+
+int ttl_env_reset_backward(ttl_env *env, int32_t *init_len, const int32_t *processing_order,
+                           float *state_out, int64_t state_pitch, void *hip_stream) {
+    if (!env || !init_len || !state_out)
+        return fail(TTL_ERR_INVALID, "ttl_env_reset_backward: null argument");
+    const ttl_env_desc &d = env->d;
+    const int64_t width = 7LL * d.n_coef + 3LL * d.n_dirs;
+    if (state_pitch < width)
+        return fail(TTL_ERR_INVALID, "ttl_env_reset_backward: state_pitch %lld < %lld",
+                    (long long)state_pitch, (long long)width);
+    if (env->length < 1) return fail(TTL_ERR_STATE, "ttl_env_reset_backward: reset first");
+    if (env->fr_cap)
+        return fail(TTL_ERR_STATE, "ttl_env_reset_backward: free-running steps are enqueued, "
+                                   "call ttl_env_freerun_end first");
+    if (env->stepped)
+        return fail(TTL_ERR_STATE, "ttl_env_reset_backward: harvest the previous step first");
+    if (!env->n_exact || env->n_active != 0)
+        return fail(TTL_ERR_STATE, "ttl_env_reset_backward: %s%d streamlines are still active",
+                    env->n_exact ? "" : "up to ", env->n_active);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int n = env->n_total;
+    const int per_block = BLOCK / 64;
+    hipLaunchKernelGGL(k_retrack_reset, dim3((n + per_block - 1) / per_block), dim3(BLOCK), 0, s,
+                       env->P, d.idx_a, init_len, n);
+    HIP_TRY(hipGetLastError());
+    env->init_len = init_len;
+    return ttl_env_rearm(env, n, processing_order, state_out, state_pitch, s);
 }
 
 // side-stream copy of {n_continue, n_stopped} to the caller's pinned buffer,
@@ -1883,11 +2023,16 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
     const int L = env->length;
     const int nb = (n_active + BLOCK - 1) / BLOCK;
     prof_mark(env, 0, 0, s);
-    for_advance_variant(env, [&](auto mode, auto keyed) {
+    for_advance_variant(env, [&](auto mode, auto keyed, auto retrack) {
         constexpr int M = decltype(mode)::value;
         constexpr bool K = decltype(keyed)::value;
-        hipLaunchKernelGGL((k_advance<M, K>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx, actions,
-                           NoiseSource<K>::of(noise, env->noise), n_active, L, reward_out, done_out);
+        if constexpr (decltype(retrack)::value)
+            hipLaunchKernelGGL((k_advance_retrack<M, K>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx,
+                               actions, NoiseSource<K>::of(noise, env->noise), n_active, L,
+                               reward_out, done_out, env->init_len);
+        else
+            hipLaunchKernelGGL((k_advance<M, K>), dim3(nb), dim3(BLOCK), 0, s, env->P, idx, actions,
+                               NoiseSource<K>::of(noise, env->noise), n_active, L, reward_out, done_out);
     });
     prof_mark(env, 0, 1, s);
     HIP_TRY(hipGetLastError());
@@ -2248,6 +2393,9 @@ int ttl_env_freerun_begin(ttl_env *env, int32_t *host_counts, void *hip_stream) 
     if (env->length < 1) return fail(TTL_ERR_STATE, "ttl_env_freerun_begin: reset first");
     if (env->stepped) return fail(TTL_ERR_STATE, "ttl_env_freerun_begin: harvest the previous step first");
     if (env->fr_cap) return fail(TTL_ERR_STATE, "ttl_env_freerun_begin: already free-running");
+    if (env->init_len)
+        return fail(TTL_ERR_UNSUPPORTED, "ttl_env_freerun_begin: a backward pass "
+                    "(ttl_env_reset_backward) has no free-running steps");
     if (!env->n_exact)
         return fail(TTL_ERR_STATE, "ttl_env_freerun_begin: the survivor count of the last step has not been read");
     if (env->n_active < 1) return fail(TTL_ERR_STATE, "ttl_env_freerun_begin: no active streamline");
@@ -2298,7 +2446,7 @@ int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_rows, flo
     const int nb = (n_cap + BLOCK - 1) / BLOCK;
     // launches only: nothing below waits, copies or asks the runtime anything,
     // so the call may run under stream capture
-    for_advance_variant(env, [&](auto mode, auto keyed) {
+    for_advance_variant(env, [&](auto mode, auto keyed, auto) {
         hipLaunchKernelGGL((k_advance_fr<decltype(mode)::value, decltype(keyed)::value>), dim3(nb),
                            dim3(BLOCK), 0, s, env->P, d.idx_a, d.idx_b, actions, n_cap, reward_out,
                            done_out);

@@ -103,12 +103,23 @@ class NoisyTrackingEnvironment(TrackingEnvironment):
             self._install_keyed_noise()
         return state
 
-    def _install_keyed_noise(self):
+    #: the backward pass of a batch draws with ``noise_seed ^ BACKWARD_SEED_XOR``
+    #: and the same ids: other numbers than the forward pass, as independent of
+    #: the batching
+    BACKWARD_SEED_XOR = 0x9E3779B97F4A7C15
+
+    def reset_backward(self):
+        state = super().reset_backward()
+        if self.device_noise == 'keyed':
+            self._install_keyed_noise(self.BACKWARD_SEED_XOR)
+        return state
+
+    def _install_keyed_noise(self, seed_xor=0):
         """Tell the handle what to draw for this batch: streamline g of the
         batch is seed ``id_base + g`` of the run."""
         n = self._n_total
         d = _lib.NoiseDesc()
-        d.seed = int(self.noise_seed) & 0xffffffffffffffff
+        d.seed = (int(self.noise_seed) ^ seed_xor) & 0xffffffffffffffff
         d.id_base = self._noise_id_base
         d.sigma = float(self.noise)
         if self._fa_coef is not None:

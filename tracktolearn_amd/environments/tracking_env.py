@@ -9,6 +9,7 @@ libttl_hip.so:
   reset / nreset   (:91-133/:47-89)   ttl_env_reset
   step             (:135-221)         ttl_env_step
   harvest          (:223-245)         ttl_env_harvest
+  reset_backward   (none)             ttl_env_reset_backward
   get_streamlines  (:247-294)         device-side ragged pack (torch) + D2H
 
 Two flavours of the step loop are offered:
@@ -240,6 +241,45 @@ class TrackingEnvironment(BaseEnv):
         self.length = 1
         self._pending = None
         self.not_stopping = None
+        self._init_len = self.flags_forward = self.seed_index = None
+        return state
+
+    #: a backward pass is on (``reset_backward``): per-streamline int32 device
+    #: tensor of the points its reversed forward half holds; None otherwise
+    _init_len = None
+    #: after ``reset_backward``: the flags the forward pass ended with, and the
+    #: index of the seed in every history row (device tensors)
+    flags_forward = seed_index = None
+
+    def reset_backward(self):
+        """Bidirectional tracking (no counterpart in the reference, whose
+        streamlines grow one way from the seed): once every streamline of the
+        batch has stopped, turn the batch round.  Every history row is reversed
+        (forward end .. seed) and the batch re-armed as after a reset; the
+        ordinary step loop then replays the stored points, ignoring its actions,
+        until a row is back at its seed, and tracks on from there
+        (``ttl_env_reset_backward``).  The buffers end up holding whole
+        streamlines, forward end .. seed .. backward end; ``initial_points``
+        keeps the seeds.  Returns the state rows of the forward ends.  Ends with
+        the next ``reset`` / ``nreset``."""
+        if self._pending is not None:
+            raise RuntimeError('harvest() the previous step first')
+        n = self._n_total
+        flags_forward = self._buf_flags[:n].clone()
+        init_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        state = self._ring_state(n)
+        sort_rows = n >= self.SPATIAL_ORDER_MIN and getattr(self, 'spatial_order', True)
+        _lib.check(self._lib.ttl_env_reset_backward(
+            self._handle, init_len.data_ptr(),
+            _lib.ORDER_BY_POSITION if sort_rows else None, state.data_ptr(),
+            self._state_pitch, self._stream()), 'ttl_env_reset_backward')
+        self._init_len = init_len       # borrowed by the handle until the next reset
+        self.flags_forward = flags_forward
+        self.seed_index = init_len - 1
+        self._n_active = n
+        self._cur = 0
+        self.length = 1
+        self.not_stopping = None
         return state
 
     #: batches at least this large get a spatially sorted processing order
@@ -446,8 +486,12 @@ class TrackingEnvironment(BaseEnv):
         else:
             scores = self._oracle.predict(self._oracle_points(None, n_points))
         from tracktolearn_amd.environments.stopping_criteria import StoppingFlags
-        return (scores < 0.5).to(torch.uint8) * \
-            StoppingFlags.STOPPING_ORACLE.value
+        stop = scores < 0.5
+        if self._init_len is not None:
+            # a backward pass: a row still on its way back to the seed is not
+            # judged (it would lose points the forward pass kept)
+            stop &= ~(self._init_len[self._idx_view(n).long()] > n_points)
+        return stop.to(torch.uint8) * StoppingFlags.STOPPING_ORACLE.value
 
     def _oracle_reward(self, n, n_points, done, reward):
         """OracleReward.__call__ (oracle_reward.py:70-93): +oracle_bonus for the
@@ -627,9 +671,10 @@ class TrackingEnvironment(BaseEnv):
     def freerun_supported(self):
         """Whether ``run_free`` can take the episode from here: a batch of at
         most FREERUN_MAX rows between steps, no oracle criterion / bonus
-        (torch code between the step's launches) and no Gaussian action noise
-        (drawn on the host per step)."""
+        (torch code between the step's launches), no Gaussian action noise
+        (drawn on the host per step) and no backward pass (``reset_backward``)."""
         return (self._pending is None and 1 <= self._n_active <= self.FREERUN_MAX
+                and self._init_len is None
                 and not self._use_oracle_stopping and not self._use_oracle_reward
                 and not self._has_action_noise()
                 and self.add_neighborhood_vox

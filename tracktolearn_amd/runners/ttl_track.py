@@ -5,7 +5,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
     ttl_track.py in_odf in_seed in_mask out_tractogram [--input_wm]
         [--sh_basis B] [--compress T] [-f] [--save_seeds] [--agent DIR]
         [--hyperparameters JSON] [--n_actor N] [--npv N] [--min_length m]
-        [--max_length M] [--noise s] [--keyed_noise] [--fa_map F]
+        [--max_length M] [--noise s] [--keyed_noise] [--fa_map F] [--bidirectional]
         [--binary_stopping_threshold t] [--rng_seed S] [--direct_output]
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
@@ -86,6 +86,7 @@ class TrackToLearnTrack(object):
         # --fa_map implies keyed noise: only the in-kernel draw scales by FA
         self.fa_map_file = track_dto.get('fa_map')
         self.keyed_noise = bool(track_dto.get('keyed_noise')) or bool(self.fa_map_file)
+        self.bidirectional = bool(track_dto.get('bidirectional'))
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -146,7 +147,7 @@ class TrackToLearnTrack(object):
         alg = self._load_policy(env)
         tracker = Tracker(alg, self.n_actor, compress=self.compress,
                           min_length=self.min_length, max_length=self.max_length,
-                          save_seeds=self.save_seeds)
+                          save_seeds=self.save_seeds, bidirectional=self.bidirectional)
         # re-derives the step in voxels, the step counts and the neighbourhood
         # radius from the rescaled step (environments/env.py:196-212)
         env.load_subject()
@@ -240,6 +241,11 @@ def add_track_args(parser):
                               '(--rng_seed, seed index, step):\nthe tractogram '
                               'no longer depends on --n_actor or on the number '
                               'of GPUs.\nNot the NumPy stream of the default.')
+    track_g.add_argument('--bidirectional', action='store_true',
+                         help='Track both ways from every seed: the streamline '
+                              'is turned round at the end of\nits forward half '
+                              'and tracked on from the seed, so that it runs '
+                              'through its seed.')
     track_g.add_argument('--fa_map', type=str, default=None,
                          help='Scale the added noise according to an FA map '
                               '(.nii.gz on the grid of\nin_mask): std = '

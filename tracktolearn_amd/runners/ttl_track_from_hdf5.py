@@ -49,6 +49,7 @@ class TrackToLearnValidation(object):
         # --fa_map implies keyed noise: only the in-kernel draw scales by FA
         self.fa_map_file = g.get('fa_map')
         self.keyed_noise = bool(g.get('keyed_noise')) or bool(self.fa_map_file)
+        self.bidirectional = bool(g.get('bidirectional'))
         self.direct_output = bool(g.get('direct_output', False))
         with open(g['hyperparameters'], 'r') as json_file:
             hp = json.load(json_file)
@@ -123,7 +124,8 @@ class TrackToLearnValidation(object):
         alg.agent.load(self.agent, 'last_model_state')
         tracker = Tracker(alg, self.n_actor, compress=0.0,
                           min_length=self.min_length,
-                          max_length=self.max_length, save_seeds=False)
+                          max_length=self.max_length, save_seeds=False,
+                          bidirectional=self.bidirectional)
         os.makedirs(self.experiment_path, exist_ok=True)
         out = join(self.experiment_path, 'tractogram_{}_{}_{}.tck'.format(
             self.experiment, self.id, env.subject_id))
@@ -154,6 +156,10 @@ def add_valid_args(parser):
                         help='Draw the noise on the GPU as a function of '
                              '(--rng_seed, seed index, step): independent of '
                              '--n_actor.')
+    parser.add_argument('--bidirectional', action='store_true',
+                        help='Track both ways from every seed: the streamline '
+                             'is turned round at the end of its forward half '
+                             'and tracked on from the seed.')
     parser.add_argument('--fa_map', type=str, default=None,
                         help='FA map (.nii.gz on the subject\'s grid) to '
                              'influence STD for probabilistic tracking: '

@@ -63,7 +63,8 @@ class Tracker(object):
     (tracker.py:19-60)."""
 
     def __init__(self, alg, n_actor, prob=0., compress=0.0, min_length=20,
-                 max_length=200, save_seeds=False, device_output=None):
+                 max_length=200, save_seeds=False, device_output=None,
+                 bidirectional=False):
         self.alg = alg
         self.n_actor = n_actor
         self.prob = prob
@@ -71,6 +72,11 @@ class Tracker(object):
         self.min_length = min_length
         self.max_length = max_length
         self.save_seeds = save_seeds
+        #: track both ways from every seed: after the forward episode the batch
+        #: is turned round (``env.reset_backward``) and tracked on from the seeds,
+        #: so that a streamline runs through its seed instead of starting there
+        #: (never while training)
+        self.bidirectional = bool(bidirectional)
         #: filter + compression + pack by the HIP output stage; None: whenever
         #: the env's buffers are on the GPU.  False: the host path
         self.device_output = device_output
@@ -205,6 +211,9 @@ class Tracker(object):
             if end > start:
                 state = env.reset(start, end)
                 self.alg.validation_episode(state, env, self.prob)
+                if self.bidirectional:
+                    state = env.reset_backward()
+                    self.alg.validation_episode(state, env, self.prob)
             else:           # an empty shard still joins the collectives
                 env._n_total = 0
             yield
@@ -320,6 +329,9 @@ class Tracker(object):
             end = min(start + self.n_actor, len(env.seeds))
             state = env.reset(start, end)
             reward = self.alg.validation_episode(state, env, self.prob)
+            if self.bidirectional:
+                state = env.reset_backward()
+                reward += self.alg.validation_episode(state, env, self.prob)
             batch = env.get_streamlines()
             if tractogram is None and len(batch) > 0:
                 tractogram = batch
