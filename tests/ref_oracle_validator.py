@@ -5,6 +5,8 @@ include/ttl_hip.h defines it, the blocked-order float64 resampler of
 and the two numbers ``Oracle`` / ``Coverage``.  The library is built with
 -ffp-contract=off -fno-fast-math, so the same float64 operations here give
 the same bits."""
+from fractions import Fraction
+
 import numpy as np
 
 
@@ -279,3 +281,39 @@ def segments_blocked(points, nb_points=128):
     ``resample_blocked``."""
     r = resample_blocked(points, nb_points)
     return r[1:] - r[:-1]
+
+
+# ---------------------------------------------------------------- 3x3 map
+def _round_f32(q):
+    """The float32 nearest to the rational q, ties to even, rounded once
+    (normal range and zero; coordinates never leave it)."""
+    if q == 0:
+        return np.float32(0.0)
+    n, d = abs(q.numerator), q.denominator
+    e = n.bit_length() - d.bit_length()          # 2^(e - 1) < |q| < 2^(e + 1)
+    if Fraction(n, d) < Fraction(2) ** e:
+        e -= 1
+    e = max(e, -126)
+    m = round(abs(q) / Fraction(2) ** (e - 23))  # round(Fraction): half to even
+    v = np.float32(np.ldexp(float(m), e - 23))   # m <= 2^24: exact
+    return -v if q < 0 else v
+
+
+def _fma_f32(a, b, c):
+    """fmaf(a, b, c): the exact a b + c rounded to float32 once."""
+    return _round_f32(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def map_points_fma(points, m):
+    """The 3x3 map of ``k_oracle_segments`` (out = p @ m, m row-major) on
+    (L, 3) float32 points as the kernel states it, in float32:
+    out_c = fma(z, m[6 + c], fma(y, m[3 + c], x * m[c])), every operation
+    rounded exactly once (exact rational arithmetic, then one rounding)."""
+    p = np.asarray(points, np.float32)
+    m = np.asarray(m, np.float32).reshape(9)
+    out = np.empty_like(p)
+    for j, (x, y, z) in enumerate(p):
+        for c in range(3):
+            t = _round_f32(Fraction(float(x)) * Fraction(float(m[c])))
+            out[j, c] = _fma_f32(z, m[6 + c], _fma_f32(y, m[3 + c], t))
+    return out

@@ -187,3 +187,128 @@ def test_hip_packed_segments_equal_the_blocked_restatement(nb):
         assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32)), (i, len(s))
         plain = _plain(s, nb)
         np.testing.assert_allclose(got[i], plain[1:] - plain[:-1], atol=1e-5, rtol=0)
+
+
+# ------------------------------------------------- the 3x3 map of ttl_oracle_segments
+# (row-major, out = p @ m: the matrix of tests/test_oracle_net.py::test_oracle_segments_kernel)
+LIN = np.array([[0.9, 0.05, 0.0], [-0.03, 1.1, 0.02], [0.01, 0.0, 0.8]], np.float32)
+MAP_LENGTHS = (1, 2, 65, 129)
+
+
+@functools.lru_cache(maxsize=None)
+def _mapped_history(L):
+    """(_history(L), its six rows' first L points through the exact-fma map)."""
+    hist = _history(L)
+    return hist, np.stack([ref.map_points_fma(hist[g, :L], LIN) for g in range(len(hist))])
+
+
+def _ordered(x):
+    """float32 -> int64 that counts representable values (-0 and +0 coincide)."""
+    i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+    return np.where(i < 0, -(i & 0x7fffffff), i)
+
+
+def test_exact_fma_map_is_within_an_ulp_of_the_float64_product():
+    """The restatement itself, without a GPU.  The three float32 roundings of
+    the fma chain (at most half an ulp each) leave it less than 1.5 ulp from
+    the exact value and the float64 product rounded to float32 lies within
+    half an ulp of it, so the two float32 values are equal or neighbours."""
+    for L in MAP_LENGTHS:
+        hist, mapped = _mapped_history(L)
+        want = (hist[:, :L].astype(np.float64) @ LIN.astype(np.float64)).astype(np.float32)
+        assert np.abs(_ordered(mapped) - _ordered(want)).max() <= 1, L
+    # the identity keeps every bit
+    assert np.array_equal(ref.map_points_fma(_history(65)[0], np.eye(3)).view(np.uint32),
+                          _history(65)[0].view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('nb', (2, 65, 128))
+def test_hip_oracle_segments_map_equals_the_exact_fma_restatement(nb):
+    """The mapped path bit for bit: the points through the exact-fma map,
+    rounded to float32, then the blocked restatement; ids with stride 2."""
+    import ctypes as C
+
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    ids = np.array([5, 3, 0, 4, 1, 2], np.int32)
+    lin = (C.c_float * 9)(*[float(v) for v in LIN.ravel()])
+    for L in MAP_LENGTHS:
+        hist, mapped = _mapped_history(L)
+        d_hist = torch.from_numpy(hist).cuda()
+        d_ids = torch.from_numpy(np.stack([ids, -np.ones_like(ids)], 1).copy()).cuda()
+        out = torch.full((len(ids), nb - 1, 3), float('nan'), dtype=torch.float32, device='cuda')
+        _lib.check(lib.ttl_oracle_segments(d_hist.data_ptr(), d_hist.stride(0), d_ids.data_ptr(),
+                                           2, len(ids), L, lin, nb, out.data_ptr(), _stream()),
+                   'segments')
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        for q, g in enumerate(ids):
+            want = ref.segments_blocked(mapped[g], nb)
+            assert np.array_equal(got[q].view(np.uint32), want.view(np.uint32)), (L, q)
+
+
+# ------------------------------------------------- more rows than waves in the grid
+# Grids are capped at 4096 (k_resample) and 8192 (the segment kernels) workgroups of four
+# waves; beyond 4 cap rows a wave takes a second row and reuses its LDS.  Seven distinct
+# short rows repeated with period 7 (which divides neither 16 384 nor 32 768): a wave's
+# successive rows differ, so values left in the LDS would show.
+WRAP_NB = 3
+
+
+@functools.lru_cache(maxsize=None)
+def _short_rows(first_len):
+    """Seven rows of first_len .. first_len + 6 points."""
+    return [_walk(first_len + r, 300 + r) for r in range(7)]
+
+
+@pytest.mark.gpu
+def test_hip_resampler_when_a_wave_takes_a_second_row():
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    n, rows = 4 * 4096 + 3, _short_rows(1)
+    pts7, len7 = _padded([(p, len(p)) for p in rows], 7, extra=0)
+    want7 = np.stack([ref.resample_blocked(p, WRAP_NB) for p in rows])
+    which = np.arange(n) % 7
+    d_pts = torch.from_numpy(pts7[which]).cuda()
+    d_len = torch.from_numpy(len7[which].astype(np.int32)).cuda()
+    out = torch.full((n, WRAP_NB, 3), float('nan'), dtype=torch.float32, device='cuda')
+    _lib.check(lib.ttl_resample_streamlines(d_pts.data_ptr(), d_pts.stride(0), d_len.data_ptr(),
+                                            None, n, 7, WRAP_NB, out.data_ptr(), _stream()),
+               'resample')
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), want7[which].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_hip_oracle_segments_when_a_wave_takes_a_second_row():
+    """Every row has five points; the rows are gathered through a permutation."""
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    n, L = 4 * 8192 + 3, 5
+    rows = [p[:L] for p in _short_rows(5)]
+    want7 = np.stack([ref.segments_blocked(p, WRAP_NB) for p in rows])
+    ids = np.random.RandomState(11).permutation(n).astype(np.int32)
+    d_hist = torch.from_numpy(np.stack(rows)[np.arange(n) % 7]).cuda()
+    d_ids = torch.from_numpy(ids).cuda()
+    out = torch.full((n, WRAP_NB - 1, 3), float('nan'), dtype=torch.float32, device='cuda')
+    _lib.check(lib.ttl_oracle_segments(d_hist.data_ptr(), d_hist.stride(0), d_ids.data_ptr(), 1,
+                                       n, L, None, WRAP_NB, out.data_ptr(), _stream()),
+               'segments')
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), want7[ids % 7].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_hip_packed_segments_when_a_wave_takes_a_second_row():
+    """Lengths 0 .. 6: an empty streamline (zero vectors) sits inside the loop."""
+    from tracktolearn_amd.oracles.oracle import oracle_segments_packed
+    n = 4 * 8192 + 3
+    rows = [np.zeros((0, 3), np.float32)] + _short_rows(1)[:6]
+    want7 = np.stack([ref.segments_blocked(p, WRAP_NB) if len(p) else
+                      np.zeros((WRAP_NB - 1, 3), np.float32) for p in rows])
+    which = np.arange(n) % 7
+    offsets = np.concatenate([[0], np.cumsum([len(rows[w]) for w in which])]).astype(np.int64)
+    points = torch.from_numpy(np.concatenate([rows[w] for w in which])).cuda()
+    got = oracle_segments_packed(points, torch.from_numpy(offsets).cuda(), WRAP_NB).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want7[which].view(np.uint32))

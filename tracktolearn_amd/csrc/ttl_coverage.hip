@@ -133,11 +133,10 @@ __global__ __launch_bounds__(BLOCK) void k_tract_coverage(
     const float *__restrict__ scores, float threshold, Dims D,
     unsigned char *__restrict__ visited) {
     const int lane = threadIdx.x & 63;
-    const int waves = (BLOCK / 64) * gridDim.x;
-    for (int row = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); row < n; row += waves) {
-        if (scores && !(scores[row] > threshold)) continue;
+    wave_rows(n, [&](int row) {
+        if (scores && !(scores[row] > threshold)) return;
         const long long o0 = offsets[row], L = offsets[row + 1] - o0;
-        if (L < 1) continue;
+        if (L < 1) return;
         const float *p = points + 3 * o0;
         if (lane == 0) {
             const double x = p[0], y = p[1], z = p[2];
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(BLOCK) void k_tract_coverage(
         }
         for (long long j = lane; j < L - 1; j += 64)
             walk_segment(p + 3 * j, p + 3 * (j + 1), D, visited);
-    }
+    });
 }
 }  // namespace
 
@@ -161,8 +160,7 @@ int ttl_tract_coverage(const float *points, const int64_t *offsets, int32_t n,
         return fail(TTL_ERR_INVALID, "ttl_tract_coverage: bad arguments");
     if (n == 0) return TTL_OK;
     const Dims D{{dims[0], dims[1], dims[2]}};
-    const int want = (n + (BLOCK / 64) - 1) / (BLOCK / 64);
-    hipLaunchKernelGGL(k_tract_coverage, dim3(want < 8192 ? want : 8192), dim3(BLOCK), 0,
+    hipLaunchKernelGGL(k_tract_coverage, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK), 0,
                        (hipStream_t)hip_stream, points, (const long long *)offsets, n, scores,
                        threshold, D, visited);
     HIP_TRY(hipGetLastError());

@@ -150,6 +150,48 @@ __device__ __forceinline__ void step_publish_counts(const EnvParams &P, int tota
     }
 }
 
+// ---------------------------------------------------------------------------
+// One wavefront per row (ttl_resample.hip, ttl_coverage.hip, ttl_peaks.hip,
+// ttl_tract.hip): the lanes of a wave hand values to each other through LDS
+// that no other wave touches.
+// ---------------------------------------------------------------------------
+// Orders this wave's LDS accesses before the barrier against those behind it
+// (the LDS executes one wave's instructions in order; this keeps the compiler
+// from moving them across)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// body(row) for the rows of this wave: row = its number in the grid, then in
+// steps of the grid's waves (a `continue` of the loop is a `return` of body)
+template <class F>
+__device__ __forceinline__ void wave_rows(int n, F body) {
+    const int waves = (TTL_BLOCK / 64) * gridDim.x;
+    for (int row = blockIdx.x * (TTL_BLOCK / 64) + (threadIdx.x >> 6); row < n; row += waves)
+        body(row);
+}
+
+// ... and the grid of such a launch: a wave for each of n rows, at most `cap` workgroups
+inline unsigned ttl_detail_wave_grid(long long n, int cap) {
+    const long long want = (n + (TTL_BLOCK / 64) - 1) / (TTL_BLOCK / 64);
+    return (unsigned)(want < cap ? want : cap);
+}
+
+// ttl_resample.hip: the one place that reserves dynamic LDS.  Static + dynamic
+// LDS of `kernel` against what the device gives a workgroup, BEFORE the launch:
+// the runtime does not reject a launch that asks for more -- the queue aborts.
+// room->fits = false: nothing was set, the caller refuses in its own words.
+// Otherwise hipFuncAttributeMaxDynamicSharedMemorySize is raised when the call
+// needs more than any before it.  What the kernel and the device report is read
+// once per thread, device and kernel (callers are on the training step's path).
+struct LdsRoom {
+    size_t fixed, limit;   // the kernel's static LDS, the device's limit per workgroup
+    bool fits;
+};
+int ttl_detail_reserve_lds(const void *kernel, size_t dynamic, LdsRoom *room);
+
 // records of the packed SH volume (padding records of the bricked order included)
 inline size_t ttl_detail_sh_records(const EnvParams &P) {
     if (!P.sh_brick) return (size_t)P.sh_dim[0] * P.sh_dim[1] * P.sh_dim[2];

@@ -668,42 +668,6 @@ __global__ __launch_bounds__(256, 2) void k_oracle_net_wg(NetArgs P) {
 
 constexpr int TTL_ORACLE_NET_MAX_FF = 8192;
 
-// Static + dynamic LDS of `kernel` (slot: 0..2 the wave kernel of 1 / 2 / 4 heads, 3..5 the
-// workgroup kernel) against the device's limit per workgroup, BEFORE the launch: the runtime
-// does not reject a launch that asks for more -- the queue aborts.  What the kernel and the
-// device report is read once per device and thread (the call is on the training step's path);
-// hipFuncAttributeMaxDynamicSharedMemorySize is raised when a call needs more dynamic LDS than
-// any before it, as ttl_oracle_segments does.
-int reserve_lds(const void *kernel, int slot, size_t dynamic, int ff_dim) {
-    struct Seen { size_t limit, fixed, allowed; bool known; };
-    static thread_local Seen seen[64][6] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    Seen fresh{};
-    Seen &k = (dev >= 0 && dev < 64) ? seen[dev][slot] : fresh;
-    if (!k.known) {
-        int limit = 0;
-        HIP_TRY(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        HIP_TRY(hipFuncGetAttributes(&fa, kernel));
-        k.limit = (size_t)(limit > 0 ? limit : 0);
-        k.fixed = fa.sharedSizeBytes;
-        k.allowed = 0;
-        k.known = true;
-    }
-    if (k.fixed + dynamic > k.limit)
-        return fail(TTL_ERR_UNSUPPORTED,
-                    "ttl_oracle_net_forward: feed-forward width %d needs %zu B of LDS (%zu static "
-                    "+ %zu for b_1 of two layers), the device gives a workgroup %zu",
-                    ff_dim, k.fixed + dynamic, k.fixed, dynamic, k.limit);
-    if (dynamic > k.allowed) {
-        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)dynamic));
-        k.allowed = dynamic;
-    }
-    return TTL_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -743,13 +707,19 @@ int ttl_oracle_net_forward(const float *dirs, int64_t n, const void *packed_half
     // k_oracle_net_wg: pbuf 48 KB + fbuf 8 KB = 56 KB, 72 KB / 120 KB in all; k_oracle_net:
     // none.  The device gives a workgroup 160 KB (gfx950).
     const size_t lds = (size_t)2 * ff_dim * sizeof(float);
-    // [workgroup kernel?][1 / 2 / 4 heads]; slot 3 wg + which is the kernel's entry in reserve_lds
+    // [workgroup kernel?][1 / 2 / 4 heads]
     static void (*const kernels[2][3])(NetArgs) = {
         {k_oracle_net<1>, k_oracle_net<2>, k_oracle_net<4>},
         {k_oracle_net_wg<1>, k_oracle_net_wg<2>, k_oracle_net_wg<4>}};
     const int which = n_head == 1 ? 0 : n_head == 2 ? 1 : 2;
     const auto kernel = kernels[wg][which];
-    if (int rc = reserve_lds((const void *)kernel, 3 * wg + which, lds, ff_dim)) return rc;
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds((const void *)kernel, lds, &room)) return rc;
+    if (!room.fits)
+        return fail(TTL_ERR_UNSUPPORTED,
+                    "ttl_oracle_net_forward: feed-forward width %d needs %zu B of LDS (%zu static "
+                    "+ %zu for b_1 of two layers), the device gives a workgroup %zu",
+                    ff_dim, room.fixed + lds, room.fixed, lds, room.limit);
     // one workgroup of four waves per streamline, or per four streamlines
     const dim3 grid((unsigned)(wg ? n : (n + 3) / 4)), block(256);
     hipLaunchKernelGGL(kernel, grid, block, lds, s, P);

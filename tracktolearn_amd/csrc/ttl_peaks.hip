@@ -72,9 +72,7 @@ __global__ __launch_bounds__(BLOCK) void k_peaks(
         const float odf_min = fmaxf(lo, 0.0f);
         // same-wave LDS hand-off (no other wave touches sfw): order the
         // lanes' writes before the neighbour reads below
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         // local maxima of the hemisphere graph: >= every neighbour, > at least
         // one, positive.  cand = value or -1
         float cand[PEAKS_MAX_DIRS_PER_LANE];
@@ -155,8 +153,7 @@ __global__ __launch_bounds__(BLOCK) void k_peaks(
             o[3 * lane + 1] = py;
             o[3 * lane + 2] = pz;
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();           // sfw is reused by the next voxel
+        wave_sync();                               // sfw is reused by the next voxel
     }
 }
 
@@ -181,16 +178,14 @@ int ttl_peaks_from_sh(const float *sh, int64_t n_voxels, int32_t n_coef,
                     npeaks, PEAKS_MAX_KEEP, max_candidates);
     const size_t lds = ((size_t)n_coef * n_vertices + (size_t)(BLOCK / 64) * n_vertices) *
                        sizeof(float);
-    if (lds > 160u * 1024u)
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds((const void *)k_peaks, lds, &room)) return rc;
+    if (!room.fits)
         return fail(TTL_ERR_INVALID, "ttl_peaks_from_sh: SH->SF matrix (%d x %d) exceeds the LDS",
                     n_coef, n_vertices);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_peaks,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long long want = (n_voxels + (BLOCK / 64) - 1) / (BLOCK / 64);
-    const int grid = (int)(want < 1024 ? want : 1024);
-    hipLaunchKernelGGL(k_peaks, dim3(grid), dim3(BLOCK), lds, (hipStream_t)hip_stream, sh,
-                       (long long)n_voxels, n_coef, sf_matrix, vertices, neighbours,
-                       n_vertices, degree, npeaks, relative_threshold, absolute_threshold,
+    hipLaunchKernelGGL(k_peaks, dim3(ttl_detail_wave_grid(n_voxels, 1024)), dim3(BLOCK), lds,
+                       (hipStream_t)hip_stream, sh, (long long)n_voxels, n_coef, sf_matrix,
+                       vertices, neighbours, n_vertices, degree, npeaks, relative_threshold, absolute_threshold,
                        min_separation_cos, max_candidates, peaks_out);
     HIP_TRY(hipGetLastError());
     return TTL_OK;

@@ -1,108 +1,224 @@
-// ttl_resample.hip -- arc-length resampling of padded streamline batches for
-// the TractOracle-Net scoring path (TrackToLearn/oracles/oracle.py:52,70:
+// ttl_resample.hip -- arc-length resampling of streamlines for the
+// TractOracle-Net scoring path (TrackToLearn/oracles/oracle.py:52,70:
 // dipy set_number_of_points(streamlines, 128)); part of libttl_hip.so.
-// One wavefront per streamline: float64 segment lengths -> blocked wave scan
-// of the cumulative arc length in LDS -> each lane places its target points
-// by binary search and interpolates linearly inside the segment.
-// k_oracle_segments_packed does the same for ragged input of any length.
+// One wavefront per streamline and ONE statement of the algorithm,
+// resample_row(): float64 segment lengths -> blocked wave scan of the
+// cumulative arc length -> each lane places its target points by binary search
+// and interpolates linearly inside the segment, the last point kept exactly.
+// It is parameterised by how the cumulative arc length is kept: CumStored
+// (every value in LDS: rows the LDS holds) or CumReplayed (the 64 lane prefixes
+// in LDS, values recomputed on demand: any length, the same bits).  The three
+// kernels are shells around it:
+//   k_resample                padded batch -> nb points              (CumStored)
+//   k_oracle_segments         history rows, optional 3x3 map -> nb - 1
+//                             difference vectors                     (CumStored)
+//   k_oracle_segments_packed  ragged input of any length -> the same (CumReplayed)
+// The file also holds the library's dynamic-LDS reservation
+// (ttl_detail_reserve_lds) and the oracle's sparse bonus.
+#include <vector>
+
 #include "ttl_internal.h"
 
 namespace {
 constexpr int BLOCK = TTL_BLOCK;
 
-__global__ __launch_bounds__(BLOCK) void k_resample(
-    const float *__restrict__ points, long long row_pitch, const int *__restrict__ lengths32,
-    const long long *__restrict__ lengths64, int n, int max_len, int nb,
-    float *__restrict__ out) {
-    extern __shared__ __align__(16) double cum_all[];
-    double *cum = cum_all + (size_t)(threadIdx.x >> 6) * max_len;   // this wave's [max_len]
-    const int lane = threadIdx.x & 63;
-    const int waves = (BLOCK / 64) * gridDim.x;
-    for (int row = blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); row < n; row += waves) {
-        const float *p = points + (size_t)row * (size_t)row_pitch;
-        float *o = out + (size_t)row * (size_t)nb * 3;
-        int L = lengths32 ? lengths32[row] : (int)lengths64[row];
-        L = min(max(L, 1), max_len);
-        const int nseg = L - 1;
-        // blocked scan: lane owns the contiguous segments [lo, hi)
+// Dynamic LDS of a launch whose waves keep `per_wave` bytes each, and this wave's part of it
+__host__ __device__ inline size_t wave_lds_bytes(size_t per_wave) {
+    return (size_t)(BLOCK / 64) * ((per_wave + 15) & ~(size_t)15);
+}
+__device__ __forceinline__ char *wave_lds(size_t per_wave) {
+    extern __shared__ __align__(16) char lds_all[];
+    return lds_all + (size_t)(threadIdx.x >> 6) * ((per_wave + 15) & ~(size_t)15);
+}
+// ... per wave: k_resample cum [max_len] doubles; k_oracle_segments cum [n_pts] doubles,
+// pts [3 n_pts] floats, res [3 nb] floats; k_oracle_segments_packed pre [64] doubles,
+// res [3 nb] floats
+__host__ __device__ inline size_t resample_lds(int max_len) { return (size_t)max_len * 8; }
+__host__ __device__ inline size_t segments_lds(int n_pts, int nb) {
+    return (size_t)n_pts * 8 + (size_t)n_pts * 12 + (size_t)nb * 12;
+}
+__host__ __device__ inline size_t packed_lds(int nb) { return (size_t)64 * 8 + (size_t)nb * 12; }
+
+// float64 length of segment j of the float32 points p
+template <class I>
+__device__ __forceinline__ double seg_len(const float *__restrict__ p, I j) {
+    const double dx = (double)p[3 * (j + 1) + 0] - (double)p[3 * j + 0];
+    const double dy = (double)p[3 * (j + 1) + 1] - (double)p[3 * j + 1];
+    const double dz = (double)p[3 * (j + 1) + 2] - (double)p[3 * j + 2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// the sum of `local` over the lanes below this one: inclusive Hillis-Steele scan
+// over the lanes, minus the lane's own
+__device__ __forceinline__ double lanes_below(double local, int lane) {
+    double before = local;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double up = __shfl_up(before, off);
+        if (lane >= off) before = before + up;
+    }
+    return before - local;
+}
+
+// The cumulative arc length cum[0 .. nseg] of a row, by a blocked scan: lane l owns the
+// contiguous segments [l per, (l + 1) per), cum[j + 1] = local_j + before, where local_j
+// is the lane's running sum and `before` the sum of the lower lanes.  Two ways to keep it,
+// with the same members: build() from the points, at(m) = cum[m], and count_le(target,
+// nseg) = #{m in [0, nseg) : cum[m + 1] <= target} as the binary search finds it.
+//
+// Stored: every value in this wave's LDS.
+struct CumStored {
+    using Index = int;
+    double *cum;                                // [nseg + 1]
+    __device__ __forceinline__ void build(const float *__restrict__ p, int nseg, int lane) {
         const int per = (nseg + 63) >> 6;
         const int lo = min(lane * per, nseg), hi = min(lo + per, nseg);
         double local = 0.0;
         for (int j = lo; j < hi; ++j) {
-            const double dx = (double)p[3 * (j + 1) + 0] - (double)p[3 * j + 0];
-            const double dy = (double)p[3 * (j + 1) + 1] - (double)p[3 * j + 1];
-            const double dz = (double)p[3 * (j + 1) + 2] - (double)p[3 * j + 2];
-            local = local + sqrt((dx * dx + dy * dy) + dz * dz);
-            cum[j + 1] = local;                 // within-chunk prefix for now
+            local = local + seg_len(p, j);
+            cum[j + 1] = local;                 // within-block prefix for now
         }
-        double before = local;                  // inclusive scan over lanes
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double up = __shfl_up(before, off);
-            if (lane >= off) before = before + up;
-        }
-        before = before - local;                // exclusive
+        const double before = lanes_below(local, lane);
         for (int j = lo; j < hi; ++j) cum[j + 1] = cum[j + 1] + before;
         if (lane == 0) cum[0] = 0.0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double total = cum[nseg];
-        for (int k = lane; k < nb; k += 64) {
-            float x, y, z;
-            if (k == nb - 1 || nseg == 0) {     // the last point is kept exactly
-                x = p[3 * nseg + 0];
-                y = p[3 * nseg + 1];
-                z = p[3 * nseg + 2];
-            } else {
-                const double target = total * ((double)k / (double)(nb - 1));
-                // j = #{m in [0, nseg) : cum[m + 1] <= target}, at most nseg - 1
-                int a = 0, b = nseg;
-                while (a < b) {
-                    const int mid = (a + b) >> 1;
-                    if (cum[mid + 1] <= target) a = mid + 1;
-                    else b = mid;
-                }
-                const int j = min(a, nseg - 1);
-                const double c0 = cum[j], c1 = cum[j + 1];
-                const double den = c1 - c0;
-                const double r = den > 0.0 ? (target - c0) / den : 0.0;
-                const double ax = p[3 * j + 0], ay = p[3 * j + 1], az = p[3 * j + 2];
-                const double bx = p[3 * j + 3], by = p[3 * j + 4], bz = p[3 * j + 5];
-                x = (float)(ax + r * (bx - ax));
-                y = (float)(ay + r * (by - ay));
-                z = (float)(az + r * (bz - az));
-            }
-            o[3 * k + 0] = x;
-            o[3 * k + 1] = y;
-            o[3 * k + 2] = z;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();        // cum is reused by the next row
     }
+    __device__ __forceinline__ double at(int m) const { return cum[m]; }
+    __device__ __forceinline__ int count_le(double target, int nseg) const {
+        int a = 0, b = nseg;
+        while (a < b) {
+            const int mid = (a + b) >> 1;
+            if (cum[mid + 1] <= target) a = mid + 1;
+            else b = mid;
+        }
+        return a;
+    }
+};
+
+// Replayed, for rows of any length: LDS holds the 64 exclusive lane prefixes only.  A
+// value cum[m] is recomputed on demand by re-walking its owner lane's block, which gives
+// the bits CumStored stores (local_j + before).  The target search replays CumStored's
+// binary search probe by probe while the interval spans several lane blocks (cum may step
+// back by an ulp at a block boundary, where `before` comes from a subtraction); inside
+// one block cum is non-decreasing, so the rest of that search is the first m with
+// cum[m + 1] > target, found by one walk of the block.
+struct CumReplayed {
+    using Index = long long;
+    double *pre;                                // [64]
+    const float *p = nullptr;                   // the row and its segments per lane: build()
+    long long per = 1;
+    __device__ __forceinline__ void build(const float *__restrict__ points, long long nseg,
+                                          int lane) {
+        p = points;
+        per = nseg > 0 ? (nseg + 63) >> 6 : 1;
+        const long long lo = min((long long)lane * per, nseg), hi = min(lo + per, nseg);
+        double local = 0.0;
+        for (long long j = lo; j < hi; ++j) local = local + seg_len(p, j);
+        pre[lane] = lanes_below(local, lane);
+    }
+    __device__ __forceinline__ double at(long long m) const {
+        if (m < 1) return 0.0;
+        const long long seg = m - 1, owner = seg / per;
+        double local = 0.0;
+        for (long long j = owner * per; j <= seg; ++j) local = local + seg_len(p, j);
+        return local + pre[owner];
+    }
+    __device__ __forceinline__ long long count_le(double target, long long nseg) const {
+        long long a = 0, b = nseg;
+        while (a < b) {
+            if (a / per == (b - 1) / per) {     // one block: cum is monotone here
+                const long long owner = a / per;
+                double acc = 0.0;
+                long long first = b;
+                for (long long j = owner * per; j < b; ++j) {
+                    acc = acc + seg_len(p, j);
+                    if (j >= a && acc + pre[owner] > target) {
+                        first = j;
+                        break;
+                    }
+                }
+                return first;
+            }
+            const long long mid = (a + b) >> 1;
+            if (at(mid + 1) <= target) a = mid + 1;
+            else b = mid;
+        }
+        return a;
+    }
+};
+
+// One wave resamples the nseg + 1 points p to nb points at equal arc length: 3 nb floats
+// to dst (LDS or global), visible to the whole wave on return; `cum` may then be rebuilt.
+template <class Cum>
+__device__ __forceinline__ void resample_row(Cum cum, const float *__restrict__ p,
+                                             typename Cum::Index nseg, int nb, float *dst,
+                                             int lane) {
+    using Index = typename Cum::Index;
+    cum.build(p, nseg, lane);
+    wave_sync();
+    const double total = cum.at(nseg);
+    for (int k = lane; k < nb; k += 64) {
+        float x, y, z;
+        if (k == nb - 1 || nseg == 0) {         // the last point is kept exactly
+            x = p[3 * nseg + 0];
+            y = p[3 * nseg + 1];
+            z = p[3 * nseg + 2];
+        } else {
+            const double target = total * ((double)k / (double)(nb - 1));
+            const Index j = min(cum.count_le(target, nseg), nseg - 1);
+            const double c0 = cum.at(j), c1 = cum.at(j + 1);
+            const double den = c1 - c0;
+            const double r = den > 0.0 ? (target - c0) / den : 0.0;
+            const double ax = p[3 * j + 0], ay = p[3 * j + 1], az = p[3 * j + 2];
+            const double bx = p[3 * j + 3], by = p[3 * j + 4], bz = p[3 * j + 5];
+            x = (float)(ax + r * (bx - ax));
+            y = (float)(ay + r * (by - ay));
+            z = (float)(az + r * (bz - az));
+        }
+        dst[3 * k + 0] = x;
+        dst[3 * k + 1] = y;
+        dst[3 * k + 2] = z;
+    }
+    wave_sync();
+}
+
+// The network's input of a row: the float32 differences of its nb resampled points `res`
+// (LDS), which the next row may overwrite on return
+__device__ __forceinline__ void difference_row(const float *res, int nb, float *__restrict__ o,
+                                               int lane) {
+    for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = res[e + 3] - res[e];
+    wave_sync();
+}
+
+__global__ __launch_bounds__(BLOCK) void k_resample(
+    const float *__restrict__ points, long long row_pitch, const int *__restrict__ lengths32,
+    const long long *__restrict__ lengths64, int n, int max_len, int nb,
+    float *__restrict__ out) {
+    double *cum = reinterpret_cast<double *>(wave_lds(resample_lds(max_len)));
+    const int lane = threadIdx.x & 63;
+    wave_rows(n, [&](int row) {
+        int L = lengths32 ? lengths32[row] : (int)lengths64[row];
+        L = min(max(L, 1), max_len);
+        resample_row(CumStored{cum}, points + (size_t)row * (size_t)row_pitch, L - 1, nb,
+                     out + (size_t)row * (size_t)nb * 3, lane);
+    });
 }
 
 // History rows -> the network's input in one pass: what the env's oracle path
 // does with torch ops (gather the rows' first n_pts points, optional 3x3 map
-// into the oracle's voxel space, resample to nb points, difference), one
-// wavefront per streamline.  The mapped points are rounded to float32 and the
-// resampled points to float32 before differencing, as the separate steps do.
+// into the oracle's voxel space, resample to nb points, difference).  The mapped
+// points are rounded to float32 and the resampled points to float32 before
+// differencing, as the separate steps do.
 struct Lin { float m[9]; };          // row-major: out = p @ m
 
 __global__ __launch_bounds__(BLOCK) void k_oracle_segments(
     const float *__restrict__ hist, long long row_pitch, const int *__restrict__ ids,
     int id_stride, int n, int n_pts, int use_lin, Lin lin, int nb, float *__restrict__ dirs) {
-    extern __shared__ __align__(16) double seg_lds[];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // per wave: cum [n_pts] doubles, pts [3 n_pts] floats, res [3 nb] floats
-    const size_t per_wave = (size_t)n_pts * 8 + (size_t)n_pts * 12 + (size_t)nb * 12;
-    char *base = reinterpret_cast<char *>(seg_lds) + (size_t)wv * ((per_wave + 15) & ~(size_t)15);
+    char *base = wave_lds(segments_lds(n_pts, nb));
     double *cum = reinterpret_cast<double *>(base);
     float *pts = reinterpret_cast<float *>(base + (size_t)n_pts * 8);
     float *res = pts + 3 * (size_t)n_pts;
-    const int waves = (BLOCK / 64) * gridDim.x;
-    const int nseg = n_pts - 1;
-    for (int row = blockIdx.x * (BLOCK / 64) + wv; row < n; row += waves) {
+    const int lane = threadIdx.x & 63;
+    wave_rows(n, [&](int row) {
         const long long g = ids ? ids[(size_t)row * id_stride] : row;
         const float *p = hist + g * row_pitch;
         for (int j = lane; j < n_pts; j += 64) {
@@ -117,182 +233,30 @@ __global__ __launch_bounds__(BLOCK) void k_oracle_segments(
             pts[3 * j + 1] = y;
             pts[3 * j + 2] = z;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // blocked scan of the segment lengths, as k_resample
-        const int per = (nseg + 63) >> 6;
-        const int lo = min(lane * per, nseg), hi = min(lo + per, nseg);
-        double local = 0.0;
-        for (int j = lo; j < hi; ++j) {
-            const double dx = (double)pts[3 * (j + 1) + 0] - (double)pts[3 * j + 0];
-            const double dy = (double)pts[3 * (j + 1) + 1] - (double)pts[3 * j + 1];
-            const double dz = (double)pts[3 * (j + 1) + 2] - (double)pts[3 * j + 2];
-            local = local + sqrt((dx * dx + dy * dy) + dz * dz);
-            cum[j + 1] = local;
-        }
-        double before = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double up = __shfl_up(before, off);
-            if (lane >= off) before = before + up;
-        }
-        before = before - local;
-        for (int j = lo; j < hi; ++j) cum[j + 1] = cum[j + 1] + before;
-        if (lane == 0) cum[0] = 0.0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double total = cum[nseg];
-        for (int k = lane; k < nb; k += 64) {
-            float x, y, z;
-            if (k == nb - 1 || nseg == 0) {
-                x = pts[3 * nseg + 0];
-                y = pts[3 * nseg + 1];
-                z = pts[3 * nseg + 2];
-            } else {
-                const double target = total * ((double)k / (double)(nb - 1));
-                int a = 0, b = nseg;
-                while (a < b) {
-                    const int mid = (a + b) >> 1;
-                    if (cum[mid + 1] <= target) a = mid + 1;
-                    else b = mid;
-                }
-                const int j = min(a, nseg - 1);
-                const double c0 = cum[j], c1 = cum[j + 1];
-                const double den = c1 - c0;
-                const double r = den > 0.0 ? (target - c0) / den : 0.0;
-                const double ax = pts[3 * j + 0], ay = pts[3 * j + 1], az = pts[3 * j + 2];
-                const double bx = pts[3 * j + 3], by = pts[3 * j + 4], bz = pts[3 * j + 5];
-                x = (float)(ax + r * (bx - ax));
-                y = (float)(ay + r * (by - ay));
-                z = (float)(az + r * (bz - az));
-            }
-            res[3 * k + 0] = x;
-            res[3 * k + 1] = y;
-            res[3 * k + 2] = z;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        float *o = dirs + (size_t)row * (size_t)(nb - 1) * 3;
-        for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = res[e + 3] - res[e];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();        // the LDS rows are reused by the next streamline
-    }
+        wave_sync();
+        resample_row(CumStored{cum}, pts, n_pts - 1, nb, res, lane);
+        difference_row(res, nb, dirs + (size_t)row * (size_t)(nb - 1) * 3, lane);
+    });
 }
 
-// Ragged streamlines (points + int64 offsets) -> the network's input, one wavefront per
-// streamline, for any length: LDS holds the 64 exclusive lane prefixes of k_resample's
-// blocked scan, not the cumulative arc length itself.  A value cum[m] is recomputed on
-// demand by re-walking its owner lane's block, which gives the bits k_resample stores
-// (cum[j + 1] = local_j + before).  The target search replays k_resample's binary search
-// probe by probe while the interval spans several lane blocks (cum may step back by an
-// ulp at a block boundary, where `before` comes from a subtraction); inside one block cum
-// is non-decreasing, so the rest of that search is the first m with cum[m + 1] > target,
-// found by one walk of the block.
-__device__ inline double seg_len(const float *__restrict__ p, long long j) {
-    const double dx = (double)p[3 * (j + 1) + 0] - (double)p[3 * j + 0];
-    const double dy = (double)p[3 * (j + 1) + 1] - (double)p[3 * j + 1];
-    const double dz = (double)p[3 * (j + 1) + 2] - (double)p[3 * j + 2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-
-// cum[m], 1 <= m <= nseg: the blocked-scan prefix k_resample keeps in LDS
-__device__ inline double cum_at(const float *__restrict__ p, const double *pre, long long per,
-                                long long m) {
-    const long long seg = m - 1, owner = seg / per;
-    double local = 0.0;
-    for (long long j = owner * per; j <= seg; ++j) local = local + seg_len(p, j);
-    return local + pre[owner];
-}
-
+// Ragged streamlines (points + int64 offsets) -> the network's input, for any length
 __global__ __launch_bounds__(BLOCK) void k_oracle_segments_packed(
     const float *__restrict__ points, const long long *__restrict__ offsets, int n, int nb,
     float *__restrict__ dirs) {
-    extern __shared__ __align__(16) double pk_lds[];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // per wave: pre [64] doubles, res [3 nb] floats
-    const size_t per_wave = ((size_t)64 * 8 + (size_t)nb * 12 + 15) & ~(size_t)15;
-    char *base = reinterpret_cast<char *>(pk_lds) + (size_t)wv * per_wave;
+    char *base = wave_lds(packed_lds(nb));
     double *pre = reinterpret_cast<double *>(base);
     float *res = reinterpret_cast<float *>(base + 64 * 8);
-    const int waves = (BLOCK / 64) * gridDim.x;
-    for (int row = blockIdx.x * (BLOCK / 64) + wv; row < n; row += waves) {
+    const int lane = threadIdx.x & 63;
+    wave_rows(n, [&](int row) {
         const long long o0 = offsets[row], L = offsets[row + 1] - o0;
         float *o = dirs + (size_t)row * (size_t)(nb - 1) * 3;
         if (L < 1) {                            // nothing to resample: zero vectors
             for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = 0.0f;
-            continue;
+            return;
         }
-        const float *p = points + 3 * o0;
-        const long long nseg = L - 1;
-        const long long per = nseg > 0 ? (nseg + 63) >> 6 : 1;
-        const long long lo = min((long long)lane * per, nseg), hi = min(lo + per, nseg);
-        double local = 0.0;
-        for (long long j = lo; j < hi; ++j) local = local + seg_len(p, j);
-        double before = local;                  // inclusive scan over lanes, as k_resample
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double up = __shfl_up(before, off);
-            if (lane >= off) before = before + up;
-        }
-        pre[lane] = before - local;             // exclusive
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double total = nseg > 0 ? cum_at(p, pre, per, nseg) : 0.0;
-        for (int k = lane; k < nb; k += 64) {
-            float x, y, z;
-            if (k == nb - 1 || nseg == 0) {     // the last point is kept exactly
-                x = p[3 * nseg + 0];
-                y = p[3 * nseg + 1];
-                z = p[3 * nseg + 2];
-            } else {
-                const double target = total * ((double)k / (double)(nb - 1));
-                // k_resample: j = #{m in [0, nseg) : cum[m + 1] <= target} by binary search
-                long long a = 0, b = nseg;
-                while (a < b) {
-                    if (a / per == (b - 1) / per) {     // one block: cum is monotone here
-                        const long long owner = a / per;
-                        double acc = 0.0;
-                        long long first = b;
-                        for (long long j = owner * per; j < b; ++j) {
-                            acc = acc + seg_len(p, j);
-                            if (j >= a && acc + pre[owner] > target) {
-                                first = j;
-                                break;
-                            }
-                        }
-                        a = first;
-                        break;
-                    }
-                    const long long mid = (a + b) >> 1;
-                    if (cum_at(p, pre, per, mid + 1) <= target) a = mid + 1;
-                    else b = mid;
-                }
-                const long long j = min(a, nseg - 1);
-                const double c0 = j > 0 ? cum_at(p, pre, per, j) : 0.0;
-                const double c1 = cum_at(p, pre, per, j + 1);
-                const double den = c1 - c0;
-                const double r = den > 0.0 ? (target - c0) / den : 0.0;
-                const double ax = p[3 * j + 0], ay = p[3 * j + 1], az = p[3 * j + 2];
-                const double bx = p[3 * j + 3], by = p[3 * j + 4], bz = p[3 * j + 5];
-                x = (float)(ax + r * (bx - ax));
-                y = (float)(ay + r * (by - ay));
-                z = (float)(az + r * (bz - az));
-            }
-            res[3 * k + 0] = x;
-            res[3 * k + 1] = y;
-            res[3 * k + 2] = z;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        for (int e = lane; e < 3 * (nb - 1); e += 64) o[e] = res[e + 3] - res[e];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();        // pre / res are reused by the next streamline
-    }
+        resample_row(CumReplayed{pre}, points + 3 * o0, L - 1, nb, res, lane);
+        difference_row(res, nb, o, lane);
+    });
 }
 
 // OracleReward's sparse bonus (oracle_reward.py:84-93): term = 0 everywhere,
@@ -310,6 +274,35 @@ __global__ __launch_bounds__(BLOCK) void k_oracle_bonus(
 }
 }  // namespace
 
+int ttl_detail_reserve_lds(const void *kernel, size_t dynamic, LdsRoom *room) {
+    struct Seen {
+        const void *kernel;
+        int dev;
+        size_t limit, fixed, allowed;
+    };
+    static thread_local std::vector<Seen> seen;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Seen *k = nullptr;
+    for (Seen &s : seen)
+        if (s.kernel == kernel && s.dev == dev) k = &s;
+    if (!k) {
+        int limit = 0;
+        HIP_TRY(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        HIP_TRY(hipFuncGetAttributes(&fa, kernel));
+        seen.push_back(Seen{kernel, dev, (size_t)(limit > 0 ? limit : 0), fa.sharedSizeBytes, 0});
+        k = &seen.back();
+    }
+    *room = LdsRoom{k->fixed, k->limit, k->fixed + dynamic <= k->limit};
+    if (room->fits && dynamic > k->allowed) {
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)dynamic));
+        k->allowed = dynamic;
+    }
+    return TTL_OK;
+}
+
 extern "C" {
 
 int ttl_resample_streamlines(const float *points, int64_t row_pitch, const int32_t *lengths32,
@@ -318,14 +311,13 @@ int ttl_resample_streamlines(const float *points, int64_t row_pitch, const int32
     if (!points || !out || (!lengths32 && !lengths64) || n < 1 || max_len < 1 ||
         nb_points < 2 || row_pitch < 3LL * max_len)
         return fail(TTL_ERR_INVALID, "ttl_resample_streamlines: bad arguments");
-    const size_t lds = (size_t)(BLOCK / 64) * (size_t)max_len * sizeof(double);
-    if (lds > 160u * 1024u)
+    const size_t lds = wave_lds_bytes(resample_lds(max_len));
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds((const void *)k_resample, lds, &room)) return rc;
+    if (!room.fits)
         return fail(TTL_ERR_INVALID, "ttl_resample_streamlines: %d points per row exceed the LDS",
                     max_len);
-    HIP_TRY(hipFuncSetAttribute((const void *)k_resample,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int want = (n + (BLOCK / 64) - 1) / (BLOCK / 64);
-    hipLaunchKernelGGL(k_resample, dim3(want < 4096 ? want : 4096), dim3(BLOCK), lds,
+    hipLaunchKernelGGL(k_resample, dim3(ttl_detail_wave_grid(n, 4096)), dim3(BLOCK), lds,
                        (hipStream_t)hip_stream, points, (long long)row_pitch, lengths32,
                        (const long long *)lengths64, n, max_len, nb_points, out);
     HIP_TRY(hipGetLastError());
@@ -338,27 +330,16 @@ int ttl_oracle_segments(const float *history, int64_t row_pitch, const int32_t *
     if (!history || !dirs_out || n < 1 || n_points < 1 || nb_points < 2 ||
         row_pitch < 3LL * n_points || (ids && id_stride < 1))
         return fail(TTL_ERR_INVALID, "ttl_oracle_segments: bad arguments");
-    const size_t per_wave =
-        (((size_t)n_points * 20 + (size_t)nb_points * 12) + 15) & ~(size_t)15;
-    const size_t lds = (size_t)(BLOCK / 64) * per_wave;
-    if (lds > 160u * 1024u)
+    const size_t lds = wave_lds_bytes(segments_lds(n_points, nb_points));
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds((const void *)k_oracle_segments, lds, &room)) return rc;
+    if (!room.fits)
         return fail(TTL_ERR_INVALID, "ttl_oracle_segments: %d points per row exceed the LDS",
                     n_points);
-    // (raised when a call needs more than any before it: the attribute is per device and
-    // process, the call is on the training step's path)
-    static thread_local size_t lds_allowed[64] = {};
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || lds > lds_allowed[dev]) {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_oracle_segments,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) lds_allowed[dev] = lds;
-    }
     Lin L{};
     if (lin)
         for (int k = 0; k < 9; ++k) L.m[k] = lin[k];
-    const int want = (n + (BLOCK / 64) - 1) / (BLOCK / 64);
-    hipLaunchKernelGGL(k_oracle_segments, dim3(want < 8192 ? want : 8192), dim3(BLOCK), lds,
+    hipLaunchKernelGGL(k_oracle_segments, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK), lds,
                        (hipStream_t)hip_stream, history, (long long)row_pitch, ids, id_stride, n,
                        n_points, lin ? 1 : 0, L, nb_points, dirs_out);
     HIP_TRY(hipGetLastError());
@@ -369,18 +350,16 @@ int ttl_oracle_segments_packed(const float *points, const int64_t *offsets, int3
                                int32_t nb_points, float *dirs_out, void *hip_stream) {
     if (!points || !offsets || !dirs_out || n < 1 || nb_points < 2)
         return fail(TTL_ERR_INVALID, "ttl_oracle_segments_packed: bad arguments");
-    const size_t per_wave = ((size_t)64 * 8 + (size_t)nb_points * 12 + 15) & ~(size_t)15;
-    const size_t lds = (size_t)(BLOCK / 64) * per_wave;
-    if (lds > 160u * 1024u)
+    const size_t lds = wave_lds_bytes(packed_lds(nb_points));
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds((const void *)k_oracle_segments_packed, lds, &room))
+        return rc;
+    if (!room.fits)
         return fail(TTL_ERR_INVALID, "ttl_oracle_segments_packed: %d output points exceed the LDS",
                     nb_points);
-    if (lds > 64u * 1024u)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_oracle_segments_packed,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int want = (n + (BLOCK / 64) - 1) / (BLOCK / 64);
-    hipLaunchKernelGGL(k_oracle_segments_packed, dim3(want < 8192 ? want : 8192), dim3(BLOCK),
-                       lds, (hipStream_t)hip_stream, points, (const long long *)offsets, n,
-                       nb_points, dirs_out);
+    hipLaunchKernelGGL(k_oracle_segments_packed, dim3(ttl_detail_wave_grid(n, 8192)),
+                       dim3(BLOCK), lds, (hipStream_t)hip_stream, points,
+                       (const long long *)offsets, n, nb_points, dirs_out);
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

@@ -20,13 +20,6 @@ constexpr int WAVES = BLOCK / 64;
 // wave); longer rows read the history from global memory instead
 constexpr int STAGE_PTS = 384;
 
-// orders this wave's LDS writes before its later LDS reads (the LDS executes
-// one wave's instructions in order; this keeps the compiler from moving them)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 struct D3 {
     double x, y, z;
 };
