@@ -586,7 +586,12 @@ TTL_API int ttl_oracle_segments_packed(const float *points, const int64_t *offse
  * steps that axis's index by sign(d_i) and marks the new voxel.  Voxels outside [0, dims)
  * are skipped, not clamped, and cost no work: per segment the work is the voxels marked
  * plus O(log dims).  Segments with a non-finite end mark nothing.  One wavefront per
- * streamline, one lane per segment; plain byte stores, no atomics. */
+ * streamline, one lane per segment; plain byte stores, no atomics.
+ * Edges (tests/test_coverage_reference.py): the gate is a float32 `>`, so a streamline
+ * with scores[i] == threshold or a NaN score is rejected and +Inf is accepted; a
+ * non-finite point costs only its own two segments (and its own mark when it is the
+ * first point), the rest of the streamline is walked; a row of 0 points marks nothing,
+ * a row of 1 point marks floor(c_0); ends may lie at any finite float32 distance. */
 TTL_API int ttl_tract_coverage(const float *points, const int64_t *offsets, int32_t n,
                                const float *scores, float threshold, const int32_t *dims,
                                uint8_t *visited, void *hip_stream);

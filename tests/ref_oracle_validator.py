@@ -5,6 +5,7 @@ include/ttl_hip.h defines it, the blocked-order float64 resampler of
 and the two numbers ``Oracle`` / ``Coverage``.  The library is built with
 -ffp-contract=off -fno-fast-math, so the same float64 operations here give
 the same bits."""
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -46,17 +47,57 @@ def _before(t0, ax0, t1, ax1):
     return t0 < t1 or (t0 == t1 and ax0 < ax1)
 
 
-def walk_segment(a, b, dims):
+# Named deviations of the bounded walk that a plausible kernel bug would
+# produce (``walk_segment(..., mutant=name)``), each one statement of the walk:
+SEGMENT_MUTANTS = (
+    'tie_higher_axis',        # the merge takes the higher axis on equal t
+    'exit_never_stops',       # X does not end the walk
+    'exit_on_t_only',         # X ends the walk on t alone (axis ignored on ties)
+    'entry_skips_E',          # the entry search also skips E itself
+    'desc_first_dim_minus_1',  # descending run starts at plane dim - 1
+    'desc_index_is_plane',    # descending index after = plane (no - 1)
+    't_not_refreshed',        # t of the stepped axis is not recomputed
+    'exit_plane_dim_minus_1',  # ascending exit plane dim - 1
+    't_float32',              # every t rounded to float32
+    'd_float32',              # d = b - a formed in float32
+)
+
+
+def walk_segment(a, b, dims, mutant=None):
     """The same voxels with the work bounded by the marked voxels plus
     O(log dims), statement for statement as ``walk_segment`` in
     csrc/ttl_coverage.hip (per axis: the run of planes whose crossing keeps
     that index inside; start every run at the last axis entering, stop at the
-    first axis leaving)."""
-    a = np.asarray(a, np.float32).astype(np.float64)
-    b = np.asarray(b, np.float32).astype(np.float64)
+    first axis leaving).
+
+    ``mutant`` (one of SEGMENT_MUTANTS) plants one deviation; the tests show
+    that each changes the marked set of cases the GPU test launches.  Three
+    further candidates change no marked set and are therefore not listed:
+    descending ``last = max(vb + 1, 0)`` (the extra crossing of plane 0 gives
+    index -1, which the in-volume test of the mark drops); ascending
+    ``first = max(va, 0)`` (the extra crossing re-marks the voxel the segment
+    starts in, which the previous segment or the first point has marked); and
+    E chosen on t alone (the other axis's tied crossing is then not skipped,
+    but the index of the axis entering later is still outside when it is
+    taken, so nothing is marked)."""
+    assert mutant is None or mutant in SEGMENT_MUTANTS, mutant
+    a32, b32 = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    a, b = a32.astype(np.float64), b32.astype(np.float64)
     if not (np.isfinite(a).all() and np.isfinite(b).all()):
         return []
     d = b - a
+    if mutant == 'd_float32':
+        with np.errstate(over='ignore'):
+            d = (b32 - a32).astype(np.float64)
+        if not np.isfinite(d).all():
+            return []
+    if mutant == 't_float32':
+        def tof(plane, i):
+            with np.errstate(over='ignore'):
+                return float(np.float32((float(plane) - a[i]) / d[i]))
+    else:
+        def tof(plane, i):
+            return (float(plane) - a[i]) / d[i]
     idx, cur, left, step = [0] * 3, [0] * 3, [0] * 3, [0] * 3
     et, eax, xt, xax = -np.inf, -1, np.inf, 3
     for i in range(3):
@@ -73,9 +114,11 @@ def walk_segment(a, b, dims):
         if vb > va:
             step[i], first, last = 1, max(va + 1, 0), min(vb, dim - 1)
             if vb >= dim:
-                exit_plane = dim
+                exit_plane = dim - 1 if mutant == 'exit_plane_dim_minus_1' else dim
         else:
             step[i], first, last = -1, min(va, dim), max(vb + 1, 1)
+            if mutant == 'desc_first_dim_minus_1':
+                first = min(va, dim - 1)
             if vb < 0:
                 exit_plane = 0
         left[i] = max((last - first) * step[i] + 1, 0)
@@ -83,11 +126,11 @@ def walk_segment(a, b, dims):
         if not inside:
             if left[i] == 0:
                 return []
-            t = (float(first) - a[i]) / d[i]
+            t = tof(first, i)
             if _before(et, eax, t, i):
                 et, eax = t, i
         if exit_plane is not None:
-            t = (float(exit_plane) - a[i]) / d[i]
+            t = tof(exit_plane, i)
             if _before(t, i, xt, xax):
                 xt, xax = t, i
     if eax >= 0:
@@ -97,8 +140,11 @@ def walk_segment(a, b, dims):
             lo, hi = 0, left[i]
             while lo < hi:
                 mid = (lo + hi) >> 1
-                t = (float(cur[i] + mid * step[i]) - a[i]) / d[i]
-                if _before(t, i, et, eax):
+                t = tof(cur[i] + mid * step[i], i)
+                skip = _before(t, i, et, eax)
+                if mutant == 'entry_skips_E':
+                    skip = not _before(et, eax, t, i)
+                if skip:
                     lo = mid + 1
                 else:
                     hi = mid
@@ -107,22 +153,69 @@ def walk_segment(a, b, dims):
                 idx[i] = plane if step[i] > 0 else plane - 1
                 cur[i] += lo * step[i]
                 left[i] -= lo
-    tn = [(float(cur[i]) - a[i]) / d[i] if left[i] else 0.0 for i in range(3)]
+    tn = [tof(cur[i], i) if left[i] else 0.0 for i in range(3)]
     out = []
     while True:
         m = -1
         for i in range(3):
-            if left[i] and (m < 0 or _before(tn[i], i, tn[m], m)):
+            if not left[i]:
+                continue
+            if mutant == 'tie_higher_axis':
+                if m < 0 or tn[i] <= tn[m]:
+                    m = i
+            elif m < 0 or _before(tn[i], i, tn[m], m):
                 m = i
-        if m < 0 or _before(xt, xax, tn[m], m):
+        if m < 0:
             break
-        idx[m] = cur[m] if step[m] > 0 else cur[m] - 1
+        if mutant == 'exit_never_stops':
+            pass
+        elif mutant == 'exit_on_t_only':
+            if xt < tn[m]:
+                break
+        elif _before(xt, xax, tn[m], m):
+            break
+        idx[m] = cur[m] if step[m] > 0 or mutant == 'desc_index_is_plane' else cur[m] - 1
         if _inside(idx, dims):
             out.append(tuple(idx))
         cur[m] += step[m]
         left[m] -= 1
-        if left[m]:
-            tn[m] = (float(cur[m]) - a[m]) / d[m]
+        if left[m] and mutant != 't_not_refreshed':
+            tn[m] = tof(cur[m], m)
+    return out
+
+
+def walk_segment_planes(a, b, dims):
+    """A third statement of the same voxels, valid at any magnitude and
+    independent of the bounded walk's structure (no entry, no exit, no search,
+    no clamped floor): floors as exact Python integers; on every axis whose
+    index changes, the planes 0 .. dims_i that lie between the two floors are
+    events (t, axis, order along the run, index after: the plane ascending,
+    the plane - 1 descending); sorted, each sets its axis's index, and the
+    voxel is marked when all three indices are inside.  Planes outside
+    0 .. dims_i move an index from outside to outside, so they never mark and
+    are left out: O(sum of dims) events wherever the ends lie."""
+    a = np.asarray(a, np.float32).astype(np.float64)
+    b = np.asarray(b, np.float32).astype(np.float64)
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return []
+    d = b - a
+    idx = [int(math.floor(v)) for v in a]
+    vb = [int(math.floor(v)) for v in b]
+    events = []
+    for i in range(3):
+        if vb[i] > idx[i]:
+            planes = range(max(idx[i] + 1, 0), min(vb[i], dims[i]) + 1)
+            events += [((float(beta) - a[i]) / d[i], i, k, beta) for k, beta in enumerate(planes)]
+        elif vb[i] < idx[i]:
+            planes = range(min(idx[i], dims[i]), max(vb[i] + 1, 0) - 1, -1)
+            events += [((float(beta) - a[i]) / d[i], i, k, beta - 1)
+                       for k, beta in enumerate(planes)]
+    events.sort()
+    out = []
+    for _, i, _, after in events:
+        idx[i] = after
+        if _inside(idx, dims):
+            out.append(tuple(idx))
     return out
 
 
@@ -146,8 +239,8 @@ def coverage_map(points, offsets, dims, accept=None, max_crossings=64):
     """visited (X, Y, Z) uint8 for the ragged tractogram (points (M, 3)
     float32, offsets (n + 1,)): the naive definition vectorised over segments
     (every crossing an event, sorted by (segment, t, axis, m)); segments with
-    more than ``max_crossings`` crossings or a non-finite end go through the
-    bounded scalar walk."""
+    more than ``max_crossings`` crossings or a non-finite end go through
+    ``walk_segment_planes``, so nothing here leans on the bounded walk."""
     X, Y, Z = (int(v) for v in dims)
     visited = np.zeros((X, Y, Z), np.uint8)
     pts = np.asarray(points, np.float32)
@@ -177,7 +270,7 @@ def coverage_map(points, offsets, dims, accept=None, max_crossings=64):
         ncross = np.where(fin[:, None], np.abs(vb - va), 0)
     big = fin & (ncross.sum(1) > max_crossings)
     for s in np.flatnonzero(big | ~fin):
-        for vox in walk_segment(pts[seg_start[s]], pts[seg_start[s] + 1], (X, Y, Z)):
+        for vox in walk_segment_planes(pts[seg_start[s]], pts[seg_start[s] + 1], (X, Y, Z)):
             visited[vox] = 1
     small = np.flatnonzero(fin & ~big)
     A, B, va, ncross = A[small], B[small], va[small], ncross[small].astype(np.int64)
@@ -212,12 +305,116 @@ def coverage_map(points, offsets, dims, accept=None, max_crossings=64):
     return visited
 
 
+WAVE, GRID_WAVES = 64, 4 * 8192     # lanes of a wave; waves of the largest grid
+
+# Named deviations of the kernel's outer loop (``coverage_rows(..., mutant=name)``)
+ROW_MUTANTS = (
+    'segments_past_64_dropped',   # the lane stride stops after one pass
+    'rows_past_grid_dropped',     # rows >= 4 * 8192 are never visited
+    'score_ge',                   # scores >= threshold accepted
+    'nan_score_accepted',         # the gate is `scores <= threshold -> skip`
+    'first_point_unmarked',
+    'first_point_clamped',        # floor of the first point clamped into the volume
+    'nonfinite_point_ends_row',   # a non-finite point drops the rest of the row
+)
+
+
+def coverage_rows(points, offsets, dims, scores=None, threshold=0.5, mutant=None):
+    """``k_tract_coverage`` row by row (its outer loop, restated): visited
+    (X, Y, Z) uint8.  The score gate compares float32 with float32; an empty
+    row marks nothing; the first point is marked when it is finite and inside;
+    every segment goes through the bounded walk.  ``mutant``: one of
+    ROW_MUTANTS, or one of SEGMENT_MUTANTS (handed to the walk)."""
+    assert mutant is None or mutant in ROW_MUTANTS + SEGMENT_MUTANTS, mutant
+    seg_mutant = mutant if mutant in SEGMENT_MUTANTS else None
+    dims = tuple(int(v) for v in dims)
+    visited = np.zeros(dims, np.uint8)
+    pts = np.asarray(points, np.float32).reshape(-1, 3)
+    offsets = np.asarray(offsets, np.int64)
+    thr = np.float32(threshold)
+    sc = None if scores is None else np.asarray(scores, np.float32)
+    for row in range(len(offsets) - 1):
+        if mutant == 'rows_past_grid_dropped' and row >= GRID_WAVES:
+            break
+        if sc is not None:
+            if mutant == 'score_ge':
+                skip = not (sc[row] >= thr)
+            elif mutant == 'nan_score_accepted':
+                skip = bool(sc[row] <= thr)
+            else:
+                skip = not (sc[row] > thr)
+            if skip:
+                continue
+        p = pts[offsets[row]:offsets[row + 1]]
+        L = len(p)
+        if L < 1:
+            continue
+        first = p[0].astype(np.float64)
+        if mutant != 'first_point_unmarked' and np.isfinite(first).all():
+            v = np.floor(first)
+            if mutant == 'first_point_clamped':
+                v = np.clip(v, 0, np.array(dims) - 1)
+            if _inside(v, dims):
+                visited[tuple(int(x) for x in v)] = 1
+        nseg = L - 1
+        if mutant == 'segments_past_64_dropped':
+            nseg = min(nseg, WAVE)
+        for j in range(nseg):
+            if mutant == 'nonfinite_point_ends_row' and not np.isfinite(p[j:j + 2]).all():
+                break
+            for vox in walk_segment(p[j], p[j + 1], dims, seg_mutant):
+                visited[vox] = 1
+    return visited
+
+
 def oracle_and_coverage(scores, visited, mask):
     """{'Oracle', 'Coverage'} from scores (n,), the visited map and the
     tracking mask (oracle_validator.py:48-56)."""
     scores = np.asarray(scores)
     return {'Oracle': float(np.mean(scores > 0.5)),
             'Coverage': float(np.count_nonzero(visited) / np.count_nonzero(mask))}
+
+
+# ------------------------------------------------------- shared test inputs
+def random_walks(rng, n, lo, hi, box, step=(0.5, 0.75), start=None):
+    """n random-walk streamlines of lo..hi points, steps of 0.5-0.75 voxel,
+    starting uniformly in [0, box)^3 (or in ``start``)."""
+    lines = []
+    for _ in range(n):
+        L = int(rng.integers(lo, hi + 1))
+        d = rng.normal(size=(L - 1, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        d *= rng.uniform(step[0], step[1], (L - 1, 1))
+        p0 = rng.uniform(0, box, 3) if start is None else rng.uniform(*start, 3)
+        lines.append(np.concatenate([p0[None], p0 + np.cumsum(d, 0)]).astype(np.float32))
+    return lines
+
+
+HAND = [   # (a, b, dims, voxels the segment enters)
+    # axis-aligned run
+    ((0.5, 0.5, 0.5), (3.5, 0.5, 0.5), (5, 5, 5), [(1, 0, 0), (2, 0, 0), (3, 0, 0)]),
+    # diagonal through an edge: the tie goes to the lower axis
+    ((0.5, 0.5, 0.5), (1.5, 1.5, 0.5), (4, 4, 4), [(1, 0, 0), (1, 1, 0)]),
+    ((2.5, 2.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(1, 2, 0), (1, 1, 0), (0, 1, 0), (0, 0, 0)]),
+    # points exactly on a face
+    ((1.0, 0.5, 0.5), (2.5, 0.5, 0.5), (4, 4, 4), [(2, 0, 0)]),
+    ((0.5, 0.5, 0.5), (1.0, 0.5, 0.5), (4, 4, 4), [(1, 0, 0)]),
+    ((1.0, 0.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0)]),
+    # negative coordinates: outside voxels are skipped, not clamped
+    ((-1.5, 0.5, 0.5), (1.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0), (1, 0, 0)]),
+    ((0.5, -0.25, 0.5), (0.5, -2.5, 0.5), (4, 4, 4), []),
+    # leaving the volume
+    ((3.5, 0.5, 0.5), (6.5, 0.5, 0.5), (5, 5, 5), [(4, 0, 0)]),
+    ((3.5, 3.5, 0.5), (5.5, 6.5, 0.5), (5, 5, 5), [(3, 4, 0), (4, 4, 0)]),
+    # zero length
+    ((1.25, 1.25, 1.25), (1.25, 1.25, 1.25), (4, 4, 4), []),
+    # a point 10^6 voxels away (both ends of the run outside on one side)
+    ((2.5, 2.5, 2.5), (2.5 + 1e6, 2.5 + 1e6, 2.5), (5, 5, 5),
+     [(3, 2, 2), (3, 3, 2), (4, 3, 2), (4, 4, 2)]),
+    ((-1e6, 2.5, 2.5), (3.5, 2.5, 2.5), (5, 5, 5),
+     [(0, 2, 2), (1, 2, 2), (2, 2, 2), (3, 2, 2)]),
+]
+
 
 
 # ---------------------------------------------------------------- resampler

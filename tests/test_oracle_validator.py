@@ -12,25 +12,12 @@ import pytest
 import torch
 
 import ref_oracle_validator as ref
+from ref_oracle_validator import HAND, random_walks
 
 DEV = 'cuda:0'
 
 
 # ------------------------------------------------------------------ helpers
-def random_walks(rng, n, lo, hi, box, step=(0.5, 0.75), start=None):
-    """n random-walk streamlines of lo..hi points, steps of 0.5-0.75 voxel,
-    starting uniformly in [0, box)^3 (or in ``start``)."""
-    lines = []
-    for _ in range(n):
-        L = int(rng.integers(lo, hi + 1))
-        d = rng.normal(size=(L - 1, 3))
-        d /= np.linalg.norm(d, axis=1, keepdims=True)
-        d *= rng.uniform(step[0], step[1], (L - 1, 1))
-        p0 = rng.uniform(0, box, 3) if start is None else rng.uniform(*start, 3)
-        lines.append(np.concatenate([p0[None], p0 + np.cumsum(d, 0)]).astype(np.float32))
-    return lines
-
-
 def env_for(mask, affine=None, reference=None):
     from tracktolearn_amd.datasets.utils import MRIDataVolume
     aff = np.eye(4) if affine is None else affine
@@ -38,32 +25,6 @@ def env_for(mask, affine=None, reference=None):
         tracking_mask=MRIDataVolume(mask, aff), affine_vox2rasmm=aff,
         reference=reference if reference is not None else
         {'affine': aff, 'shape': mask.shape[:3]})
-
-
-HAND = [   # (a, b, dims, voxels the segment enters)
-    # axis-aligned run
-    ((0.5, 0.5, 0.5), (3.5, 0.5, 0.5), (5, 5, 5), [(1, 0, 0), (2, 0, 0), (3, 0, 0)]),
-    # diagonal through an edge: the tie goes to the lower axis
-    ((0.5, 0.5, 0.5), (1.5, 1.5, 0.5), (4, 4, 4), [(1, 0, 0), (1, 1, 0)]),
-    ((2.5, 2.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(1, 2, 0), (1, 1, 0), (0, 1, 0), (0, 0, 0)]),
-    # points exactly on a face
-    ((1.0, 0.5, 0.5), (2.5, 0.5, 0.5), (4, 4, 4), [(2, 0, 0)]),
-    ((0.5, 0.5, 0.5), (1.0, 0.5, 0.5), (4, 4, 4), [(1, 0, 0)]),
-    ((1.0, 0.5, 0.5), (0.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0)]),
-    # negative coordinates: outside voxels are skipped, not clamped
-    ((-1.5, 0.5, 0.5), (1.5, 0.5, 0.5), (4, 4, 4), [(0, 0, 0), (1, 0, 0)]),
-    ((0.5, -0.25, 0.5), (0.5, -2.5, 0.5), (4, 4, 4), []),
-    # leaving the volume
-    ((3.5, 0.5, 0.5), (6.5, 0.5, 0.5), (5, 5, 5), [(4, 0, 0)]),
-    ((3.5, 3.5, 0.5), (5.5, 6.5, 0.5), (5, 5, 5), [(3, 4, 0), (4, 4, 0)]),
-    # zero length
-    ((1.25, 1.25, 1.25), (1.25, 1.25, 1.25), (4, 4, 4), []),
-    # a point 10^6 voxels away (both ends of the run outside on one side)
-    ((2.5, 2.5, 2.5), (2.5 + 1e6, 2.5 + 1e6, 2.5), (5, 5, 5),
-     [(3, 2, 2), (3, 3, 2), (4, 3, 2), (4, 4, 2)]),
-    ((-1e6, 2.5, 2.5), (3.5, 2.5, 2.5), (5, 5, 5),
-     [(0, 2, 2), (1, 2, 2), (2, 2, 2), (3, 2, 2)]),
-]
 
 
 # ----------------------------------------------------------------- CPU tests
