@@ -596,6 +596,64 @@ TTL_API int ttl_tract_coverage(const float *points, const int64_t *offsets, int3
                                const float *scores, float threshold, const int32_t *dims,
                                uint8_t *visited, void *hip_stream);
 
+/* The Tractometer validator (TrackToLearn/experiment/tractometer_validator.py: scilpy's
+ * segment_tractogram_from_roi and compute_tractometry with compute_ic = False, unique = True;
+ * scilpy's source is absent: restated here, parity unpinned).  Input is the
+ * ragged layout of ttl_tract_coverage: corner-origin voxel coordinates of the Tractometer's
+ * reference anatomy, dims = {X, Y, Z} (host memory).  The B = n_bundles bundles (1 .. 64,
+ * the order of scil_scoring_config.json) live in bit planes, uint64 [X * Y * Z] each, word
+ * (x * Y + y) * Z + z, bit b = bundle b: head, tail, all (all_mask; a bundle without one
+ * has its bit set in every word), any (any_mask), gt (gt_mask).  has_all / has_any name the
+ * bundles that have such a mask.  limits: device double [B][TTL_TRACTOMETER_LIMITS] =
+ * {length lo, hi; dir x lo, hi, y .., z ..; absdir x lo, hi, y .., z ..; angle; unused},
+ * -inf / +inf where the config sets none.  lin: host double [9], row-major linear part of
+ * the reference's voxel -> RAS mm affine.
+ *
+ * For streamline s with points c_0 .. c_{L-1} (float32 read as float64, all sums float64):
+ *   ends      e0 = floor(c_0), e1 = floor(c_{L-1}) (floor, not truncation: -0.3 is voxel
+ *             -1); an end that is non-finite or outside [0, dims) lies in no ROI.
+ *   connects(b) = (head_b[e0] & tail_b[e1]) | (tail_b[e0] & head_b[e1]).
+ *   V(s)      the in-volume voxels of the walk of ttl_tract_coverage: floor(c_0) and the
+ *             voxel entered at every plane crossing, same order, same ties.
+ *   within(b) every voxel of V(s) has bit b in all (tested for the bundles of has_all);
+ *   touches(b) some voxel of V(s) has bit b in any (tested for the bundles of has_any).
+ *   v_j = lin (c_{j+1} - c_j), each row ((m0 x + m1 y) + m2 z); length = sum |v_j|,
+ *   dir_k = |sum_j v_jk|, absdir_k = sum_j |v_jk|; limits are inclusive, lo <= x <= hi.
+ *   winding   dipy's, on the voxel coordinates: q_j = c_j - mean(c), S = sum q_j q_j^T,
+ *             u1, u2 the unit eigenvectors of its two largest eigenvalues (cyclic Jacobi,
+ *             a fixed number of sweeps), p_j = (q_j . u1, q_j . u2), winding = (180 / pi)
+ *             sum_j acos(clip(p_j . p_j+1 / (|p_j| |p_j+1|), -1, 1)); the bundle passes iff
+ *             winding < angle (strict; a NaN fails); angle = +inf: not tested.
+ *   valid(b)  = connects(b) and every criterion above that bundle b sets.
+ * ttl_tractometer_classify writes bundle[s] = the lowest b with valid(b), else -1, and
+ * connected[s] = the bit set of b with connects(b) (int32 [n], uint64 [n], device).  A row
+ * of fewer than 2 points gives -1 and 0; a row with a non-finite point gives -1 (and the
+ * connected set of its ends when both are finite).  One wavefront per streamline: the ends
+ * first (four words; a row that connects nothing leaves here), then the sums and the limits
+ * (lane b tests bundle b), then the walk if a surviving bundle has an all / any mask, then
+ * the winding if one sets an angle.  The sums are butterfly reductions over the lanes, so a
+ * quantity within rounding of a limit may decide differently than another summation order.
+ *
+ * ttl_tractometer_overlap: every row with 0 <= bundle[s] < B ORs bit bundle[s] into
+ * visited_bits (uint64 [X * Y * Z], zeroed by the caller; only ones are ORed in, by
+ * device-wide atomics, so the result does not depend on the order) for the voxels of V(s);
+ * then counts[b] = {|M_b & G_b|, |M_b \ G_b|} (int64 [B][2], overwritten), M_b = the voxels
+ * with bit b in visited_bits, G_b = those with bit b in gt: integer atomics, exact.
+ * Both: device pointers unless stated; TTL_ERR_INVALID for a null pointer, n < 0, B outside
+ * 1 .. 64 or a dim < 1; n == 0 is a successful no-op (overlap still counts). */
+#define TTL_TRACTOMETER_LIMITS 16
+TTL_API int ttl_tractometer_classify(const float *points, const int64_t *offsets, int32_t n,
+                                     const int32_t *dims, int32_t n_bundles,
+                                     const uint64_t *head, const uint64_t *tail,
+                                     const uint64_t *all, const uint64_t *any,
+                                     uint64_t has_all, uint64_t has_any, const double *limits,
+                                     const double *lin, int32_t *bundle, uint64_t *connected,
+                                     void *hip_stream);
+TTL_API int ttl_tractometer_overlap(const float *points, const int64_t *offsets, int32_t n,
+                                    const int32_t *bundle, const int32_t *dims,
+                                    int32_t n_bundles, const uint64_t *gt,
+                                    uint64_t *visited_bits, int64_t *counts, void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

@@ -27,6 +27,7 @@ ORDER_ACTIVE = 0
 ORDER_PARTITION = 1
 ORDER_BY_POSITION = C.c_void_p(1)      # TTL_ORDER_BY_POSITION (ttl_env_reset)
 TRACT_FILE_TRK, TRACT_FILE_TCK = 0, 1
+TRACTOMETER_LIMITS = 16               # TTL_TRACTOMETER_LIMITS
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4
 
 
@@ -147,6 +148,14 @@ SYMBOLS = {
                                              C.c_void_p, C.c_void_p]),
     'ttl_tract_coverage': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float,
                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    'ttl_tractometer_classify': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_uint64, C.c_void_p, C.POINTER(C.c_double),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_tractometer_overlap': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

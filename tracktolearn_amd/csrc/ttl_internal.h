@@ -179,6 +179,146 @@ inline unsigned ttl_detail_wave_grid(long long n, int cap) {
     return (unsigned)(want < cap ? want : cap);
 }
 
+// ---------------------------------------------------------------------------
+// The voxel walk of a streamline (ttl_coverage.hip, ttl_tractometer.hip),
+// stated once: include/ttl_hip.h, ttl_tract_coverage.
+// ---------------------------------------------------------------------------
+struct WalkDims {
+    int d[3];
+};
+
+// visit(x, y, z) when the voxel lies inside the volume
+template <class Visit>
+__device__ __forceinline__ void walk_visit(const WalkDims &D, long long x, long long y,
+                                           long long z, Visit &visit) {
+    if (x < 0 || y < 0 || z < 0 || x >= D.d[0] || y >= D.d[1] || z >= D.d[2]) return;
+    visit((int)x, (int)y, (int)z);
+}
+
+// crossing order: increasing t, the lower axis first on ties
+__device__ inline bool walk_before(double t0, int ax0, double t1, int ax1) {
+    return t0 < t1 || (t0 == t1 && ax0 < ax1);
+}
+
+// floor of a finite coordinate, clamped to [-1, dim]: every test below (inside at the
+// start, first / last in-volume plane, leaving the volume) sees the same answer as with
+// the unclamped index, and the value fits an int
+__device__ inline long long walk_clamped_floor(double v, int dim) {
+    return (long long)fmin(fmax(floor(v), -1.0), (double)dim);
+}
+
+// The voxel of a streamline's first point: visited when the point is finite and inside.
+template <class Visit>
+__device__ __forceinline__ void walk_first_point(const float *__restrict__ p, const WalkDims &D,
+                                                 Visit visit) {
+    const double x = p[0], y = p[1], z = p[2];
+    if (isfinite(x) && isfinite(y) && isfinite(z))
+        walk_visit(D, walk_clamped_floor(x, D.d[0]), walk_clamped_floor(y, D.d[1]),
+                   walk_clamped_floor(z, D.d[2]), visit);
+}
+
+// The walk of segment a -> b (ttl_hip.h): the voxel entered at every integer-plane
+// crossing, crossings in increasing t = (plane - a_i) / d_i (float64, straight from the
+// formula), the lower axis first on ties.  Only the crossings during which all three
+// indices stay inside the volume are visited: on each axis the planes whose crossing
+// leaves that index inside form one run; the in-volume crossings are the part of the
+// merged order after the last axis enters (E) and up to the first axis leaving (X).  The
+// runs start at E by binary search (t is monotone along a run), so the work is the
+// voxels visited plus O(log dim).  visit(x, y, z) gets the in-volume voxels in walk order.
+template <class Visit>
+__device__ void walk_segment(const float *__restrict__ pa, const float *__restrict__ pb,
+                             const WalkDims &D, Visit visit) {
+    double a[3], b[3], d[3];
+    long long idx[3], cur[3], left[3];
+    int step[3];
+    double et = -INFINITY, xt = INFINITY;      // entry E / exit X: (t, axis)
+    int eax = -1, xax = 3;
+    for (int i = 0; i < 3; ++i) {
+        const double ai = pa[i], bi = pb[i];
+        if (!isfinite(ai) || !isfinite(bi)) return;
+        a[i] = ai;
+        b[i] = bi;
+        d[i] = bi - ai;
+    }
+    for (int i = 0; i < 3; ++i) {
+        const int dim = D.d[i];
+        const long long va = walk_clamped_floor(a[i], dim), vb = walk_clamped_floor(b[i], dim);
+        const bool inside = va >= 0 && va < dim;
+        idx[i] = va;
+        left[i] = 0;
+        if (va == vb) {
+            if (!inside) return;               // this index never enters the volume
+            continue;
+        }
+        long long first, last, exit_plane = -2;
+        if (vb > va) {                         // planes va+1 .. vb, index after = plane
+            step[i] = 1;
+            first = max(va + 1, 0LL);
+            last = min(vb, (long long)dim - 1);
+            if (vb >= dim) exit_plane = dim;
+        } else {                               // planes va .. vb+1, index after = plane - 1
+            step[i] = -1;
+            first = min(va, (long long)dim);
+            last = max(vb + 1, 1LL);
+            if (vb < 0) exit_plane = 0;
+        }
+        const long long count = (last - first) * step[i] + 1;
+        left[i] = count > 0 ? count : 0;
+        cur[i] = first;
+        if (!inside) {
+            if (left[i] == 0) return;
+            const double t = ((double)first - a[i]) / d[i];
+            if (walk_before(et, eax, t, i)) {
+                et = t;
+                eax = i;
+            }
+        }
+        if (exit_plane != -2) {
+            const double t = ((double)exit_plane - a[i]) / d[i];
+            if (walk_before(t, i, xt, xax)) {
+                xt = t;
+                xax = i;
+            }
+        }
+    }
+    if (eax >= 0) {                            // skip the crossings before E on every axis
+        for (int i = 0; i < 3; ++i) {
+            if (left[i] == 0) continue;
+            long long lo = 0, hi = left[i];    // first position with (t, i) >= E
+            while (lo < hi) {
+                const long long mid = (lo + hi) >> 1;
+                const double t = ((double)(cur[i] + mid * step[i]) - a[i]) / d[i];
+                if (walk_before(t, i, et, eax)) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo > 0) {
+                const long long plane = cur[i] + (lo - 1) * step[i];
+                idx[i] = step[i] > 0 ? plane : plane - 1;
+                cur[i] += lo * step[i];
+                left[i] -= lo;
+            }
+        }
+    }
+    double tn[3];
+    for (int i = 0; i < 3; ++i)
+        tn[i] = left[i] ? ((double)cur[i] - a[i]) / d[i] : 0.0;
+    for (;;) {
+        int m = -1;
+        for (int i = 0; i < 3; ++i)
+            if (left[i] && (m < 0 || walk_before(tn[i], i, tn[m], m))) m = i;
+        if (m < 0 || walk_before(xt, xax, tn[m], m)) break;
+        idx[m] = step[m] > 0 ? cur[m] : cur[m] - 1;
+        walk_visit(D, idx[0], idx[1], idx[2], visit);
+        cur[m] += step[m];
+        if (--left[m]) tn[m] = ((double)cur[m] - a[m]) / d[m];
+    }
+}
+
+// row-major index of voxel (x, y, z)
+__device__ __forceinline__ size_t walk_index(const WalkDims &D, int x, int y, int z) {
+    return ((size_t)x * (size_t)D.d[1] + (size_t)y) * (size_t)D.d[2] + (size_t)z;
+}
+
 // ttl_resample.hip: the one place that reserves dynamic LDS.  Static + dynamic
 // LDS of `kernel` against what the device gives a workgroup, BEFORE the launch:
 // the runtime does not reject a launch that asks for more -- the queue aborts.

@@ -108,6 +108,19 @@ def load_corner_voxels(filename, ref_affine):
     return corner_voxels_from_rasmm(points, ref_affine), offsets
 
 
+def packed_corner_voxels(tractogram_or_filename, env, ref_affine):
+    """Both input paths of a validator: a .trk / .tck file name, or the
+    in-memory ``Tractogram`` (or list of streamlines) in the tracker's voxel
+    coordinates -> (points, offsets) of the streamlines with >= 2 points in the
+    voxel space of ``ref_affine``, corner origin."""
+    if isinstance(tractogram_or_filename, (str, bytes, os.PathLike)):
+        return load_corner_voxels(os.fsdecode(tractogram_or_filename), ref_affine)
+    lines = tractogram_or_filename.streamlines \
+        if isinstance(tractogram_or_filename, Tractogram) else tractogram_or_filename
+    points, offsets = pack(keep_streamlines(lines))
+    return corner_voxels_from_tracker(points, env.affine_vox2rasmm, ref_affine), offsets
+
+
 def tract_coverage(points, offsets, dims, scores=None, threshold=0.5, visited=None):
     """``ttl_tract_coverage`` on device tensors: visited (X * Y * Z,) uint8,
     1 where an accepted streamline (scores > threshold; every one when scores
@@ -149,12 +162,7 @@ class OracleValidator(Validator):
         self.model = OracleSingleton(checkpoint, self.device)
 
     def _packed(self, tractogram_or_filename, env, ref_affine):
-        if isinstance(tractogram_or_filename, (str, bytes, os.PathLike)):
-            return load_corner_voxels(os.fsdecode(tractogram_or_filename), ref_affine)
-        lines = tractogram_or_filename.streamlines \
-            if isinstance(tractogram_or_filename, Tractogram) else tractogram_or_filename
-        points, offsets = pack(keep_streamlines(lines))
-        return corner_voxels_from_tracker(points, env.affine_vox2rasmm, ref_affine), offsets
+        return packed_corner_voxels(tractogram_or_filename, env, ref_affine)
 
     def __call__(self, tractogram_or_filename, env):
         ref_affine, dims = reference_space(env)

@@ -1,0 +1,401 @@
+"""TractometerValidator: bundle segmentation and overlap of a validation
+tractogram, on the GPU.
+
+Mirror of TrackToLearn/experiment/tractometer_validator.py.  The reference
+hands the saved .trk to scilpy on the CPU (``segment_tractogram_from_roi``,
+then ``compute_tractometry`` with ``compute_ic=False, unique=True``): every
+streamline's ends against the head and tail ROIs of every bundle, the length /
+orientation / angle / all_mask / any_mask criteria, a tract-count map per valid
+bundle and its intersection with the ground-truth mask.  Here the scoring data
+is packed once, at construction, into bit planes (bit b of a voxel's 64-bit
+word = bundle b) and a table of limits; a call uploads the tractogram once,
+runs ``ttl_tractometer_classify`` and ``ttl_tractometer_overlap`` and reads
+back a few hundred bytes.
+
+    VC = #{streamlines with a bundle} / n      NC = 1 - VC
+    VB = #{bundles with a streamline}          IC = IS = IB = 0
+    OL_b = |M_b & G_b| / |G_b|                 mean_OL over bundles with a gt_mask
+
+The definitions (ends, voxel walk, lengths, winding) are stated in
+include/ttl_hip.h (scilpy's source is absent: restated, parity unpinned;
+DESIGN 3.12).  ``__call__`` takes the reference's filename (.trk / .tck) or the
+in-memory ``Tractogram`` of ``Tracker.track_and_validate``.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import torch
+
+from tracktolearn_amd.experiment.oracle_validator import (corner_voxels_from_rasmm, pack,
+                                                          packed_corner_voxels, reference_space,
+                                                          tract_coverage)
+from tracktolearn_amd.experiment.validators import Validator
+
+def_len = [0, np.inf]
+MAX_BUNDLES = 64
+CONFIG_NAME = 'scil_scoring_config.json'
+# columns of a bundle's row of limits (TTL_TRACTOMETER_LIMITS doubles, ttl_hip.h)
+LIM_LENGTH, LIM_DIR, LIM_ABSDIR, LIM_ANGLE, LIM_COLUMNS = 0, 2, 8, 14, 16
+
+
+# ------------------------------------------------------------------- config
+def read_config_file(gt_config, gt_dir='', use_gt_masks_as_all_masks=False):
+    """tractometer_validator.py:69-229: (bundles, gt_masks, all_masks,
+    any_masks, roi_options, lengths, angles, orientation_lengths,
+    abs_orientation_lengths), one entry per bundle in the file's order, None
+    where the config sets nothing; file names joined to ``gt_dir``."""
+    def path(name):
+        return os.path.join(gt_dir, name) if gt_dir else name
+
+    with open(gt_config, 'r') as json_file:
+        config = json.load(json_file)
+    bundles = list(config.keys())
+    out = {k: [] for k in ('gt', 'all', 'any', 'roi', 'length', 'angle', 'dir', 'absdir')}
+    for bundle in bundles:
+        cfg = config[bundle]
+        if 'endpoints' not in cfg and 'head' not in cfg:
+            raise ValueError("Bundle configuration for bundle {} misses 'endpoints' or "
+                             "'head'/'tail'".format(bundle))
+        scalars = {}
+        gt_mask = all_mask = any_mask = roi_option = None
+        for key in cfg.keys():
+            if key in ('angle', 'length', 'length_x', 'length_y', 'length_z', 'length_x_abs',
+                       'length_y_abs', 'length_z_abs'):
+                scalars[key] = cfg[key]
+            elif key == 'gt_mask':
+                gt_mask = path(cfg['gt_mask'])
+                if use_gt_masks_as_all_masks:
+                    all_mask = gt_mask
+            elif key == 'all_mask':
+                if use_gt_masks_as_all_masks:
+                    raise ValueError('With the option --use_gt_masks_as_all_masks, you should '
+                                     'not add any all_mask in the config file.')
+                all_mask = path(cfg['all_mask'])
+            elif key == 'endpoints':
+                if 'head' in cfg or 'tail' in cfg:
+                    raise ValueError('Bundle {} has confusing keywords in the config file. '
+                                     'Please choose either endpoints OR head/tail.'
+                                     .format(bundle))
+                roi_option = {'gt_endpoints': path(cfg['endpoints'])}
+            elif key == 'head':
+                if 'tail' not in cfg:
+                    raise ValueError('You have provided the head for bundle {}, but not the '
+                                     'tail'.format(bundle))
+                roi_option = {'gt_head': path(cfg['head']), 'gt_tail': path(cfg['tail'])}
+            elif key == 'tail':
+                pass    # dealt with at head
+            elif key == 'any_mask':
+                any_mask = path(cfg['any_mask'])
+            else:
+                raise ValueError('Unrecognized value {} in the config file for bundle {}'
+                                 .format(key, bundle))
+        if roi_option is None:      # a tail without a head
+            raise ValueError("Bundle configuration for bundle {} misses 'endpoints' or "
+                             "'head'/'tail'".format(bundle))
+        out['angle'].append(scalars.get('angle'))
+        out['length'].append(scalars.get('length'))
+        for name, suffix in (('dir', ''), ('absdir', '_abs')):
+            xyz = [scalars.get(f'length_{a}{suffix}') for a in 'xyz']
+            out[name].append(None if all(v is None for v in xyz) else
+                             [v if v is not None else def_len for v in xyz])
+        out['gt'].append(gt_mask)
+        out['all'].append(all_mask)
+        out['any'].append(any_mask)
+        out['roi'].append(roi_option)
+    return (bundles, out['gt'], out['all'], out['any'], out['roi'], out['length'],
+            out['angle'], out['dir'], out['absdir'])
+
+
+def compute_endpoint_masks(roi_options):
+    """(tails, heads) file names per bundle (tractometer_validator.py:232-261).
+    A bundle given as ``endpoints`` has no head and tail to return: the
+    reference fails on it with a KeyError, here the error says why."""
+    for opt in roi_options:
+        if 'gt_head' not in opt or 'gt_tail' not in opt:
+            raise ValueError(
+                "a bundle configured with 'endpoints' has no 'head' and 'tail': the "
+                'Tractometer validator needs the two ROIs as separate masks '
+                f"(got {opt.get('gt_endpoints')!r})")
+    return [o['gt_tail'] for o in roi_options], [o['gt_head'] for o in roi_options]
+
+
+# -------------------------------------------------------------- host packing
+def dilate(mask, iterations):
+    """``scipy.ndimage.binary_dilation(mask, iterations=k)`` with its default
+    structure (the 6-neighbour cross; outside the volume counts as 0), written
+    with shifts.  k = 0: no dilation."""
+    m = np.asarray(mask) != 0
+    for _ in range(int(iterations)):
+        out = m.copy()
+        for axis in range(m.ndim):
+            lo = [slice(None)] * m.ndim
+            hi = [slice(None)] * m.ndim
+            lo[axis], hi[axis] = slice(None, -1), slice(1, None)
+            lo, hi = tuple(lo), tuple(hi)
+            out[hi] |= m[lo]
+            out[lo] |= m[hi]
+        m = out
+    return m
+
+
+def pack_bit_planes(masks, dims, missing=False):
+    """uint64 [X * Y * Z], C order: bit b is set where ``masks[b]`` is non-zero;
+    a bundle whose mask is None has its bit set everywhere when ``missing``."""
+    if len(masks) > MAX_BUNDLES:
+        raise ValueError(f'{len(masks)} bundles: the bit planes hold at most {MAX_BUNDLES}')
+    dims = tuple(int(v) for v in dims)
+    planes = np.zeros(dims, np.uint64)
+    for b, mask in enumerate(masks):
+        bit = np.uint64(1) << np.uint64(b)
+        if mask is None:
+            if missing:
+                planes |= bit
+            continue
+        mask = np.asarray(mask)
+        if mask.shape != dims:
+            raise ValueError(f'mask of bundle {b} has shape {mask.shape}, expected {dims}')
+        planes[mask != 0] |= bit
+    return planes.reshape(-1)
+
+
+def bundle_word(flags):
+    """The uint64 whose bit b is ``bool(flags[b])``."""
+    return sum(1 << b for b, f in enumerate(flags) if f)
+
+
+def limits_table(lengths, angles, orientation_lengths, abs_orientation_lengths):
+    """float64 [B][16] (ttl_hip.h): {length lo, hi; dir x, y, z lo, hi; absdir
+    x, y, z lo, hi; angle; unused}, -inf / +inf where nothing is set."""
+    B = len(lengths)
+    table = np.empty((B, LIM_COLUMNS), np.float64)
+    table[:, 0:LIM_ANGLE:2] = -np.inf
+    table[:, 1:LIM_ANGLE:2] = np.inf
+    table[:, LIM_ANGLE] = np.inf
+    table[:, LIM_ANGLE + 1] = 0.0
+    for b in range(B):
+        if lengths[b] is not None:
+            table[b, LIM_LENGTH:LIM_LENGTH + 2] = lengths[b]
+        for col, per_axis in ((LIM_DIR, orientation_lengths[b]),
+                              (LIM_ABSDIR, abs_orientation_lengths[b])):
+            if per_axis is not None:
+                for k in range(3):
+                    table[b, col + 2 * k:col + 2 * k + 2] = per_axis[k]
+        if angles[b] is not None:
+            table[b, LIM_ANGLE] = angles[b]
+    return table
+
+
+def metrics(n, per_bundle, counts, gt_sizes):
+    """The returned dict from integers: n streamlines, ``per_bundle[b]``
+    streamlines of bundle b, ``counts[b] = (|M_b & G_b|, |M_b \\ G_b|)``,
+    ``gt_sizes[b]`` = |G_b| or None without a gt_mask."""
+    vs = int(sum(int(c) for c in per_bundle))
+    vc = vs / n
+    ols = []
+    for b, size in enumerate(gt_sizes):
+        if size is None:
+            continue
+        ols.append(int(counts[b][0]) / size if size else 0.0)
+    return {'VC': vc, 'IC': 0, 'IS': 0, 'NC': 1 - vc,
+            'mean_OL': float(sum(ols) / len(ols)) if ols else 0.0,
+            'VB': int(sum(1 for c in per_bundle if int(c) > 0)), 'IB': 0}
+
+
+# ------------------------------------------------------------ device wrappers
+def _as_device_words(array, device):
+    """A uint64 NumPy array as an int64 device tensor (the same bits)."""
+    return torch.from_numpy(np.ascontiguousarray(array, np.uint64).view(np.int64)).to(device)
+
+
+class ScoringData(object):
+    """The packed scoring set on the device: bit planes head / tail / all / any
+    / gt (uint64 words held in int64 tensors), the limits table, and the words
+    naming the bundles with an all_mask / any_mask."""
+
+    def __init__(self, dims, heads, tails, all_masks, any_masks, gt_masks, limits, device):
+        self.dims = tuple(int(v) for v in dims)
+        self.n_bundles = len(heads)
+        if not 1 <= self.n_bundles <= MAX_BUNDLES:
+            raise ValueError(f'{self.n_bundles} bundles: the Tractometer validator takes 1 to '
+                             f'{MAX_BUNDLES}')
+        self.device = torch.device(device)
+        self.head = _as_device_words(pack_bit_planes(heads, dims), device)
+        self.tail = _as_device_words(pack_bit_planes(tails, dims), device)
+        self.all = _as_device_words(pack_bit_planes(all_masks, dims, missing=True), device)
+        self.any = _as_device_words(pack_bit_planes(any_masks, dims), device)
+        self.gt = _as_device_words(pack_bit_planes(gt_masks, dims), device)
+        self.has_all = bundle_word(m is not None for m in all_masks)
+        self.has_any = bundle_word(m is not None for m in any_masks)
+        limits = np.ascontiguousarray(limits, np.float64)
+        assert limits.shape == (self.n_bundles, LIM_COLUMNS), limits.shape
+        self.limits = torch.from_numpy(limits).to(device)
+        self.gt_sizes = [None if m is None else int(np.count_nonzero(m)) for m in gt_masks]
+
+
+def classify(points, offsets, data, lin):
+    """``ttl_tractometer_classify`` on device tensors: (bundle int32 [n],
+    connected int64 [n] holding the uint64 bit sets)."""
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    dev = points.device
+    n = int(offsets.shape[0]) - 1
+    bundle = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    connected = torch.empty(max(n, 0), dtype=torch.int64, device=dev)
+    if n <= 0:
+        return bundle, connected
+    pts = points.to(torch.float32).contiguous()
+    off = offsets.to(torch.int64).contiguous()
+    dims_c = (C.c_int32 * 3)(*data.dims)
+    lin_c = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.ttl_tractometer_classify(
+            pts.data_ptr(), off.data_ptr(), n, dims_c, data.n_bundles, data.head.data_ptr(),
+            data.tail.data_ptr(), data.all.data_ptr(), data.any.data_ptr(), data.has_all,
+            data.has_any, data.limits.data_ptr(), lin_c, bundle.data_ptr(),
+            connected.data_ptr(), stream), 'ttl_tractometer_classify')
+    return bundle, connected
+
+
+def overlap(points, offsets, bundle, data, visited_bits=None):
+    """``ttl_tractometer_overlap`` on device tensors: (counts int64 [B][2],
+    visited_bits int64 [X * Y * Z] holding the uint64 words).  ``visited_bits``
+    (zeroed) may be given."""
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    dev = points.device
+    n = int(offsets.shape[0]) - 1
+    X, Y, Z = data.dims
+    if visited_bits is None:
+        visited_bits = torch.zeros(X * Y * Z, dtype=torch.int64, device=dev)
+    counts = torch.empty((data.n_bundles, 2), dtype=torch.int64, device=dev)
+    pts = points.to(torch.float32).contiguous()
+    off = offsets.to(torch.int64).contiguous()
+    dims_c = (C.c_int32 * 3)(X, Y, Z)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.ttl_tractometer_overlap(
+            pts.data_ptr(), off.data_ptr(), max(n, 0), bundle.data_ptr(), dims_c,
+            data.n_bundles, data.gt.data_ptr(), visited_bits.data_ptr(), counts.data_ptr(),
+            stream), 'ttl_tractometer_overlap')
+    return counts, visited_bits
+
+
+# ---------------------------------------------------------------- validator
+def _load_image(path):
+    from tracktolearn_amd.io import nifti
+    return nifti.load(path)
+
+
+class TractometerValidator(Validator):
+    """``TractometerValidator(base_dir, reference, dilate_endpoints, device)
+    (tractogram_or_filename, env)`` -> ``{'VC', 'IC', 'IS', 'NC', 'mean_OL',
+    'VB', 'IB'}``, ``{}`` without a streamline of >= 2 points.  ``reference``:
+    the NIfTI file of the Tractometer's reference anatomy, or None to score in
+    the env's reference space (``reference_space``)."""
+
+    def __init__(self, base_dir, reference, dilate_endpoints=1, device='cuda'):
+        self.name = 'Tractometer'
+        self.gt_config = os.path.join(base_dir, CONFIG_NAME)
+        if not os.path.isfile(self.gt_config):
+            raise ValueError(f'the Tractometer validator needs {CONFIG_NAME} in the scoring '
+                             f'data, {self.gt_config} does not exist')
+        self.gt_dir = base_dir
+        self.reference = reference
+        self.dilation_factor = int(dilate_endpoints)
+        self.device = torch.device(device)
+        self.ref_affine = self.dims = None
+        if reference is not None:
+            img = _load_image(reference)
+            self.ref_affine = np.asarray(img.affine, np.float64)
+            self.dims = tuple(int(v) for v in img.shape[:3])
+
+        (self.bundle_names, gt_files, all_files, any_files, roi_options, self.bundle_lengths,
+         self.angles, self.orientation_lengths, self.abs_orientation_lengths) = \
+            read_config_file(self.gt_config, self.gt_dir, False)
+        if len(self.bundle_names) > MAX_BUNDLES:
+            raise ValueError(f'{len(self.bundle_names)} bundles in {self.gt_config}: the '
+                             f'Tractometer validator takes at most {MAX_BUNDLES}')
+        if not self.bundle_names:
+            raise ValueError(f'{self.gt_config} names no bundle')
+        self.gt_tails, self.gt_heads = compute_endpoint_masks(roi_options)
+
+        cache = {}
+        heads = [dilate(self._mask(f, cache), self.dilation_factor) for f in self.gt_heads]
+        tails = [dilate(self._mask(f, cache), self.dilation_factor) for f in self.gt_tails]
+        optional = [[None if f is None else self._mask(f, cache) for f in files]
+                    for files in (all_files, any_files, gt_files)]
+        limits = limits_table(self.bundle_lengths, self.angles, self.orientation_lengths,
+                              self.abs_orientation_lengths)
+        self.data = ScoringData(self.dims, heads, tails, *optional, limits, self.device)
+
+    def _mask(self, path, cache):
+        """A scoring file as a boolean volume of the reference's dims: a NIfTI
+        mask (non-zero = 1), or a .trk / .tck bundle turned into the map of the
+        voxels it passes through (``ttl_tract_coverage``)."""
+        if path in cache:
+            return cache[path]
+        lower = str(path).lower()
+        if lower.endswith(('.trk', '.tck')):
+            mask = self._mask_from_bundle(path)
+        else:
+            img = _load_image(path)
+            mask = np.asarray(img.dataobj) != 0
+            if self.dims is None:
+                self.dims = tuple(int(v) for v in mask.shape[:3])
+        if tuple(mask.shape) != tuple(self.dims):
+            raise ValueError(f'{path}: dimensions {tuple(mask.shape)} differ from the '
+                             f"reference's {tuple(self.dims)}")
+        cache[path] = mask
+        return mask
+
+    def _mask_from_bundle(self, path):
+        from tracktolearn_amd.io import streamlines as sio
+        if str(path).lower().endswith('.trk'):   # its own header is its reference
+            tract, header = sio.load_trk(path)
+            affine = np.asarray(header['voxel_to_rasmm'], np.float64)
+            dims = tuple(int(v) for v in header['dimensions'])
+        else:
+            if self.ref_affine is None:
+                raise ValueError(f'{path}: a .tck bundle needs --tractometer_reference')
+            tract, _ = sio.load_tck(path)
+            affine, dims = self.ref_affine, self.dims
+        if self.dims is None:
+            self.dims = dims
+        points, offsets = pack([np.asarray(s) for s in tract.streamlines if len(s) >= 1])
+        points = corner_voxels_from_rasmm(points, affine)
+        visited = tract_coverage(torch.from_numpy(points).to(self.device),
+                                 torch.from_numpy(offsets).to(self.device), dims)
+        return visited.cpu().numpy().reshape(dims) != 0
+
+    def space(self, env):
+        """(vox -> RAS mm affine, dims) the streamlines are scored in."""
+        if self.ref_affine is not None:
+            return self.ref_affine, self.dims
+        affine, dims = reference_space(env)
+        if tuple(dims) != tuple(self.dims):
+            raise ValueError(f"the env's reference has dimensions {tuple(dims)}, the scoring "
+                             f'data {tuple(self.dims)}: give --tractometer_reference')
+        return affine, dims
+
+    def __call__(self, tractogram_or_filename, env):
+        ref_affine, _ = self.space(env)
+        points, offsets = packed_corner_voxels(tractogram_or_filename, env, ref_affine)
+        n = len(offsets) - 1
+        if n == 0:
+            return {}
+        data = self.data
+        pts = torch.from_numpy(points).to(self.device)
+        off = torch.from_numpy(offsets).to(self.device)
+        bundle, _ = classify(pts, off, data, ref_affine[:3, :3])
+        counts, _ = overlap(pts, off, bundle, data)
+        per_bundle = torch.bincount(bundle.to(torch.int64) + 1, minlength=data.n_bundles + 1)
+        back = torch.cat([per_bundle[1:], counts.reshape(-1)]).cpu().numpy()
+        B = data.n_bundles
+        return metrics(n, back[:B], back[B:].reshape(B, 2), data.gt_sizes)
+
+
+__all__ = ['TractometerValidator', 'ScoringData', 'read_config_file', 'compute_endpoint_masks',
+           'dilate', 'pack_bit_planes', 'limits_table', 'metrics', 'classify', 'overlap']

@@ -6,9 +6,11 @@ groups) and of the parts of TrackToLearn/experiment/experiment.py it needs
 validators).  ``--oracle_validator`` scores every validation tractogram with
 TractOracle on the GPU (experiment/oracle_validator.py: ``Oracle`` and
 ``Coverage``, printed and kept in ``plots/oracle.npy`` / ``coverage.npy``).
-The Tractometer validator and Comet.ml are outside the hot-path scope
-(SURVEY 2.1): ``--use_comet`` and ``--tractometer_validator`` are accepted and
-ignored with a notice.
+``--tractometer_validator --scoring_data DIR`` segments it into the bundles of
+``DIR/scil_scoring_config.json`` on the GPU (experiment/tractometer_validator.py:
+``VC``, ``NC``, ``VB``, ``mean_OL`` ..., kept in ``plots/vc.npy`` etc.).
+Comet.ml is outside the hot-path scope: ``--use_comet`` is
+accepted and ignored with a notice.
 """
 import json
 import os
@@ -62,6 +64,14 @@ class TrackToLearnTraining(object):
         self.oracle_stopping_criterion = g['oracle_stopping_criterion']
         self.tractometer_validator = g['tractometer_validator']
         self.scoring_data = g['scoring_data']
+        self.tractometer_reference = g.get('tractometer_reference')
+        self.tractometer_dilate = g.get('tractometer_dilate', 1)
+        if self.tractometer_validator:
+            from tracktolearn_amd.experiment.tractometer_validator import CONFIG_NAME
+            if not self.scoring_data:
+                raise ValueError('--tractometer_validator needs --scoring_data')
+            if not os.path.isfile(pjoin(self.scoring_data, CONFIG_NAME)):
+                raise ValueError(f'--scoring_data {self.scoring_data} holds no {CONFIG_NAME}')
         self.compute_reward = True       # always during training
         self.fa_map = None
         self.comet_experiment = comet_experiment
@@ -70,10 +80,9 @@ class TrackToLearnTraining(object):
         self.use_comet = g['use_comet']
         self.validators = []
         self.score_monitors = {}
-        for flag in ('use_comet', 'tractometer_validator'):
-            if g[flag]:
-                print(f'NOTE: --{flag} is outside the scope of this build and '
-                      'is ignored')
+        if g['use_comet']:
+            print('NOTE: --use_comet is outside the scope of this build and '
+                  'is ignored')
 
         torch.manual_seed(self.rng_seed)
         np.random.seed(self.rng_seed)
@@ -222,19 +231,28 @@ class TrackToLearnTraining(object):
         t = 0
         train_tracker = Tracker(alg, self.n_actor, prob=0.0, compress=0.0)
         valid_tracker = Tracker(alg, self.n_actor, prob=1.0, compress=0.0)
-        # validators (train.py:216-226; the Tractometer stays out)
+        # validators (train.py:216-226), the Tractometer first as there; Comet
+        # is ignored: the scores are kept as plots/<name>.npy
         self.validators = []
         self.score_monitors = {}
+        p = self.experiment_path
+        if self.tractometer_validator:
+            from tracktolearn_amd.experiment.tractometer_validator import \
+                TractometerValidator
+            self.validators.append(TractometerValidator(
+                self.scoring_data, self.tractometer_reference,
+                dilate_endpoints=self.tractometer_dilate, device=self.device))
+            self.score_monitors.update({
+                key: LossHistory(key, key.lower(), p)
+                for key in ('VC', 'IC', 'NC', 'VB', 'IB', 'mean_OL')})
         if self.oracle_validator:
             from tracktolearn_amd.experiment.oracle_validator import \
                 OracleValidator
             self.validators.append(OracleValidator(self.oracle_checkpoint,
                                                    self.device))
-            # Comet is ignored: the scores are kept as plots/<name>.npy
-            p = self.experiment_path
-            self.score_monitors = {
+            self.score_monitors.update({
                 'Oracle': LossHistory('Oracle', 'oracle', p),
-                'Coverage': LossHistory('Coverage', 'coverage', p)}
+                'Coverage': LossHistory('Coverage', 'coverage', p)})
         self._validate(valid_tracker, valid_env, alg, i_episode)
         while i_episode < self.max_ep:
             self.last_episode = i_episode
@@ -334,7 +352,8 @@ def add_tractometer_args(parser: ArgumentParser):
     tractom.add_argument('--tractometer_reference', type=str, default=None,
                          help='Reference anatomy for the Tractometer.')
     tractom.add_argument('--tractometer_validator', action='store_true',
-                         help='Run tractometer during validation (ignored).')
+                         help='Run tractometer during validation (needs '
+                              '--scoring_data).')
     tractom.add_argument('--tractometer_dilate', default=1, type=int,
                          help='Dilation factor for the ROIs of the Tractometer.')
 
