@@ -40,6 +40,21 @@ def test_library_exports_every_declared_symbol():
         assert not [r[-1] for r in rows if 'ttl_detail' in r[-1]]
 
 
+def test_workspace_bytes_are_what_they_were():
+    """The size callers allocate for a handle: the literals are what the library
+    of commit 9ff48a7 answered (the last one with the size summed apart from the
+    layout ttl_env_create carves)."""
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    was = {0: 4326144, 1: 4330520, 255: 4365288, 256: 4365312, 257: 4369688, 700: 4433824,
+           65536: 14355200, 262144: 44442368, 1048576: 164791040}
+    got = {n: lib.ttl_env_workspace_bytes(n) for n in was}
+    assert got == was
+    assert lib.ttl_env_workspace_bytes(-1) == 0
+    sizes = [got[n] for n in sorted(got)]
+    assert sizes == sorted(sizes)
+
+
 def test_descriptor_layout_matches_header():
     """ctypes struct mirrors the C struct field for field (names, order)."""
     from tracktolearn_amd import _lib

@@ -22,6 +22,7 @@
 // the gather), ttl_peaks.hip (fODF peaks), ttl_resample.hip (oracle input).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -30,6 +31,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 #include "ttl_hip.h"
 
@@ -1358,64 +1360,69 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 }  // namespace
 
 struct ttl_env {
-    ttl_env_desc d;
-    EnvParams P;
-    int length;      // points per active streamline (reference: self.length)
-    int n_active;    // rows of the current continue_idx
-    int cur;         // 0: idx_a is continue_idx, 1: idx_b
-    int stepped;     // 0: idle, 2: step begun (advanced), 1: step done, awaiting harvest
-    int last_order;
-    int last_n;      // n_active of the pending step
-    uint8_t *last_done;  // done_out of the pending step (k_restop updates it)
-    int *proc[2];        // processing order of the state gather, double buffered
-    char *order_ws;      // scratch of the in-library order refresh (ttl_order.hip)
-    size_t order_ws_bytes;
-    int proc_cur;        // which proc buffer is current
-    int use_proc;        // a processing order was installed for this episode
-    int n_slots;         // length of the processing order (>= n_active: with the fused tail it keeps
-                         // the length of its last refresh, stopped streamlines leave holes)
-    int tail_fused;      // k_tail instead of k_prefix + k_proc_scatter (TTL_TAIL_FUSED) ...
-    int tail_fused_max;  // ... for processing orders of at most this many slots (TTL_TAIL_FUSED_MAX_ROWS)
-    int proc_min_rows;   // batches below this many rows drop the processing order (TTL_ORDER_MIN_ROWS)
-    int instep;          // > 0: k_tail steps re-bucket the order by brick on every instep-th step
-                         // of an episode (TTL_ORDER_INSTEP); 0: only the host-driven refresh
-    int instep_after;    // k_order_scatter behind the gather instead of in front (TTL_ORDER_INSTEP_AFTER)
-    int tail_riders;     // bit 0: the order scatter, bit 1: the row maps of a k_tail step run as
-                         // riders of the gather launch (TTL_TAIL_RIDERS, see TailRiders)
-    int last_riders;     // the same bits: what rode in the last step's gather launch
-    int instep_bins;     // bins of the brick raster, 0: too many for the in-step path
-    int instep_nb[3];    // the raster
-    int2 *ord_rec;       // [n_max] {bin and offset, next row} per slot, k_tail -> k_order_scatter
-    unsigned *ord_count[2];  // bin counts; the scatter of one re-bucket clears the other's
-    int ord_parity;      // which of them the next re-bucket counts into
+    ttl_env_desc d{};
+    EnvParams P{};
+    int length = 0;      // points per active streamline (reference: self.length)
+    int n_active = 0;    // rows of the current continue_idx
+    int cur = 0;         // 0: idx_a is continue_idx, 1: idx_b
+    int stepped = 0;     // 0: idle, 2: step begun (advanced), 1: step done, awaiting harvest
+    int last_order = TTL_ORDER_ACTIVE;
+    int last_n = 0;      // n_active of the pending step
+    uint8_t *last_done = nullptr;  // done_out of the pending step (k_restop updates it)
+    // The processing order of the state gather.  Its state -- use_proc, n_slots,
+    // proc_cur, ord_parity -- changes through the order_* operations below only.
+    int *proc[2] = {};   // double buffered: a step reads one and leaves the next order in the other
+    int proc_cur = 0;    // which proc buffer is current
+    int use_proc = 0;    // a processing order was installed for this episode
+    int n_slots = 0;     // length of the processing order (>= n_active: with the fused tail it keeps
+                         // the length of its last refresh, stopped streamlines leave holes);
+                         // -1: dense, as long as the rows (read through order_len)
+    char *order_ws = nullptr;      // scratch of the in-library order refresh (ttl_order.hip)
+    size_t order_ws_bytes = 0;
+    int instep_bins = 0;     // bins of the brick raster, 0: too many for the in-step path
+    int instep_nb[3] = {};   // the raster
+    int2 *ord_rec = nullptr; // [n_max] {bin and offset, next row} per slot, k_tail -> k_order_scatter
+    unsigned *ord_count[2] = {};  // bin counts; the scatter of one re-bucket clears the other's
+    int ord_parity = 0;      // which of them the next re-bucket counts into
+    int last_riders = 0;     // bits of tail_riders: what rode in the last step's gather launch
+    // Knobs (ttl_env_read_knobs; store_flavour, xcd_remap, xcd_rot, fuse_max_rows,
+    // persist_rows and slot_rec are knobs too and live in P, where the kernels read them)
+    int tail_fused = 0;      // k_tail instead of k_prefix + k_proc_scatter ...
+    int tail_fused_max = 0;  // ... for processing orders of at most this many slots
+    int proc_min_rows = 0;   // batches below this many rows drop the processing order
+    int instep = 0;          // > 0: k_tail steps re-bucket the order by brick on every instep-th step
+                             // of an episode; 0: only the host-driven refresh
+    int instep_after = 0;    // k_order_scatter behind the gather instead of in front
+    int tail_riders = 0;     // bit 0: the order scatter, bit 1: the row maps of a k_tail step run as
+                             // riders of the gather launch (see TailRiders)
+    int state_kernel = 0;    // 0: k_state (all 56 corner fetches), 3: k_state_dd with scalar tail stores, else k_state_dd
+    int fuse_small = 0;      // batches <= 16384 rows: one launch for prefix + gather
+    int poll_counts = 0;     // counts written by the kernel into the pinned buffer
+    int local_sort = 0;      // k_proc_scatter re-sorts each block's slots by current voxel
+    hipStream_t side = nullptr;      // carries the early device->host copy of the counts
+    hipEvent_t ev_prefix = nullptr;  // main stream: k_prefix done (counts are final)
+    hipEvent_t ev_counts = nullptr;  // side stream: counts have landed in host memory
+    int counts_pending = 0;          // 1: an early copy is in flight / unread, 2: the step's own
+                                     // kernel writes the caller's pinned buffer, host polls
+    const int32_t *host_counts = nullptr;  // where the counts land (caller's pinned memory)
+    const int32_t *host_probe = nullptr;   // pinned buffer whose device address is cached below
+    int *host_dev = nullptr;         // device address of host_probe, null if it has none
+    int poll_seq = 0;                // sequence number the polled word must reach
+    hipStream_t poll_stream = nullptr;
+    int n_exact = 0;           // n_active is the exact survivor count (read back)
+    int fr_cap = 0;            // > 0: free-running steps are being enqueued for this many rows
+    int *fr_host_word = nullptr;  // device address of the pinned words a free-running step reports to
+    int keyed = 0;             // ttl_env_set_noise: the steps draw their noise themselves ...
+    NoiseParams noise{};       // ... from this
+    int n_total = 0;           // rows of the last reset
+    const int *init_len = nullptr;  // ttl_env_reset_backward: a backward pass is on, rows replay while
+                                    // the length is below init_len[g]; null otherwise
     // optional per-kernel timing with HIP events on the caller's stream
-    int state_kernel; // 0: k_state (all 56 corner fetches), 3: k_state_dd with scalar tail stores, else k_state_dd
-    hipStream_t side;      // carries the early device->host copy of the counts
-    hipEvent_t ev_prefix;  // main stream: k_prefix done (counts are final)
-    hipEvent_t ev_counts;  // side stream: counts have landed in host memory
-    int counts_pending;    // 1: an early copy is in flight / unread, 2: the step's own
-                           // kernel writes the caller's pinned buffer, host polls
-    const int32_t *host_counts;  // where the counts land (caller's pinned memory)
-    const int32_t *host_probe;   // pinned buffer whose device address is cached below
-    int *host_dev;         // device address of host_probe, null if it has none
-    int poll_seq;          // sequence number the polled word must reach
-    hipStream_t poll_stream;
-    int fuse_small;        // batches <= 16384 rows: one launch for prefix + gather
-    int poll_counts;       // counts written by the kernel into the pinned buffer (TTL_POLL_COUNTS)
-    int local_sort;        // k_proc_scatter re-sorts each block's slots by current voxel
-    int n_exact;           // n_active is the exact survivor count (read back)
-    int fr_cap;            // > 0: free-running steps are being enqueued for this many rows
-    int *fr_host_word;     // device address of the pinned words a free-running step reports to
-    int keyed;             // ttl_env_set_noise: the steps draw their noise themselves ...
-    NoiseParams noise;     // ... from this
-    int n_total;           // rows of the last reset
-    const int *init_len;   // ttl_env_reset_backward: a backward pass is on, rows replay while the
-                           // length is below init_len[g]; null otherwise
-    int prof_on;
-    int prof_mask;    // bit k: time kernel class k
-    int prof_cap;     // event pairs available per kernel class
-    int prof_n[TTL_PROFILE_CLASSES];    // launches recorded: advance, prefix, state, proc_scatter
-    hipEvent_t *prof_ev[TTL_PROFILE_CLASSES];  // [2 * prof_cap] start/stop pairs
+    int prof_on = 0;
+    int prof_mask = (1 << TTL_PROFILE_CLASSES) - 1;  // bit k: time kernel class k
+    int prof_cap = 0;     // event pairs available per kernel class
+    int prof_n[TTL_PROFILE_CLASSES] = {};    // launches recorded: advance, prefix, state, proc_scatter
+    hipEvent_t *prof_ev[TTL_PROFILE_CLASSES] = {};  // [2 * prof_cap] start/stop pairs
 };
 
 // Measurement support (profiles/pmc_summary.py): with TTL_GATHER_ROWS_LOG=<file>
@@ -1459,6 +1466,104 @@ static void for_advance_variant(const ttl_env *env, F &&f) {
     else with_retrack(integral_constant<int, TTL_MODE_F32NORM>{}, std::false_type{});
 }
 
+// The workspace of a handle for n rows, stated once: every region in turn, each
+// 256-byte aligned, from `base`.  Fills the pointers of e (null ones under a null
+// base: ttl_env_workspace_bytes) and returns the end offset, the size a caller
+// must provide.  The two ord_count buffers lie side by side: ttl_env_rearm
+// clears both with one memset.
+static size_t ttl_env_carve(ttl_env &e, size_t n, void *base) {
+    EnvParams &P = e.P;
+    const size_t nb = (n + BLOCK - 1) / BLOCK + 1;      // per-block counts
+    size_t end = 0;
+    const auto rows = [&](auto *&region, size_t count, size_t per_row, size_t align = 256) {
+        region = base ? reinterpret_cast<std::remove_reference_t<decltype(region)>>(
+                            static_cast<char *>(base) + end) : nullptr;
+        end += align_up(count * per_row, align);
+    };
+    rows(P.stop, n, 1);
+    rows(P.rank, n, sizeof(int));
+    rows(P.surv_pos, n, sizeof(int));
+    rows(P.row_dest, n, sizeof(int));
+    rows(P.block_counts, nb, sizeof(int));
+    rows(P.proc_rank, n, sizeof(int));
+    rows(P.proc_counts, nb, sizeof(int));
+    rows(e.proc[0], n, sizeof(int));
+    rows(e.proc[1], n, sizeof(int));
+    rows(P.head, n, 4 * sizeof(float));
+    rows(P.slot_head, n, 4 * sizeof(float));
+    rows(P.last2, n, 8 * sizeof(float));
+    rows(P.pos_dest, n, 2 * sizeof(int));
+    rows(P.stop_list, n, 2 * sizeof(int));
+    rows(P.slot_dest, n, sizeof(int));
+    rows(P.counts, 64, sizeof(int));
+    e.order_ws_bytes = ttl_detail_order_workspace_bytes(n);
+    rows(e.order_ws, e.order_ws_bytes, 1, 1);       // (as long as ttl_order.hip asks, unrounded)
+    rows(e.ord_rec, n, sizeof(int2));
+    rows(e.ord_count[0], 1, ttl_detail_order_instep_count_bytes());
+    rows(e.ord_count[1], 1, ttl_detail_order_instep_count_bytes());
+    return end;
+}
+
+// The knobs of a handle, stated once (DESIGN.md Appendix B points here), a line
+// each: the field, the variable, its value when unset, how a set one is parsed.
+// Read when a handle is created, fixed for its life.
+static int knob(const char *name, int unset) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : unset;
+}
+static void ttl_env_read_knobs(ttl_env &e) {
+    EnvParams &P = e.P;
+    const int rider_kinds[4] = {0, 3, 1, 2};     // 0: none, 1: both, 2 / 3: one kind (measurement)
+    // (the tests lower it to reach the order's kernels with small batches)
+    e.proc_min_rows = knob("TTL_ORDER_MIN_ROWS", 8192);
+    // measured best of 1 / 2 / 3 / 4: profiles/r05_instep_ab.log
+    e.instep = std::max(knob("TTL_ORDER_INSTEP", 2), 0);
+    e.instep_after = knob("TTL_ORDER_INSTEP_AFTER", 0) != 0;
+    e.tail_riders = rider_kinds[knob("TTL_TAIL_RIDERS", 1) & 3];
+    e.state_kernel = knob("TTL_STATE_KERNEL", 4);
+    P.slot_rec = e.state_kernel != 2;
+    P.xcd_remap = knob("TTL_XCD_REMAP", 1);
+    P.xcd_rot = knob("TTL_XCD_ROTATE", 0) & 7;
+    P.store_flavour = knob("TTL_STORE_FLAVOUR", 0);
+    e.fuse_small = knob("TTL_FUSE_SMALL", 1);
+    P.fuse_max_rows = std::clamp(knob("TTL_FUSE_MAX_ROWS", 64 * BLOCK), BLOCK, TTL_FUSE_MAX_BLOCKS * BLOCK);
+    P.persist_rows = knob("TTL_GATHER_PERSIST_ROWS", 0);
+    e.tail_fused = knob("TTL_TAIL_FUSED", 1);
+    e.tail_fused_max = std::min(knob("TTL_TAIL_FUSED_MAX_ROWS", 262144), TTL_TAIL_MAX_BLOCKS * BLOCK);
+    e.local_sort = knob("TTL_LOCAL_SORT", 1);
+    e.poll_counts = knob("TTL_POLL_COUNTS", 1);
+}
+
+// floats of a state row
+static int64_t state_width(const ttl_env_desc &d) { return 7LL * d.n_coef + 3LL * d.n_dirs; }
+
+// continue_idx of the rows now active; ahead = 1: the buffer a step writes the
+// next one to (the harvest swaps them)
+static int *idx_of(const ttl_env *env, int ahead = 0) {
+    return (env->cur ^ ahead) ? env->d.idx_b : env->d.idx_a;
+}
+
+// The state of the processing order changes here and nowhere else.
+// an order of n slots stands in the current buffer: installed by a reset, a
+// refresh or the caller, or read by a k_tail step, which keeps its length
+static void order_holds(ttl_env *env, int n) { env->use_proc = 1, env->n_slots = n; }
+// the rest of the episode runs without one
+static void order_dropped(ttl_env *env) { env->use_proc = 0; }
+// a reset: the episode's order of n slots goes into buffer 0, or there is none;
+// the count buffers of the re-bucket are clear
+static void order_rearmed(ttl_env *env, bool installed, int n) {
+    env->proc_cur = env->ord_parity = 0;
+    installed ? order_holds(env, n) : order_dropped(env);
+}
+// the two-kernel tail left the next order without holes: as long as the next step's rows
+static void order_compacted(ttl_env *env) { env->n_slots = -1; }
+// so did the scatter of a re-bucket, from the counts the next re-bucket does not count into
+static void order_rebuilt(ttl_env *env) { env->ord_parity ^= 1, env->n_slots = -1; }
+// harvest: the order the step left becomes the current one
+static void order_swapped(ttl_env *env) { env->proc_cur ^= env->use_proc ? 1 : 0; }
+// slots of the order while `rows` rows are active (the one reader of n_slots)
+static int order_len(const ttl_env *env, int rows) { return env->n_slots < 0 ? rows : env->n_slots; }
+
 extern "C" {
 
 const char *ttl_last_error(void) { return g_err; }
@@ -1466,22 +1571,8 @@ uint32_t ttl_abi_version(void) { return TTL_ABI_VERSION; }
 size_t ttl_env_desc_size(void) { return sizeof(ttl_env_desc); }
 
 size_t ttl_env_workspace_bytes(int32_t n_max) {
-    if (n_max < 0) return 0;
-    const size_t n = (size_t)n_max;
-    const size_t nb = (n + BLOCK - 1) / BLOCK + 1;
-    size_t b = 0;
-    b += align_up(n, 256);                    // stop
-    b += 6 * align_up(n * sizeof(int), 256);  // rank, surv_pos, row_dest, proc_rank, proc x2
-    b += 2 * align_up(n * 4 * sizeof(float), 256); // head, slot_head
-    b += align_up(n * 8 * sizeof(float), 256); // last2
-    b += 2 * align_up(n * 2 * sizeof(int), 256); // pos_dest, stop_list
-    b += align_up(n * sizeof(int), 256);      // slot_dest
-    b += 2 * align_up(nb * sizeof(int), 256); // block_counts, proc_counts
-    b += 256;                                 // counts
-    b += ttl_detail_order_workspace_bytes(n); // order refresh scratch
-    b += align_up(n * sizeof(int2), 256);     // ord_rec
-    b += 2 * align_up(ttl_detail_order_instep_count_bytes(), 256);  // ord_count x2
-    return b;
+    ttl_env sized;
+    return n_max < 0 ? 0 : ttl_env_carve(sized, (size_t)n_max, nullptr);
 }
 
 int64_t ttl_sh_volume_records(const int32_t *dim, int32_t layout) {
@@ -1669,11 +1760,10 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
         (((uintptr_t)d.workspace) & 255))
         return fail(TTL_ERR_INVALID, "ttl_env_create: workspace too small or not 256B aligned");
 
-    ttl_env *e = new (std::nothrow) ttl_env;
+    ttl_env *e = new (std::nothrow) ttl_env();
     if (!e) return fail(TTL_ERR_INVALID, "ttl_env_create: out of host memory");
     e->d = d;
     EnvParams &P = e->P;
-    memset(&P, 0, sizeof(P));
     P.mode = d.mode;
     for (int a = 0; a < 3; ++a) {
         P.sh_dim[a] = d.sh_dim[a];
@@ -1709,108 +1799,9 @@ int ttl_env_create(const ttl_env_desc *desc, ttl_env **out) {
     P.flags = d.flags;
     P.lengths = d.lengths;
     P.dones = d.dones;
-    const size_t n = (size_t)d.n_max;
-    const size_t nb = (n + BLOCK - 1) / BLOCK + 1;
-    char *w = (char *)d.workspace;
-    P.stop = (uint8_t *)w;        w += align_up(n, 256);
-    P.rank = (int *)w;            w += align_up(n * sizeof(int), 256);
-    P.surv_pos = (int *)w;        w += align_up(n * sizeof(int), 256);
-    P.row_dest = (int *)w;        w += align_up(n * sizeof(int), 256);
-    P.block_counts = (int *)w;    w += align_up(nb * sizeof(int), 256);
-    P.proc_rank = (int *)w;       w += align_up(n * sizeof(int), 256);
-    P.proc_counts = (int *)w;     w += align_up(nb * sizeof(int), 256);
-    e->proc[0] = (int *)w;        w += align_up(n * sizeof(int), 256);
-    e->proc[1] = (int *)w;        w += align_up(n * sizeof(int), 256);
-    P.head = (float *)w;          w += align_up(n * 4 * sizeof(float), 256);
-    P.slot_head = (float *)w;     w += align_up(n * 4 * sizeof(float), 256);
-    P.last2 = (float *)w;         w += align_up(n * 8 * sizeof(float), 256);
-    P.pos_dest = (int *)w;        w += align_up(n * 2 * sizeof(int), 256);
-    P.stop_list = (int *)w;       w += align_up(n * 2 * sizeof(int), 256);
-    P.slot_dest = (int *)w;       w += align_up(n * sizeof(int), 256);
-    P.counts = (int *)w;          w += 256;
-    e->order_ws = w;
-    e->order_ws_bytes = ttl_detail_order_workspace_bytes(n);
-    w += e->order_ws_bytes;
-    e->ord_rec = (int2 *)w;       w += align_up(n * sizeof(int2), 256);
-    for (int k = 0; k < 2; ++k) {
-        e->ord_count[k] = (unsigned *)w;
-        w += align_up(ttl_detail_order_instep_count_bytes(), 256);
-    }
-    e->ord_parity = 0;
-    e->proc_min_rows = 8192;     // (the tests lower it to reach the order's kernels with small batches)
-    if (const char *v = getenv("TTL_ORDER_MIN_ROWS")) e->proc_min_rows = atoi(v);
-    e->instep = 2;      // measured best of 1 / 2 / 3 / 4: profiles/r05_instep_ab.log
-    if (const char *v = getenv("TTL_ORDER_INSTEP")) e->instep = atoi(v) > 0 ? atoi(v) : 0;
-    e->instep_after = 0;
-    if (const char *v = getenv("TTL_ORDER_INSTEP_AFTER")) e->instep_after = atoi(v) != 0;
+    ttl_env_carve(*e, (size_t)d.n_max, d.workspace);
+    ttl_env_read_knobs(*e);
     e->instep_bins = ttl_detail_order_bins(P, e->instep_nb);
-    e->tail_riders = 3;
-    if (const char *v = getenv("TTL_TAIL_RIDERS")) {      // 0: none, 1: both, 2 / 3: one kind (measurement)
-        const int kinds[4] = {0, 3, 1, 2};
-        e->tail_riders = kinds[atoi(v) & 3];
-    }
-    e->last_riders = 0;
-    e->length = 0;
-    e->n_active = 0;
-    e->cur = 0;
-    e->stepped = 0;
-    e->last_order = TTL_ORDER_ACTIVE;
-    e->last_n = 0;
-    e->last_done = nullptr;
-    e->proc_cur = 0;
-    e->use_proc = 0;
-    e->state_kernel = 4;
-    if (const char *v = getenv("TTL_STATE_KERNEL")) e->state_kernel = atoi(v);
-    P.slot_rec = e->state_kernel != 2;
-    P.xcd_remap = 1;
-    if (const char *v = getenv("TTL_XCD_REMAP")) P.xcd_remap = atoi(v);
-    P.xcd_rot = 0;
-    if (const char *v = getenv("TTL_XCD_ROTATE")) P.xcd_rot = atoi(v) & 7;
-    P.store_flavour = 0;
-    if (const char *v = getenv("TTL_STORE_FLAVOUR")) P.store_flavour = atoi(v);
-    e->side = nullptr;
-    e->ev_prefix = nullptr;
-    e->ev_counts = nullptr;
-    e->counts_pending = 0;
-    e->host_counts = nullptr;
-    e->host_probe = nullptr;
-    e->host_dev = nullptr;
-    e->poll_seq = 0;
-    e->poll_stream = nullptr;
-    e->fuse_small = 1;
-    if (const char *v = getenv("TTL_FUSE_SMALL")) e->fuse_small = atoi(v);
-    P.fuse_max_rows = 64 * BLOCK;
-    if (const char *v = getenv("TTL_FUSE_MAX_ROWS")) {
-        const int rows = atoi(v);
-        P.fuse_max_rows = rows < BLOCK ? BLOCK : rows > TTL_FUSE_MAX_BLOCKS * BLOCK
-                                                     ? TTL_FUSE_MAX_BLOCKS * BLOCK : rows;
-    }
-    e->local_sort = 1;
-    P.persist_rows = 0;
-    if (const char *v = getenv("TTL_GATHER_PERSIST_ROWS")) P.persist_rows = atoi(v);
-    e->tail_fused = 1;
-    if (const char *v = getenv("TTL_TAIL_FUSED")) e->tail_fused = atoi(v);
-    e->tail_fused_max = 262144;
-    if (const char *v = getenv("TTL_TAIL_FUSED_MAX_ROWS")) e->tail_fused_max = atoi(v);
-    if (e->tail_fused_max > TTL_TAIL_MAX_BLOCKS * BLOCK) e->tail_fused_max = TTL_TAIL_MAX_BLOCKS * BLOCK;
-    e->n_slots = 0;
-    if (const char *v = getenv("TTL_LOCAL_SORT")) e->local_sort = atoi(v);
-    e->poll_counts = 1;
-    if (const char *v = getenv("TTL_POLL_COUNTS")) e->poll_counts = atoi(v);
-    e->n_exact = 0;
-    e->fr_cap = 0;
-    e->fr_host_word = nullptr;
-    e->keyed = 0;
-    memset(&e->noise, 0, sizeof(e->noise));
-    e->n_total = 0;
-    e->init_len = nullptr;
-    e->prof_mask = (1 << TTL_PROFILE_CLASSES) - 1;
-    e->prof_on = 0;
-    e->prof_cap = 0;
-    for (int k = 0; k < TTL_PROFILE_CLASSES; ++k) {
-        e->prof_n[k] = 0;
-        e->prof_ev[k] = nullptr;
-    }
     *out = e;
     return TTL_OK;
 }
@@ -1886,8 +1877,41 @@ int ttl_scripted_actions(const float *state, int64_t state_pitch, int32_t dir_of
     return TTL_OK;
 }
 
+// What a reset does once the per-row records are written (k_reset,
+// k_retrack_reset): the handle's host state, the processing order and the first
+// state rows.
 static int ttl_env_rearm(ttl_env *env, int32_t n, const int32_t *processing_order,
-                         float *state_out, int64_t state_pitch, hipStream_t s);
+                         float *state_out, int64_t state_pitch, hipStream_t s) {
+    env->cur = 0;
+    env->length = 1;
+    env->n_active = n;
+    env->n_exact = 1;
+    env->stepped = 0;
+    env->fr_cap = 0;
+    order_rearmed(env, processing_order != nullptr, n);
+    if (env->instep && env->instep_bins) {
+        // the re-bucket steps count into buffers that each of them leaves clear
+        // for the next; an episode starts from both clear (the two lie side by
+        // side, see ttl_env_carve; also without an order now: one may be
+        // installed later on)
+        HIP_TRY(hipMemsetAsync(env->ord_count[0], 0,
+                               (size_t)((char *)env->ord_count[1] - (char *)env->ord_count[0]) +
+                                   ttl_detail_order_instep_count_bytes(), s));
+    }
+    if (processing_order == TTL_ORDER_BY_POSITION) {
+        // the library's own order: rows sorted by the brick of their seed
+        if (const int rc = ttl_detail_refresh_order(env->P, env->d.idx_a, n, env->order_ws,
+                                                    env->order_ws_bytes, env->proc[0], s))
+            return rc;
+    } else if (env->use_proc) {
+        HIP_TRY(hipMemcpyAsync(env->proc[0], processing_order, (size_t)n * sizeof(int32_t),
+                               hipMemcpyDeviceToDevice, s));
+    }
+    log_gather_rows(n);
+    return ttl_detail_launch_state(env->P, env->state_kernel, nullptr, nullptr,
+                                   env->use_proc ? env->proc[0] : nullptr, n, 1, state_out,
+                                   state_pitch, s);
+}
 
 int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
                   const int32_t *processing_order, float *state_out,
@@ -1897,10 +1921,9 @@ int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
     const ttl_env_desc &d = env->d;
     if (n < 1 || n > d.n_max)
         return fail(TTL_ERR_INVALID, "ttl_env_reset: n=%d outside [1, %d]", n, d.n_max);
-    const int64_t width = 7LL * d.n_coef + 3LL * d.n_dirs;
-    if (state_pitch < width)
+    if (state_pitch < state_width(d))
         return fail(TTL_ERR_INVALID, "ttl_env_reset: state_pitch %lld < %lld",
-                    (long long)state_pitch, (long long)width);
+                    (long long)state_pitch, (long long)state_width(d));
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t hist_bytes = (size_t)n * (size_t)(d.max_nb_steps + 1) * 3 * sizeof(float);
     HIP_TRY(hipMemsetAsync(d.streamlines, 0, hist_bytes, s));
@@ -1912,54 +1935,14 @@ int ttl_env_reset(ttl_env *env, const float *seeds, int32_t n,
     return ttl_env_rearm(env, n, processing_order, state_out, state_pitch, s);
 }
 
-// What a reset does once the per-row records are written (k_reset,
-// k_retrack_reset): the handle's host state, the processing order and the first
-// state rows.
-static int ttl_env_rearm(ttl_env *env, int32_t n, const int32_t *processing_order,
-                         float *state_out, int64_t state_pitch, hipStream_t s) {
-    const ttl_env_desc &d = env->d;
-    env->cur = 0;
-    env->length = 1;
-    env->n_active = n;
-    env->n_exact = 1;
-    env->stepped = 0;
-    env->fr_cap = 0;
-    env->proc_cur = 0;
-    env->use_proc = processing_order != nullptr;
-    env->n_slots = n;
-    if (env->instep && env->instep_bins) {
-        // the re-bucket steps count into buffers that each of them leaves clear
-        // for the next; an episode starts from both clear (the two lie side by
-        // side; also without an order now: one may be installed later on)
-        HIP_TRY(hipMemsetAsync(env->ord_count[0], 0,
-                               (size_t)((char *)env->ord_count[1] - (char *)env->ord_count[0]) +
-                                   ttl_detail_order_instep_count_bytes(), s));
-        env->ord_parity = 0;
-    }
-    if (processing_order == TTL_ORDER_BY_POSITION) {
-        // the library's own order: rows sorted by the brick of their seed
-        const int rc = ttl_detail_refresh_order(env->P, d.idx_a, n, env->order_ws,
-                                                env->order_ws_bytes, env->proc[0], s);
-        if (rc != TTL_OK) return rc;
-    } else if (env->use_proc) {
-        HIP_TRY(hipMemcpyAsync(env->proc[0], processing_order, (size_t)n * sizeof(int32_t),
-                               hipMemcpyDeviceToDevice, s));
-    }
-    log_gather_rows(n);
-    return ttl_detail_launch_state(env->P, env->state_kernel, nullptr, nullptr,
-                                   env->use_proc ? env->proc[0] : nullptr, n, 1, state_out,
-                                   state_pitch, s);
-}
-
 int ttl_env_reset_backward(ttl_env *env, int32_t *init_len, const int32_t *processing_order,
                            float *state_out, int64_t state_pitch, void *hip_stream) {
     if (!env || !init_len || !state_out)
         return fail(TTL_ERR_INVALID, "ttl_env_reset_backward: null argument");
     const ttl_env_desc &d = env->d;
-    const int64_t width = 7LL * d.n_coef + 3LL * d.n_dirs;
-    if (state_pitch < width)
+    if (state_pitch < state_width(d))
         return fail(TTL_ERR_INVALID, "ttl_env_reset_backward: state_pitch %lld < %lld",
-                    (long long)state_pitch, (long long)width);
+                    (long long)state_pitch, (long long)state_width(d));
     if (env->length < 1) return fail(TTL_ERR_STATE, "ttl_env_reset_backward: reset first");
     if (env->fr_cap)
         return fail(TTL_ERR_STATE, "ttl_env_reset_backward: free-running steps are enqueued, "
@@ -2019,7 +2002,7 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
         return fail(TTL_ERR_INVALID, "ttl_env_step: keyed noise is set (ttl_env_set_noise), "
                                      "the step takes no noise rows");
     hipStream_t s = (hipStream_t)hip_stream;
-    const int *idx = env->cur ? d.idx_b : d.idx_a;
+    const int *idx = idx_of(env);
     const int L = env->length;
     const int nb = (n_active + BLOCK - 1) / BLOCK;
     prof_mark(env, 0, 0, s);
@@ -2043,27 +2026,19 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
     return TTL_OK;
 }
 
-// whether steps over a processing order of `slots` slots re-bucket it themselves:
-// the knob, a brick raster the scatter can scan, and everything that makes
-// ttl_env_step_end take k_tail with the per-block sort
-static bool ttl_order_instep_on(const ttl_env *env, int slots) {
-    return env->instep > 0 && env->instep_bins > 0 && env->local_sort && env->tail_fused &&
-           env->P.slot_rec && ttl_detail_state_dedupes(env->P, env->state_kernel) &&
-           slots <= env->tail_fused_max && slots <= (1 << TTL_INSTEP_OFF_BITS);
+// whether a step over a processing order of `slots` slots takes k_tail (rows and
+// slots in one launch): the gather must read per-slot records and the block
+// counts fit k_tail's scan
+static bool ttl_takes_k_tail(const ttl_env *env, int slots) {
+    return env->tail_fused && env->P.slot_rec &&
+           ttl_detail_state_dedupes(env->P, env->state_kernel) && slots <= env->tail_fused_max;
 }
 
-// second half of a re-bucket step: the dense order of the survivors goes where
-// the next step reads it (k_tail<true> wrote nothing there); the order has no
-// holes afterwards, so it is as long as the next step's rows
-static int ttl_order_instep_scatter(ttl_env *env, hipStream_t s) {
-    const int rc = ttl_detail_order_scatter(env->ord_rec, env->n_slots,
-                                            env->ord_count[env->ord_parity],
-                                            env->ord_count[env->ord_parity ^ 1], env->instep_bins,
-                                            env->proc[env->proc_cur ^ 1], s);
-    if (rc != TTL_OK) return rc;
-    env->ord_parity ^= 1;
-    env->n_slots = -1;
-    return TTL_OK;
+// whether steps over a processing order of `slots` slots re-bucket it themselves:
+// the knob, a brick raster the scatter can scan, and k_tail with the per-block sort
+static bool ttl_order_instep_on(const ttl_env *env, int slots) {
+    return env->instep > 0 && env->instep_bins > 0 && env->local_sort &&
+           ttl_takes_k_tail(env, slots) && slots <= (1 << TTL_INSTEP_OFF_BITS);
 }
 
 // what a step is asked to write: the row order and the pitch of the state rows
@@ -2071,7 +2046,7 @@ static int ttl_order_instep_scatter(ttl_env *env, hipStream_t s) {
 static int ttl_check_step_rows(const ttl_env *env, int32_t order, int64_t state_pitch) {
     if (order != TTL_ORDER_ACTIVE && order != TTL_ORDER_PARTITION)
         return fail(TTL_ERR_INVALID, "ttl_env_step: bad order %d", order);
-    if (env && state_pitch < 7LL * env->d.n_coef + 3LL * env->d.n_dirs)
+    if (env && state_pitch < state_width(env->d))
         return fail(TTL_ERR_INVALID, "ttl_env_step: state_pitch too small");
     return TTL_OK;
 }
@@ -2082,7 +2057,7 @@ static int ttl_check_step_rows(const ttl_env *env, int32_t order, int64_t state_
 // stream, no copy kernel waiting for free CUs behind the gather, no API calls
 // between the step's launches; the host polls the sequence word.  Returns the
 // buffer's device address and the step's sequence number for the tail kernel,
-// or null: then ttl_counts_after_tail() ships the count.
+// or null: then the step ships the count with ttl_copy_counts().
 static int *ttl_counts_to_host(ttl_env *env, int32_t *host_counts, hipStream_t s, int *seq) {
     *seq = 0;
     if (!host_counts || !env->poll_counts) return nullptr;
@@ -2109,11 +2084,98 @@ static int *ttl_counts_to_host(ttl_env *env, int32_t *host_counts, hipStream_t s
     return env->host_dev;
 }
 
-// the fallback (buffer not device-visible): ship the count on a side stream as
-// soon as the kernel that computes it has run, in front of the gather
-static hipError_t ttl_counts_after_tail(ttl_env *env, int32_t *host_counts, const int *host_word,
-                                        hipStream_t s) {
-    return host_counts && !host_word ? ttl_copy_counts(env, host_counts, s) : hipSuccess;
+// The launches of a step's second half, decided before any of them is made.
+enum StepTail {
+    TAIL_ONE_LAUNCH,   // small batch without an order: prefix + compaction + gather in ONE launch
+    TAIL_K_TAIL,       // a processing order, rows and slots in one launch; the order keeps its
+                       // length between re-buckets (holes), the gather covers n_slots slots
+    TAIL_TWO_KERNEL,   // k_prefix, and with a processing order k_proc_scatter, which compacts it
+};
+enum StepScatter {     // the order scatter of a re-bucket step (second half of TTL_ORDER_INSTEP)
+    SCATTER_NONE,
+    SCATTER_RIDES,     // behind the gather's own workgroups, in its launch
+    SCATTER_BEFORE,    // k_order_scatter in front of the gather
+    SCATTER_AFTER,     // ... behind it (TTL_ORDER_INSTEP_AFTER)
+};
+struct StepPlan {
+    int n_active, n_pts;
+    StepTail tail;
+    bool drops_order;    // the processing order ends in front of this step
+    bool ordered;        // the step reads a processing order
+    bool rebucket;       // k_tail counts the survivors' bricks, a scatter writes the next order from them
+    StepScatter scatter;
+    bool row_maps_ride;  // the row maps run in the gather launch, from the bases k_tail scanned
+    int n_slots;         // slots of the order the step reads
+    int n_gather;        // rows or slots the gather covers
+    int row_blocks, slot_blocks, scatter_blocks;  // grids: k_prefix / row maps, k_tail, order scatter
+};
+
+static StepPlan ttl_plan_step(const ttl_env *env, int n_active, int n_pts) {
+    StepPlan p{};
+    p.n_active = p.n_gather = n_active;
+    p.n_pts = n_pts;
+    p.row_blocks = (n_active + BLOCK - 1) / BLOCK;
+    // a few thousand streamlines fit the caches in any order: stop paying for
+    // the processing order in the episode's tail (from 16 384 rows down the
+    // one-launch tail takes over)
+    const bool small = env->fuse_small && ttl_detail_can_fuse_tail(env->P, n_active);
+    p.drops_order = env->use_proc && (n_active < env->proc_min_rows || small);
+    p.ordered = env->use_proc && !p.drops_order;
+    p.tail = !p.ordered && small && env->state_kernel != 0 ? TAIL_ONE_LAUNCH : TAIL_TWO_KERNEL;
+    if (!p.ordered) return p;
+    p.n_slots = order_len(env, n_active);
+    if (!ttl_takes_k_tail(env, p.n_slots)) return p;
+    p.tail = TAIL_K_TAIL;
+    p.n_gather = p.n_slots;
+    p.slot_blocks = (p.n_slots + BLOCK - 1) / BLOCK;
+    p.rebucket = ttl_order_instep_on(env, p.n_slots) && (n_pts - 1) % env->instep == 0;
+    // what the gather launch can carry behind its own workgroups (TTL_TAIL_RIDERS):
+    // a grid of one workgroup per block, and LDS that leaves its occupancy alone
+    const int ride = env->P.persist_rows > 0 ? 0 : env->tail_riders;
+    p.row_maps_ride = (ride & 2) != 0;
+    if (p.rebucket) {
+        p.scatter_blocks = (p.n_slots + TTL_INSTEP_CHUNK - 1) / TTL_INSTEP_CHUNK;
+        p.scatter = env->instep_after ? SCATTER_AFTER
+                    : (ride & 1) && ttl_detail_order_scatter_lds(env->instep_bins) <= TTL_RIDER_MAX_LDS
+                        ? SCATTER_RIDES : SCATTER_BEFORE;
+    }
+    return p;
+}
+
+// what rides in the gather launch of a planned step
+static TailRiders ttl_plan_riders(const ttl_env *env, const StepPlan &p, int order,
+                                  const int *row_base) {
+    TailRiders r{};
+    if (p.scatter == SCATTER_RIDES) {
+        r.n_scatter = p.scatter_blocks;
+        r.rec = env->ord_rec;
+        r.count = env->ord_count[env->ord_parity];
+        r.count_other = env->ord_count[env->ord_parity ^ 1];
+        r.order_out = env->proc[env->proc_cur ^ 1];
+        r.n_slots = p.n_slots;
+        r.bins = env->instep_bins;
+    }
+    if (p.row_maps_ride) {
+        r.n_row_blocks = p.row_blocks;
+        r.row_base = row_base;
+        r.idx = idx_of(env);
+        r.idx_next = idx_of(env, 1);
+        r.n_active = p.n_active;
+        r.order = order;
+        r.n_pts = p.n_pts;
+    }
+    return r;
+}
+
+// the stand-alone order scatter of a re-bucket step: the dense order of the
+// survivors goes where the next step reads it (k_tail<true> wrote nothing there)
+static int ttl_order_instep_scatter(ttl_env *env, const StepPlan &p, hipStream_t s) {
+    const int rc = ttl_detail_order_scatter(env->ord_rec, p.n_slots,
+                                            env->ord_count[env->ord_parity],
+                                            env->ord_count[env->ord_parity ^ 1], env->instep_bins,
+                                            env->proc[env->proc_cur ^ 1], s);
+    if (rc == TTL_OK) order_rebuilt(env);
+    return rc;
 }
 
 int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
@@ -2124,144 +2186,89 @@ int ttl_env_step_end(ttl_env *env, const uint8_t *extra_flags, int32_t order,
     if (env->stepped != 2)
         return fail(TTL_ERR_STATE, "ttl_env_step_end: call ttl_env_step_begin first");
     if (const int rc = ttl_check_step_rows(env, order, state_pitch)) return rc;
-    const ttl_env_desc &d = env->d;
+    const StepPlan p = ttl_plan_step(env, env->last_n, env->length);
+    // the plan, carried out: launches in stream order, then what they leave behind
     hipStream_t s = (hipStream_t)hip_stream;
-    const int *idx = env->cur ? d.idx_b : d.idx_a;
-    int *idx_next = env->cur ? d.idx_a : d.idx_b;
-    const int n_active = env->last_n;
-    const int n_pts = env->length;
-    const int nb = (n_active + BLOCK - 1) / BLOCK;
+    int seq = 0;
+    int *host_word = ttl_counts_to_host(env, host_counts, s, &seq);
+    // (buffer not device-visible: the count leaves on a side stream as soon as
+    // the kernel that computes it has run, in front of the gather)
+    const bool copy_counts = host_counts && !host_word;
+    const int *idx = idx_of(env);
+    int *idx_next = idx_of(env, 1);
     if (extra_flags) {
-        hipLaunchKernelGGL(k_restop, dim3(nb), dim3(BLOCK), 0, s, env->P, idx,
-                           extra_flags, n_active, env->last_done);
+        hipLaunchKernelGGL(k_restop, dim3(p.row_blocks), dim3(BLOCK), 0, s, env->P, idx,
+                           extra_flags, p.n_active, env->last_done);
         HIP_TRY(hipGetLastError());
     }
-    // a few thousand streamlines fit the caches in any order: stop paying for
-    // the processing order in the episode's tail (from 16 384 rows down the
-    // one-launch tail below takes over)
-    if (env->use_proc && (n_active < env->proc_min_rows ||
-                          (env->fuse_small && ttl_detail_can_fuse_tail(env->P, n_active))))
-        env->use_proc = 0;
-    const int *proc = env->use_proc ? env->proc[env->proc_cur] : nullptr;
+    if (p.drops_order) order_dropped(env);
+    const int *proc = p.ordered ? env->proc[env->proc_cur] : nullptr;
+    int *proc_next = env->proc[env->proc_cur ^ 1];
     env->stepped = 1;
     env->last_order = order;
     env->last_riders = 0;
-    int seq = 0;
-    int *host_word = ttl_counts_to_host(env, host_counts, s, &seq);
-    if (!proc && env->fuse_small && env->state_kernel != 0 &&
-        ttl_detail_can_fuse_tail(env->P, n_active)) {
-        // small batch: prefix + compaction + gather in ONE launch
+    if (p.tail == TAIL_ONE_LAUNCH) {
         prof_mark(env, 2, 0, s);
-        const int rc = ttl_detail_launch_fused_tail(env->P, idx, idx_next, n_active, order,
-                                                    n_pts, state_out, state_pitch,
+        const int rc = ttl_detail_launch_fused_tail(env->P, idx, idx_next, p.n_active, order,
+                                                    p.n_pts, state_out, state_pitch,
                                                     host_word, seq, s);
         prof_mark(env, 2, 1, s);
-        if (rc != TTL_OK) return rc;
-        HIP_TRY(ttl_counts_after_tail(env, host_counts, host_word, s));
-        return TTL_OK;
+        if (rc == TTL_OK && copy_counts) HIP_TRY(ttl_copy_counts(env, host_counts, s));
+        return rc;
     }
-    // batches with a processing order: rows and slots in one launch (k_tail)
-    // when the gather reads per-slot records and the block counts fit its scan;
-    // the order then keeps its length between refreshes (holes), so the gather
-    // is launched for n_slots slots
-    int n_gather = n_active;
-    bool rebucket = false;
-    TailRiders riders{};
-    const bool fused_tail = proc && env->tail_fused && env->P.slot_rec &&
-                            ttl_detail_state_dedupes(env->P, env->state_kernel) &&
-                            (env->n_slots < 0 ? n_active : env->n_slots) <= env->tail_fused_max;
     // the two-kernel tail reads proc[j] for j < n_active without a hole check:
-    // an order that still holds holes (left by k_tail) must never reach it.
-    // The knobs that choose the tail are fixed per handle, so this cannot
-    // happen today; a setter that flips one mid-episode fails here instead
-    // of reading stop[-1]
-    if (!fused_tail && proc && env->n_slots > n_active)
+    // an order that still holds holes (left by k_tail) must never reach it
+    // (it cannot while the knobs that choose the tail are fixed per handle)
+    if (p.tail == TAIL_TWO_KERNEL && p.n_slots > p.n_active)
         return fail(TTL_ERR_STATE, "ttl_env_step: the processing order holds %d holes but "
                                    "the step tail was switched to the two-kernel form; "
-                                   "refresh the order first", env->n_slots - n_active);
+                                   "refresh the order first", p.n_slots - p.n_active);
+    // (the block bases k_tail scans for riding row maps go where the two-kernel
+    // tail keeps its slot counts: a k_tail step has no use for them)
+    int *row_base = p.row_maps_ride ? env->P.proc_counts : nullptr;
+    const TailRiders riders = p.tail == TAIL_K_TAIL ? ttl_plan_riders(env, p, order, row_base)
+                                                    : TailRiders{};
     prof_mark(env, 1, 0, s);
-    if (fused_tail) {
-        if (env->n_slots < 0) env->n_slots = n_active;     // the order was dense so far
-        n_gather = env->n_slots;
-        const int nbs = (env->n_slots + BLOCK - 1) / BLOCK;
-        // a re-bucket step (TTL_ORDER_INSTEP): k_tail counts the survivors' bricks
-        // on the way, k_order_scatter writes the next step's order from them
-        rebucket = ttl_order_instep_on(env, env->n_slots) && (n_pts - 1) % env->instep == 0;
-        unsigned *cnt = env->ord_count[env->ord_parity];
-        // what the gather launch can carry behind its own workgroups (TTL_TAIL_RIDERS):
-        // a grid of one workgroup per block, and LDS that leaves its occupancy alone
-        const int ride = env->P.persist_rows > 0 ? 0 : env->tail_riders;
-        if ((ride & 1) && rebucket && !env->instep_after &&
-            ttl_detail_order_scatter_lds(env->instep_bins) <= TTL_RIDER_MAX_LDS) {
-            riders.n_scatter = (env->n_slots + TTL_INSTEP_CHUNK - 1) / TTL_INSTEP_CHUNK;
-            riders.rec = env->ord_rec;
-            riders.count = cnt;
-            riders.count_other = env->ord_count[env->ord_parity ^ 1];
-            riders.order_out = env->proc[env->proc_cur ^ 1];
-            riders.n_slots = env->n_slots;
-            riders.bins = env->instep_bins;
-        }
-        // (the scanned bases go where the two-kernel tail keeps its slot counts:
-        // a k_tail step has no use for them)
-        int *row_base = nullptr;
-        if (ride & 2) {
-            row_base = env->P.proc_counts;
-            riders.n_row_blocks = nb;
-            riders.row_base = row_base;
-            riders.idx = idx;
-            riders.idx_next = idx_next;
-            riders.n_active = n_active;
-            riders.order = order;
-            riders.n_pts = n_pts;
-        }
-        if (rebucket)
-            hipLaunchKernelGGL(k_tail<true>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
-                               proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
-                               order, n_pts, host_word, seq, env->local_sort, env->ord_rec, cnt,
-                               env->instep_nb[0], env->instep_nb[1], env->instep_nb[2], row_base);
-        else
-            hipLaunchKernelGGL(k_tail<false>, dim3(nbs), dim3(BLOCK), 0, s, env->P, idx, idx_next,
-                               proc, env->proc[env->proc_cur ^ 1], n_active, env->n_slots, nb,
-                               order, n_pts, host_word, seq, env->local_sort, nullptr, nullptr,
-                               0, 0, 0, row_base);
+    if (p.tail == TAIL_K_TAIL) {
+        order_holds(env, p.n_slots);
+        const auto launch = [&](auto kernel, int2 *rec, unsigned *count, int nbx, int nby, int nbz) {
+            hipLaunchKernelGGL(kernel, dim3(p.slot_blocks), dim3(BLOCK), 0, s, env->P, idx, idx_next,
+                               proc, proc_next, p.n_active, p.n_slots, p.row_blocks, order, p.n_pts,
+                               host_word, seq, env->local_sort, rec, count, nbx, nby, nbz, row_base);
+        };
+        if (p.rebucket) launch(k_tail<true>, env->ord_rec, env->ord_count[env->ord_parity],
+                               env->instep_nb[0], env->instep_nb[1], env->instep_nb[2]);
+        else launch(k_tail<false>, nullptr, nullptr, 0, 0, 0);
     } else {
-        hipLaunchKernelGGL(k_prefix, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, idx_next,
-                           proc, n_active, nb, order, n_pts, host_word, seq);
+        hipLaunchKernelGGL(k_prefix, dim3(p.row_blocks), dim3(BLOCK), 0, s, env->P, idx, idx_next,
+                           proc, p.n_active, p.row_blocks, order, p.n_pts, host_word, seq);
     }
     prof_mark(env, 1, 1, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(ttl_counts_after_tail(env, host_counts, host_word, s));
-    if (fused_tail) {
-        if (rebucket && !env->instep_after && !riders.n_scatter) {
-            const int rc = ttl_order_instep_scatter(env, s);
-            if (rc != TTL_OK) return rc;
-        }
-    } else if (proc) {
+    if (copy_counts) HIP_TRY(ttl_copy_counts(env, host_counts, s));
+    if (p.scatter == SCATTER_BEFORE)
+        if (const int rc = ttl_order_instep_scatter(env, p, s)) return rc;
+    if (p.tail == TAIL_TWO_KERNEL && p.ordered) {
         // next step's processing order: this one, compacted in its own order
         // (ranks from k_prefix) and renumbered with the survivors' new row
         // ids; plus this step's per-slot records for the gather
         prof_mark(env, 3, 0, s);
-        hipLaunchKernelGGL(k_proc_scatter, dim3(nb), dim3(BLOCK), 0, s, env->P, idx, proc,
-                           env->proc[env->proc_cur ^ 1], n_active, nb,
+        hipLaunchKernelGGL(k_proc_scatter, dim3(p.row_blocks), dim3(BLOCK), 0, s, env->P, idx,
+                           proc, proc_next, p.n_active, p.row_blocks,
                            env->local_sort && env->P.slot_rec);
         prof_mark(env, 3, 1, s);
         HIP_TRY(hipGetLastError());
-        env->n_slots = -1;         // compacted: as long as the next step's active rows
+        order_compacted(env);
     }
     prof_mark(env, 2, 0, s);
-    log_gather_rows(n_active);
-    const bool ride = riders.n_scatter || riders.n_row_blocks;
+    log_gather_rows(p.n_active);
     const int rc = ttl_detail_launch_state(env->P, env->state_kernel, idx, env->P.row_dest, proc,
-                                           n_gather, n_pts, state_out, state_pitch, s,
-                                           ride ? &riders : nullptr);
+                                           p.n_gather, p.n_pts, state_out, state_pitch, s, &riders);
     prof_mark(env, 2, 1, s);
     if (rc != TTL_OK) return rc;
     env->last_riders = (riders.n_scatter ? 1 : 0) | (riders.n_row_blocks ? 2 : 0);
-    if (riders.n_scatter) {     // the order is rebuilt: what ttl_order_instep_scatter notes
-        env->ord_parity ^= 1;
-        env->n_slots = -1;
-    }
-    if (rebucket && env->instep_after) return ttl_order_instep_scatter(env, s);
+    if (p.scatter == SCATTER_RIDES) order_rebuilt(env);
+    if (p.scatter == SCATTER_AFTER) return ttl_order_instep_scatter(env, p, s);
     return rc;
 }
 
@@ -2271,10 +2278,10 @@ int ttl_env_step(ttl_env *env, const float *actions, const double *noise,
                  int32_t *host_counts, void *hip_stream) {
     // nothing is launched for a step whose output arguments are bad
     if (!state_out) return fail(TTL_ERR_INVALID, "ttl_env_step: null argument");
-    int rc = ttl_check_step_rows(env, order, state_pitch);
-    if (rc != TTL_OK) return rc;
-    rc = ttl_env_step_begin(env, actions, noise, n_active, reward_out, done_out, hip_stream);
-    if (rc != TTL_OK) return rc;
+    if (const int rc = ttl_check_step_rows(env, order, state_pitch)) return rc;
+    if (const int rc = ttl_env_step_begin(env, actions, noise, n_active, reward_out, done_out,
+                                          hip_stream))
+        return rc;
     return ttl_env_step_end(env, nullptr, order, state_out, state_pitch,
                             host_counts, hip_stream);
 }
@@ -2285,7 +2292,7 @@ int ttl_env_harvest(ttl_env *env, const float *state_in, float *state_out,
     if (env->stepped != 1) return fail(TTL_ERR_STATE, "ttl_env_harvest: no finished step to harvest");
     const ttl_env_desc &d = env->d;
     hipStream_t s = (hipStream_t)hip_stream;
-    const int *idx = env->cur ? d.idx_b : d.idx_a;
+    const int *idx = idx_of(env);
     const int n = env->last_n;
     const int nb = (n + BLOCK - 1) / BLOCK;
     if (env->last_order == TTL_ORDER_ACTIVE) {
@@ -2295,15 +2302,14 @@ int ttl_env_harvest(ttl_env *env, const float *state_in, float *state_out,
         if (state_out) {
             if (!state_in)
                 return fail(TTL_ERR_INVALID, "ttl_env_harvest: state_in needed to compact rows");
-            const int width = 7 * d.n_coef + 3 * d.n_dirs;
             hipLaunchKernelGGL(k_copy_rows, dim3((n + 3) / 4), dim3(BLOCK), 0, s,
-                               env->P, n, width, state_in, state_out,
+                               env->P, n, (int)state_width(d), state_in, state_out,
                                (long long)state_pitch);
             HIP_TRY(hipGetLastError());
         }
     }
     env->cur ^= 1;
-    if (env->use_proc) env->proc_cur ^= 1;
+    order_swapped(env);
     env->stepped = 0;
     // until ttl_env_wait_counts() has read the survivor count back, the
     // previous count is only an upper bound
@@ -2422,7 +2428,7 @@ int ttl_env_freerun_begin(ttl_env *env, int32_t *host_counts, void *hip_stream) 
         hipLaunchKernelGGL(k_fr_noise, dim3(1), dim3(1), 0, s, env->P, env->noise);
         HIP_TRY(hipGetLastError());
     }
-    env->use_proc = 0;
+    order_dropped(env);
     env->counts_pending = 0;
     env->fr_cap = env->n_active;
     return TTL_OK;
@@ -2438,8 +2444,7 @@ int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_rows, flo
         return fail(TTL_ERR_INVALID, "ttl_env_freerun_step: n_rows=%d outside [1, %d]", n_rows,
                     env->fr_cap);
     const ttl_env_desc &d = env->d;
-    const int64_t width = 7LL * d.n_coef + 3LL * d.n_dirs;
-    if (state_pitch < width)
+    if (state_pitch < state_width(d))
         return fail(TTL_ERR_INVALID, "ttl_env_freerun_step: state_pitch too small");
     hipStream_t s = (hipStream_t)hip_stream;
     const int n_cap = n_rows;
@@ -2570,15 +2575,14 @@ int ttl_env_set_processing_order(ttl_env *env, const int32_t *order, int32_t n,
                     n, env->n_active);
     HIP_TRY(hipMemcpyAsync(env->proc[env->proc_cur], order, (size_t)n * sizeof(int32_t),
                            hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
-    env->use_proc = 1;
-    env->n_slots = n;
+    order_holds(env, n);
     return TTL_OK;
 }
 
 int ttl_env_order_slots(ttl_env *env, int32_t *n_slots_out, int32_t *instep_out) {
     if (!env || !n_slots_out)
         return fail(TTL_ERR_INVALID, "ttl_env_order_slots: null argument");
-    const int slots = !env->use_proc ? 0 : env->n_slots < 0 ? env->n_active : env->n_slots;
+    const int slots = env->use_proc ? order_len(env, env->n_active) : 0;
     *n_slots_out = slots;
     if (instep_out) *instep_out = ttl_order_instep_on(env, slots) ? env->instep : 0;
     return TTL_OK;
@@ -2601,14 +2605,10 @@ int ttl_env_refresh_processing_order(ttl_env *env, void *hip_stream) {
         return fail(TTL_ERR_STATE, "ttl_env_refresh_processing_order: between harvest and step only");
     if (!env->n_exact)
         return fail(TTL_ERR_STATE, "ttl_env_refresh_processing_order: survivor count not read back yet");
-    const int *idx = env->cur ? env->d.idx_b : env->d.idx_a;
-    const int rc = ttl_detail_refresh_order(env->P, idx, env->n_active, env->order_ws,
+    const int rc = ttl_detail_refresh_order(env->P, idx_of(env), env->n_active, env->order_ws,
                                             env->order_ws_bytes, env->proc[env->proc_cur],
                                             (hipStream_t)hip_stream);
-    if (rc == TTL_OK) {
-        env->use_proc = 1;
-        env->n_slots = env->n_active;
-    }
+    if (rc == TTL_OK) order_holds(env, env->n_active);
     return rc;
 }
 
@@ -2628,7 +2628,7 @@ int ttl_pack_streamlines(const float *history, int64_t row_pitch, const int64_t 
 int ttl_env_view(ttl_env *env, const int32_t **continue_idx,
                  const int32_t **row_dest, int32_t *length) {
     if (!env) return fail(TTL_ERR_INVALID, "ttl_env_view: null handle");
-    if (continue_idx) *continue_idx = env->cur ? env->d.idx_b : env->d.idx_a;
+    if (continue_idx) *continue_idx = idx_of(env);
     if (row_dest) *row_dest = env->P.row_dest;
     if (length) *length = env->length;
     return TTL_OK;
