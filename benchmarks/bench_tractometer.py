@@ -8,13 +8,17 @@ scoring set of 21 bundles: head and tail ROIs are cubes of edge 14 about 12
 voxels apart, a third of the bundles have an all_mask, a third an any_mask,
 all have a length limit, a third an angle, all a gt_mask.  Per size one JSON
 line with the HIP-event time of ``upload`` (points and offsets, pageable host
-memory), ``classify`` (ttl_tractometer_classify) and ``overlap``
-(ttl_tractometer_overlap: memset, mark, count), the host time of packing, the
-share of rows that leave after the end test, the share that reach the walk's
-result with a bundle, and the metrics.  Best of ``--reps``.  A last line times
-the NumPy definition (tests/ref_tractometer.py) on a subsample on the CPU and
-scales it to the first size, labelled as such: the reference itself (scilpy)
-cannot run here.
+memory), ``classify`` (ttl_tractometer_classify), ``overlap``
+(ttl_tractometer_overlap: memset, mark, count) and ``invalid``
+(ttl_tractometer_invalid against the 42 head / tail ROIs of the 21 bundles, each
+bundle's own pair valid), the host time of packing, the share of rows that
+leave after the end test, the share that reach the walk's result with a bundle,
+the share that reach the invalid kernel's end test (no bundle) and that leave
+it with a pair, and the metrics (compute_ic).  ``device_ms``, which picks the
+best repetition, is classify + overlap as before.  Best of ``--reps``.  A last
+line times the NumPy definition (tests/ref_tractometer.py) on a subsample on
+the CPU and scales it to the first size, labelled as such: the reference itself
+(scilpy) cannot run here.
 """
 import argparse
 import json
@@ -69,7 +73,8 @@ def main(argv=None):
     from bench_oracle_validator import tractogram
     from tracktolearn_amd.experiment.oracle_validator import corner_voxels_from_tracker, pack
     from tracktolearn_amd.experiment.tractometer_validator import (ScoringData, classify,
-                                                                   limits_table, metrics, overlap)
+                                                                   invalid, limits_table,
+                                                                   metrics, overlap)
 
     dev = torch.device('cuda:0')
     D = 145
@@ -77,10 +82,16 @@ def main(argv=None):
     rng = np.random.default_rng(0)
     bundles = scoring_set(rng, D)
     cols = {k: [b[k] for b in bundles] for k in bundles[0]}
+    # the ROIs: every head, then every tail; bundle b joins b and N_BUNDLES + b
+    R = 2 * N_BUNDLES
+    valid = np.eye(R, dtype=bool)
+    for b in range(N_BUNDLES):
+        valid[b, N_BUNDLES + b] = valid[N_BUNDLES + b, b] = True
     t0 = time.perf_counter()
     data = ScoringData((D, D, D), cols['head'], cols['tail'], cols['all'], cols['any'],
                        cols['gt'], limits_table(cols['length'], cols['angle'], cols['dir'],
-                                                cols['absdir']), dev)
+                                                cols['absdir']), dev,
+                       roi_masks=cols['head'] + cols['tail'], valid=valid)
     torch.cuda.synchronize()
     setup_ms = 1e3 * (time.perf_counter() - t0)
     lin = aff[:3, :3]
@@ -96,7 +107,7 @@ def main(argv=None):
             p, o = pack(lines)
             p = corner_voxels_from_tracker(p, aff, aff)
             t1 = time.perf_counter()
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             visited = torch.zeros(D * D * D, dtype=torch.int64, device=dev)
             ev[0].record()
             pd, od = torch.from_numpy(p).to(dev), torch.from_numpy(o).to(dev)
@@ -105,26 +116,33 @@ def main(argv=None):
             ev[2].record()
             counts, _ = overlap(pd, od, bundle, data, visited)
             ev[3].record()
-            ev[3].synchronize()
+            pair = invalid(pd, od, bundle, data)
+            ev[4].record()
+            ev[4].synchronize()
             row = {'pack_host_ms': 1e3 * (t1 - t0), 'upload_ms': ev[0].elapsed_time(ev[1]),
                    'classify_ms': ev[1].elapsed_time(ev[2]),
-                   'overlap_ms': ev[2].elapsed_time(ev[3])}
+                   'overlap_ms': ev[2].elapsed_time(ev[3]),
+                   'invalid_ms': ev[3].elapsed_time(ev[4])}
             row['device_ms'] = row['classify_ms'] + row['overlap_ms']
             if best is None or row['device_ms'] < best[0]['device_ms']:
                 per = torch.bincount(bundle.to(torch.int64) + 1, minlength=N_BUNDLES + 1)
-                back = torch.cat([per[1:], counts.reshape(-1),
+                per_pair = torch.bincount(pair.to(torch.int64) + 1, minlength=R * R + 1)[1:]
+                back = torch.cat([per[1:], counts.reshape(-1), per_pair.sum().reshape(1),
+                                  (per_pair > 0).sum().reshape(1),
                                   (connected == 0).sum().reshape(1)]).cpu().numpy()
                 best = (row, back)
         row, back = best
         M = int(lens.sum())
-        result = metrics(n, back[:N_BUNDLES], back[N_BUNDLES:-1].reshape(N_BUNDLES, 2),
-                         data.gt_sizes)
+        result = metrics(n, back[:N_BUNDLES], back[N_BUNDLES:-3].reshape(N_BUNDLES, 2),
+                         data.gt_sizes, invalid=back[-3:-1])
         print(json.dumps({
             'object': 'tractometer_validator', 'streamlines': n, 'points': M,
-            'bundles': N_BUNDLES, 'scoring_setup_ms': round(setup_ms, 1),
+            'bundles': N_BUNDLES, 'rois': R, 'scoring_setup_ms': round(setup_ms, 1),
             **{k: round(v, 3) for k, v in row.items()},
             'left_after_end_test': round(int(back[-1]) / n, 4),
             'with_a_bundle': round(int(back[:N_BUNDLES].sum()) / n, 4),
+            'reach_invalid': round(1 - int(back[:N_BUNDLES].sum()) / n, 4),
+            'with_a_pair': round(int(back[-3]) / n, 4),
             'result': result, 'reps': args.reps,
             'device': torch.cuda.get_device_name(0)}), flush=True)
         if first is None:

@@ -654,6 +654,43 @@ TTL_API int ttl_tractometer_overlap(const float *points, const int64_t *offsets,
                                     int32_t n_bundles, const uint64_t *gt,
                                     uint64_t *visited_bits, int64_t *counts, void *hip_stream);
 
+/* The Tractometer's invalid connections (TTL_HAS_TRACTOMETER_IC; scilpy's
+ * compute_ic = True; its source is absent: this project's own statement, parity unpinned).
+ * The R = n_rois ROIs (2 .. TTL_TRACTOMETER_MAX_ROIS) are the distinct head / tail files of
+ * the scoring set, sorted as strings: rois = sorted(set(gt_tails + gt_heads)); a file that
+ * serves several bundles is one ROI.  D_r is ROI r's mask, dilated like the heads and tails
+ * of ttl_tractometer_classify.  valid(i, j) holds when some bundle has {head, tail} =
+ * {rois[i], rois[j]};  P = [(i, j) : 0 <= i < j < R, not valid(i, j)] in lexicographic
+ * order is the list of invalid pairs.
+ *   roi    device uint64 [X * Y * Z][W], W = (R + 63) / 64: bit r % 64 of word r / 64 of
+ *          voxel (x * Y + y) * Z + z is D_r there; the words of a voxel are adjacent (and
+ *          16-byte aligned when W = 2), so an end costs one 8- or 16-byte load.
+ *   valid  device uint64 [R][W]: bit j of row i when valid(i, j) or i == j.
+ *   bundle device int32 [n], as ttl_tractometer_classify wrote it.
+ * Streamline s is a candidate when bundle[s] < 0 and it has L >= 2 points (a row that
+ * connects a bundle's own ROIs but fails its criteria, connected[s] != 0, is a candidate
+ * too).  Its ends e0, e1 are those of ttl_tractometer_classify (floor; an end that is
+ * non-finite or outside [0, dims) lies in no ROI); interior points are not read.  With
+ * A = {r : D_r[e0]}, B = {r : D_r[e1]} and
+ *   connects(i, j) = (i in A and j in B) or (j in A and i in B),
+ * pair[s] = i * R + j for the first (i, j) of P with connects(i, j), else -1 (int32 [n],
+ * device).  A row with a bundle or with fewer than 2 points gets -1; so does a row whose
+ * ends lie in one ROI and nowhere else (i == j is no pair).
+ * One thread per streamline, grid-stride over at most 2048 workgroups; a row reads two
+ * offsets, its bundle, two points and 2 W words.  The first pair is found without a loop
+ * over P: for the set bits i of A | B in ascending order, J_i = ((i in A ? B : 0) |
+ * (i in B ? A : 0)) & ~valid[i] & (bits above i); the first non-zero J_i gives j, its
+ * lowest bit (a pair of P that connects has its smaller index in A | B, and J_i is the set
+ * of its partners).  No atomics: counts per pair are the caller's histogram of pair.
+ * TTL_ERR_INVALID for a null pointer, n < 0, R outside 2 .. 128 or a dim < 1; n == 0 is a
+ * successful no-op. */
+#define TTL_HAS_TRACTOMETER_IC 1
+#define TTL_TRACTOMETER_MAX_ROIS 128
+TTL_API int ttl_tractometer_invalid(const float *points, const int64_t *offsets, int32_t n,
+                                    const int32_t *bundle, const int32_t *dims, int32_t n_rois,
+                                    const uint64_t *roi, const uint64_t *valid, int32_t *pair,
+                                    void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

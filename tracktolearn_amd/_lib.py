@@ -28,6 +28,7 @@ ORDER_PARTITION = 1
 ORDER_BY_POSITION = C.c_void_p(1)      # TTL_ORDER_BY_POSITION (ttl_env_reset)
 TRACT_FILE_TRK, TRACT_FILE_TCK = 0, 1
 TRACTOMETER_LIMITS = 16               # TTL_TRACTOMETER_LIMITS
+TRACTOMETER_MAX_ROIS = 128            # TTL_TRACTOMETER_MAX_ROIS
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4
 
 
@@ -154,6 +155,9 @@ SYMBOLS = {
                                            C.c_uint64, C.c_void_p, C.POINTER(C.c_double),
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_tractometer_overlap': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                          C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_tractometer_invalid': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,

@@ -10,7 +10,10 @@
 // ttl_internal.h: the walk of ttl_tract_coverage) and, where a surviving
 // bundle sets an angle, the winding.  overlap: the valid streamlines are
 // walked again and OR their bundle's bit into a bit volume, which a second
-// kernel counts against the ground-truth planes with integer atomics.
+// kernel counts against the ground-truth planes with integer atomics.  invalid
+// (ttl_tractometer_invalid): the rows left without a bundle, one thread each,
+// test their two ends against the bit planes of the distinct ROIs and name the
+// first invalid pair of ROIs they connect.
 #include "ttl_internal.h"
 
 namespace {
@@ -291,6 +294,85 @@ __global__ __launch_bounds__(BLOCK) void k_tractometer_count(
     if (tid < 2 * B && s_count[tid]) atomicAdd(&counts[tid], (u64)s_count[tid]);
 }
 
+// ---- invalid connections (ttl_hip.h, ttl_tractometer_invalid): a set of ROIs is W words,
+// bit r % 64 of word r / 64 = ROI r
+template <int W>
+struct RoiSet {
+    u64 w[W];
+};
+
+// element `index` of an array of W-word sets, by one load
+template <int W>
+__device__ __forceinline__ RoiSet<W> load_set(const u64 *__restrict__ base, size_t index);
+template <>
+__device__ __forceinline__ RoiSet<1> load_set<1>(const u64 *__restrict__ base, size_t index) {
+    return RoiSet<1>{{base[index]}};
+}
+template <>
+__device__ __forceinline__ RoiSet<2> load_set<2>(const u64 *__restrict__ base, size_t index) {
+    const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(base)[index];
+    return RoiSet<2>{{v.x, v.y}};
+}
+
+// i * R + j of the first invalid pair (i < j, lexicographic) that the end sets A and B
+// connect, or -1.  Such a pair has i in A | B, and its partners are J below.
+template <int W>
+__device__ __forceinline__ int first_invalid_pair(const RoiSet<W> &A, const RoiSet<W> &B,
+                                                  const u64 *__restrict__ valid, int R) {
+    u64 any_a = 0, any_b = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        any_a |= A.w[w];
+        any_b |= B.w[w];
+    }
+    if (any_a == 0 || any_b == 0) return -1;       // an end in no ROI connects nothing
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        u64 m = A.w[w] | B.w[w];
+        while (m) {
+            const int bit = __builtin_ctzll(m);
+            m &= m - 1;
+            const u64 one = 1ull << bit;
+            const bool in_a = (A.w[w] & one) != 0, in_b = (B.w[w] & one) != 0;
+            const int i = 64 * w + bit;
+            const RoiSet<W> V = load_set<W>(valid, (size_t)i);
+#pragma unroll
+            for (int v = w; v < W; ++v) {
+                u64 J = ((in_a ? B.w[v] : 0ull) | (in_b ? A.w[v] : 0ull)) & ~V.w[v];
+                if (v == w) J &= ~((one << 1) - 1ull);      // the bits above i (none above 63)
+                if (J) return i * R + 64 * v + __builtin_ctzll(J);
+            }
+        }
+    }
+    return -1;
+}
+
+// one thread per streamline; top = the bits of the last word that name an ROI (bits at or
+// above R in the caller's planes are not read as ROIs, so i and j stay below R)
+template <int W>
+__global__ __launch_bounds__(BLOCK) void k_tractometer_invalid(
+    const float *__restrict__ points, const long long *__restrict__ offsets, int n,
+    const int *__restrict__ bundle, WalkDims D, int R, u64 top, const u64 *__restrict__ roi,
+    const u64 *__restrict__ valid, int *__restrict__ pair) {
+    const long long stride = (long long)gridDim.x * BLOCK;
+    for (long long row = (long long)blockIdx.x * BLOCK + threadIdx.x; row < n; row += stride) {
+        int found = -1;
+        const long long o0 = offsets[row], L = offsets[row + 1] - o0;
+        if (bundle[row] < 0 && L >= 2) {
+            const float *p = points + 3 * o0;
+            size_t i0, i1;
+            if (end_voxel(p, D, &i0) && end_voxel(p + 3 * (L - 1), D, &i1)) {
+                RoiSet<W> A = load_set<W>(roi, i0), B = load_set<W>(roi, i1);
+                A.w[W - 1] &= top;
+                B.w[W - 1] &= top;
+                found = first_invalid_pair<W>(A, B, valid, R);
+            }
+        }
+        pair[row] = found;
+    }
+}
+constexpr int INVALID_GRID = 2048;      // workgroups: 8 per CU of 256, every wave slot
+
 bool bad_dims(const int32_t *dims) {
     return !dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1;
 }
@@ -339,6 +421,34 @@ int ttl_tractometer_overlap(const float *points, const int64_t *offsets, int32_t
     hipLaunchKernelGGL(k_tractometer_count, dim3((unsigned)(want < 2048 ? want : 2048)),
                        dim3(BLOCK), 0, s, (const u64 *)visited_bits, (const u64 *)gt, n_vox,
                        n_bundles, (u64 *)counts);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+int ttl_tractometer_invalid(const float *points, const int64_t *offsets, int32_t n,
+                            const int32_t *bundle, const int32_t *dims, int32_t n_rois,
+                            const uint64_t *roi, const uint64_t *valid, int32_t *pair,
+                            void *hip_stream) {
+    if (!points || !offsets || !bundle || !roi || !valid || !pair || n < 0 || n_rois < 2 ||
+        n_rois > TTL_TRACTOMETER_MAX_ROIS || bad_dims(dims))
+        return fail(TTL_ERR_INVALID, "ttl_tractometer_invalid: bad arguments");
+    const int W = (n_rois + 63) / 64;
+    if (W == 2 && (((uintptr_t)roi | (uintptr_t)valid) & 15))
+        return fail(TTL_ERR_INVALID, "ttl_tractometer_invalid: two-word sets need 16-byte "
+                                     "aligned roi and valid");
+    if (n == 0) return TTL_OK;
+    const WalkDims D{{dims[0], dims[1], dims[2]}};
+    const u64 top = n_rois % 64 ? (1ull << (n_rois % 64)) - 1ull : ~0ull;
+    const long long want = ((long long)n + BLOCK - 1) / BLOCK;
+    const dim3 grid((unsigned)(want < INVALID_GRID ? want : INVALID_GRID));
+    if (W == 1)
+        hipLaunchKernelGGL(k_tractometer_invalid<1>, grid, dim3(BLOCK), 0,
+                           (hipStream_t)hip_stream, points, (const long long *)offsets, n,
+                           bundle, D, n_rois, top, (const u64 *)roi, (const u64 *)valid, pair);
+    else
+        hipLaunchKernelGGL(k_tractometer_invalid<2>, grid, dim3(BLOCK), 0,
+                           (hipStream_t)hip_stream, points, (const long long *)offsets, n,
+                           bundle, D, n_rois, top, (const u64 *)roi, (const u64 *)valid, pair);
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

@@ -20,6 +20,14 @@ The definitions (ends, voxel walk, lengths, winding) are stated in
 include/ttl_hip.h (scilpy's source is absent: restated, parity unpinned;
 DESIGN 3.12).  ``__call__`` takes the reference's filename (.trk / .tck) or the
 in-memory ``Tractogram`` of ``Tracker.track_and_validate``.
+
+With ``compute_ic=True`` the streamlines left without a bundle are tested
+against the distinct head / tail ROIs (``rois_and_pairs``,
+``ttl_tractometer_invalid``): one that connects two ROIs no bundle joins is an
+invalid connection, and IC / IS / IB / NC are filled.  ``score`` returns the
+full result (per-bundle VS, WPC, TP, FP, FN, OL, OR, f1, the invalid bundles and
+the per-streamline ``bundle`` / ``pair`` arrays) that
+``ttl_score_tractogram.py`` writes.
 """
 import ctypes as C
 import json
@@ -28,13 +36,15 @@ import os
 import numpy as np
 import torch
 
-from tracktolearn_amd.experiment.oracle_validator import (corner_voxels_from_rasmm, pack,
+from tracktolearn_amd.experiment.oracle_validator import (corner_voxels_from_rasmm,
+                                                          corner_voxels_from_tracker, pack,
                                                           packed_corner_voxels, reference_space,
                                                           tract_coverage)
 from tracktolearn_amd.experiment.validators import Validator
 
 def_len = [0, np.inf]
 MAX_BUNDLES = 64
+MAX_ROIS = 128          # TTL_TRACTOMETER_MAX_ROIS
 CONFIG_NAME = 'scil_scoring_config.json'
 # columns of a bundle's row of limits (TTL_TRACTOMETER_LIMITS doubles, ttl_hip.h)
 LIM_LENGTH, LIM_DIR, LIM_ABSDIR, LIM_ANGLE, LIM_COLUMNS = 0, 2, 8, 14, 16
@@ -121,6 +131,38 @@ def compute_endpoint_masks(roi_options):
     return [o['gt_tail'] for o in roi_options], [o['gt_head'] for o in roi_options]
 
 
+def rois_and_pairs(gt_tails, gt_heads):
+    """(rois, valid, pairs) of the invalid connections (ttl_hip.h,
+    ttl_tractometer_invalid): ``rois`` the distinct head / tail files sorted as
+    strings, ``valid`` bool (R, R), True where some bundle joins the two ROIs
+    and on the diagonal, ``pairs`` the invalid (i, j), i < j, in lexicographic
+    order."""
+    rois = sorted(set(list(gt_tails) + list(gt_heads)))
+    index = {name: r for r, name in enumerate(rois)}
+    valid = np.eye(len(rois), dtype=bool)
+    for tail, head in zip(gt_tails, gt_heads):
+        valid[index[tail], index[head]] = valid[index[head], index[tail]] = True
+    pairs = [(i, j) for i in range(len(rois)) for j in range(i + 1, len(rois))
+             if not valid[i, j]]
+    return rois, valid, pairs
+
+
+def roi_names(rois):
+    """The ROI files' names without directory and extension; when two files
+    share one, every name gets its index."""
+    names = []
+    for path in rois:
+        name = os.path.basename(str(path))
+        for ext in ('.nii.gz', '.nii', '.trk', '.tck'):
+            if name.lower().endswith(ext):
+                name = name[:-len(ext)]
+                break
+        names.append(name)
+    if len(set(names)) != len(names):
+        names = [f'{name}_{r}' for r, name in enumerate(names)]
+    return names
+
+
 # -------------------------------------------------------------- host packing
 def dilate(mask, iterations):
     """``scipy.ndimage.binary_dilation(mask, iterations=k)`` with its default
@@ -160,6 +202,33 @@ def pack_bit_planes(masks, dims, missing=False):
     return planes.reshape(-1)
 
 
+def pack_roi_words(masks, dims):
+    """uint64 [X * Y * Z][W], W = (R + 63) // 64: bit r % 64 of word r // 64 is
+    set where ``masks[r]`` is non-zero; the words of a voxel are adjacent."""
+    R = len(masks)
+    if not 2 <= R <= MAX_ROIS:
+        raise ValueError(f'{R} distinct head / tail ROIs: the invalid connections take 2 to '
+                         f'{MAX_ROIS}')
+    dims = tuple(int(v) for v in dims)
+    words = np.zeros(dims + ((R + 63) // 64,), np.uint64)
+    for r, mask in enumerate(masks):
+        mask = np.asarray(mask)
+        if mask.shape != dims:
+            raise ValueError(f'mask of ROI {r} has shape {mask.shape}, expected {dims}')
+        word = words[..., r // 64]
+        word[mask != 0] |= np.uint64(1) << np.uint64(r % 64)
+    return words.reshape(-1, words.shape[-1])
+
+
+def pack_valid_words(valid):
+    """uint64 [R][W]: bit j of row i where ``valid[i, j]`` or i == j."""
+    valid = np.asarray(valid, bool) | np.eye(len(valid), dtype=bool)
+    words = np.zeros((len(valid), (len(valid) + 63) // 64), np.uint64)
+    for i, j in zip(*np.nonzero(valid)):
+        words[i, j // 64] |= np.uint64(1) << np.uint64(j % 64)
+    return words
+
+
 def bundle_word(flags):
     """The uint64 whose bit b is ``bool(flags[b])``."""
     return sum(1 << b for b, f in enumerate(flags) if f)
@@ -187,10 +256,12 @@ def limits_table(lengths, angles, orientation_lengths, abs_orientation_lengths):
     return table
 
 
-def metrics(n, per_bundle, counts, gt_sizes):
+def metrics(n, per_bundle, counts, gt_sizes, invalid=None):
     """The returned dict from integers: n streamlines, ``per_bundle[b]``
     streamlines of bundle b, ``counts[b] = (|M_b & G_b|, |M_b \\ G_b|)``,
-    ``gt_sizes[b]`` = |G_b| or None without a gt_mask."""
+    ``gt_sizes[b]`` = |G_b| or None without a gt_mask.  ``invalid`` (compute_ic):
+    (streamlines with an invalid pair, invalid pairs with a streamline); then
+    IC = the former / n, IB = the latter, NC = (n - VS - #IC) / n, IS = IC + NC."""
     vs = int(sum(int(c) for c in per_bundle))
     vc = vs / n
     ols = []
@@ -198,9 +269,53 @@ def metrics(n, per_bundle, counts, gt_sizes):
         if size is None:
             continue
         ols.append(int(counts[b][0]) / size if size else 0.0)
-    return {'VC': vc, 'IC': 0, 'IS': 0, 'NC': 1 - vc,
-            'mean_OL': float(sum(ols) / len(ols)) if ols else 0.0,
-            'VB': int(sum(1 for c in per_bundle if int(c) > 0)), 'IB': 0}
+    out = {'VC': vc, 'IC': 0, 'IS': 0, 'NC': 1 - vc,
+           'mean_OL': float(sum(ols) / len(ols)) if ols else 0.0,
+           'VB': int(sum(1 for c in per_bundle if int(c) > 0)), 'IB': 0}
+    if invalid is not None:
+        n_ic, n_ib = (int(v) for v in invalid)
+        out['IC'], out['NC'], out['IB'] = n_ic / n, (n - vs - n_ic) / n, n_ib
+        out['IS'] = out['IC'] + out['NC']
+    return out
+
+
+def _ratio(num, den):
+    return num / den if den else 0.0
+
+
+def full_scores(n, names, per_bundle, counts, gt_sizes, wpc, invalid_bundles=None):
+    """The full result from integers: the totals ``n, VS, VC, IC,
+    IS, NC, VB, IB, mean_OL, mean_OR_gt, mean_OR_vs, mean_f1``, per bundle
+    ``bundles[name] = {VS, WPC, TP, FP, FN, OL, OR_gt, OR_vs, f1}`` with TP =
+    |M & G|, FP = |M \\ G|, FN = |G \\ M|, OL = TP / |G|, OR_gt = FP / |G|, OR_vs =
+    FP / |M|, f1 = 2 TP / (|M| + |G|) (a ratio with a zero denominator is 0; None
+    for a bundle without a gt_mask, which no mean counts), and
+    ``invalid_bundles`` = {'<roiA>__<roiB>': streamlines}, given with its positive
+    counts only, or None when the invalid connections were not computed (IC = IB
+    = 0 and NC = 1 - VC, as ``metrics`` without them)."""
+    invalid = None if invalid_bundles is None else \
+        (sum(int(c) for c in invalid_bundles.values()), len(invalid_bundles))
+    m = metrics(n, per_bundle, counts, gt_sizes, invalid)
+    bundles, per_gt = {}, {'OR_gt': [], 'OR_vs': [], 'f1': []}
+    for b, name in enumerate(names):
+        entry = {'VS': int(per_bundle[b]), 'WPC': int(wpc[b])}
+        size = gt_sizes[b]
+        if size is None:
+            entry.update(dict.fromkeys(('TP', 'FP', 'FN', 'OL', 'OR_gt', 'OR_vs', 'f1')))
+        else:
+            tp, fp = int(counts[b][0]), int(counts[b][1])
+            entry.update(TP=tp, FP=fp, FN=size - tp, OL=_ratio(tp, size),
+                         OR_gt=_ratio(fp, size), OR_vs=_ratio(fp, tp + fp),
+                         f1=_ratio(2 * tp, tp + fp + size))
+            for key in per_gt:
+                per_gt[key].append(entry[key])
+        bundles[name] = entry
+    means = {key: float(sum(v) / len(v)) if v else 0.0 for key, v in per_gt.items()}
+    return {'n': int(n), 'VS': int(sum(int(c) for c in per_bundle)), 'VC': m['VC'],
+            'IC': m['IC'], 'IS': m['IS'], 'NC': m['NC'], 'VB': m['VB'], 'IB': m['IB'],
+            'mean_OL': m['mean_OL'], 'mean_OR_gt': means['OR_gt'], 'mean_OR_vs': means['OR_vs'],
+            'mean_f1': means['f1'], 'bundles': bundles,
+            'invalid_bundles': dict(invalid_bundles or {})}
 
 
 # ------------------------------------------------------------ device wrappers
@@ -212,9 +327,13 @@ def _as_device_words(array, device):
 class ScoringData(object):
     """The packed scoring set on the device: bit planes head / tail / all / any
     / gt (uint64 words held in int64 tensors), the limits table, and the words
-    naming the bundles with an all_mask / any_mask."""
+    naming the bundles with an all_mask / any_mask.  For the invalid
+    connections, when ``roi_masks`` (the dilated masks of ``rois_and_pairs``'
+    ROIs) and ``valid`` are given: the ROI planes ``roi`` [X * Y * Z][W] and
+    the matrix ``valid`` [R][W]; otherwise both are None."""
 
-    def __init__(self, dims, heads, tails, all_masks, any_masks, gt_masks, limits, device):
+    def __init__(self, dims, heads, tails, all_masks, any_masks, gt_masks, limits, device,
+                 roi_masks=None, valid=None):
         self.dims = tuple(int(v) for v in dims)
         self.n_bundles = len(heads)
         if not 1 <= self.n_bundles <= MAX_BUNDLES:
@@ -232,6 +351,13 @@ class ScoringData(object):
         assert limits.shape == (self.n_bundles, LIM_COLUMNS), limits.shape
         self.limits = torch.from_numpy(limits).to(device)
         self.gt_sizes = [None if m is None else int(np.count_nonzero(m)) for m in gt_masks]
+        self.n_rois, self.roi, self.valid = 0, None, None
+        if roi_masks is not None:
+            self.n_rois = len(roi_masks)
+            valid = np.asarray(valid, bool)
+            assert valid.shape == (self.n_rois, self.n_rois), valid.shape
+            self.roi = _as_device_words(pack_roi_words(roi_masks, dims), device)
+            self.valid = _as_device_words(pack_valid_words(valid), device)
 
 
 def classify(points, offsets, data, lin):
@@ -283,6 +409,32 @@ def overlap(points, offsets, bundle, data, visited_bits=None):
     return counts, visited_bits
 
 
+def invalid(points, offsets, bundle, data):
+    """``ttl_tractometer_invalid`` on device tensors: pair int32 [n], i * R + j
+    of the first invalid pair of ROIs a row without a bundle connects, else -1.
+    ``data`` holds the ROI planes (``ScoringData(..., roi_masks, valid)``)."""
+    from tracktolearn_amd import _lib
+    lib = _lib.load()
+    if data.roi is None:
+        raise ValueError('the scoring data was packed without the ROI planes of the invalid '
+                         'connections (compute_ic)')
+    dev = points.device
+    n = int(offsets.shape[0]) - 1
+    pair = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
+    if n <= 0:
+        return pair
+    pts = points.to(torch.float32).contiguous()
+    off = offsets.to(torch.int64).contiguous()
+    dims_c = (C.c_int32 * 3)(*data.dims)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.ttl_tractometer_invalid(
+            pts.data_ptr(), off.data_ptr(), n, bundle.data_ptr(), dims_c, data.n_rois,
+            data.roi.data_ptr(), data.valid.data_ptr(), pair.data_ptr(), stream),
+            'ttl_tractometer_invalid')
+    return pair
+
+
 # ---------------------------------------------------------------- validator
 def _load_image(path):
     from tracktolearn_amd.io import nifti
@@ -294,10 +446,14 @@ class TractometerValidator(Validator):
     (tractogram_or_filename, env)`` -> ``{'VC', 'IC', 'IS', 'NC', 'mean_OL',
     'VB', 'IB'}``, ``{}`` without a streamline of >= 2 points.  ``reference``:
     the NIfTI file of the Tractometer's reference anatomy, or None to score in
-    the env's reference space (``reference_space``)."""
+    the env's reference space (``reference_space``).  ``compute_ic``: also
+    segment the invalid connections; ``__call__`` then fills IC, IS, IB and NC.
+    ``score`` gives the full result."""
 
-    def __init__(self, base_dir, reference, dilate_endpoints=1, device='cuda'):
+    def __init__(self, base_dir, reference, dilate_endpoints=1, device='cuda',
+                 compute_ic=False):
         self.name = 'Tractometer'
+        self.compute_ic = bool(compute_ic)
         self.gt_config = os.path.join(base_dir, CONFIG_NAME)
         if not os.path.isfile(self.gt_config):
             raise ValueError(f'the Tractometer validator needs {CONFIG_NAME} in the scoring '
@@ -329,7 +485,16 @@ class TractometerValidator(Validator):
                     for files in (all_files, any_files, gt_files)]
         limits = limits_table(self.bundle_lengths, self.angles, self.orientation_lengths,
                               self.abs_orientation_lengths)
-        self.data = ScoringData(self.dims, heads, tails, *optional, limits, self.device)
+        self.rois = self.roi_names = roi_masks = valid = None
+        if self.compute_ic:
+            self.rois, valid, _ = rois_and_pairs(self.gt_tails, self.gt_heads)
+            if len(self.rois) < 2:
+                raise ValueError(f'{self.gt_config} names one head / tail ROI only: there is '
+                                 'no pair of ROIs to connect (compute_ic)')
+            self.roi_names = roi_names(self.rois)
+            roi_masks = [dilate(self._mask(f, cache), self.dilation_factor) for f in self.rois]
+        self.data = ScoringData(self.dims, heads, tails, *optional, limits, self.device,
+                                roi_masks=roi_masks, valid=valid)
 
     def _mask(self, path, cache):
         """A scoring file as a boolean volume of the reference's dims: a NIfTI
@@ -392,10 +557,108 @@ class TractometerValidator(Validator):
         bundle, _ = classify(pts, off, data, ref_affine[:3, :3])
         counts, _ = overlap(pts, off, bundle, data)
         per_bundle = torch.bincount(bundle.to(torch.int64) + 1, minlength=data.n_bundles + 1)
-        back = torch.cat([per_bundle[1:], counts.reshape(-1)]).cpu().numpy()
+        parts = [per_bundle[1:], counts.reshape(-1)]
+        if self.compute_ic:
+            per_pair = self._per_pair(invalid(pts, off, bundle, data))
+            parts += [per_pair.sum().reshape(1), (per_pair > 0).sum().reshape(1)]
+        back = torch.cat(parts).cpu().numpy()
         B = data.n_bundles
-        return metrics(n, back[:B], back[B:].reshape(B, 2), data.gt_sizes)
+        return metrics(n, back[:B], back[B:3 * B].reshape(B, 2), data.gt_sizes,
+                       invalid=back[3 * B:] if self.compute_ic else None)
+
+    def _per_pair(self, pair):
+        """Streamlines per pair i * R + j, int64 [R * R] on the device."""
+        R = self.data.n_rois
+        return torch.bincount(pair.to(torch.int64) + 1, minlength=R * R + 1)[1:]
+
+    # ---- the full result
+    def load(self, filename):
+        """A .trk / .tck for ``score_loaded``: (tractogram in RAS+mm, the .trk's
+        header dict or None, the vox -> RAS mm affine it is scored in: the
+        reference's when one was given, else the .trk's own)."""
+        from tracktolearn_amd.io import streamlines as sio
+        lower = str(filename).lower()
+        if lower.endswith('.trk'):
+            tract, header = sio.load_trk(filename)
+        elif lower.endswith('.tck'):
+            (tract, _), header = sio.load_tck(filename), None
+        else:
+            raise ValueError(f'{filename}: the Tractometer validator reads .trk or .tck')
+        if self.ref_affine is not None:
+            return tract, header, self.ref_affine
+        if header is None:
+            raise ValueError(f'{filename}: a .tck needs a reference')
+        if tuple(int(v) for v in header['dimensions']) != tuple(self.dims):
+            raise ValueError(f"{filename}: its header's dimensions "
+                             f"{tuple(header['dimensions'])} differ from the scoring data's "
+                             f'{tuple(self.dims)}: give a reference')
+        return tract, header, np.asarray(header['voxel_to_rasmm'], np.float64)
+
+    def corner_voxels(self, tractogram_or_filename, env=None):
+        """(points, offsets, index, affine): the streamlines with >= 2 points
+        in the voxel space they are scored in, corner origin, packed; ``index``
+        their numbers in the input; ``affine`` that space's vox -> RAS mm."""
+        if isinstance(tractogram_or_filename, (str, bytes, os.PathLike)):
+            tract, _, affine = self.load(os.fsdecode(tractogram_or_filename))
+            return self._from_rasmm(tract.streamlines, affine)
+        if env is None:
+            raise ValueError('an in-memory tractogram is in the voxel space of its env: '
+                             'give the env')
+        lines = getattr(tractogram_or_filename, 'streamlines', tractogram_or_filename)
+        affine, _ = self.space(env)
+        index = np.array([i for i, s in enumerate(lines) if len(s) >= 2], np.int64)
+        points, offsets = pack([np.asarray(lines[i]) for i in index])
+        return (corner_voxels_from_tracker(points, env.affine_vox2rasmm, affine), offsets,
+                index, affine)
+
+    @staticmethod
+    def _from_rasmm(lines, affine):
+        index = np.array([i for i, s in enumerate(lines) if len(s) >= 2], np.int64)
+        points, offsets = pack([np.asarray(lines[i]) for i in index])
+        return corner_voxels_from_rasmm(points, affine), offsets, index, affine
+
+    def score(self, tractogram_or_filename, env=None):
+        """The full result of ``full_scores`` plus ``bundle`` and ``pair`` (int32
+        per streamline with >= 2 points; pair = -1 everywhere without
+        compute_ic) and ``index``, those streamlines' numbers in the input.
+        A file needs no env when a reference was given, a .trk none at all.
+        ``{}`` without a streamline of >= 2 points."""
+        return self._score(*self.corner_voxels(tractogram_or_filename, env))
+
+    def score_loaded(self, tractogram, affine):
+        """``score`` of what ``load`` returned."""
+        return self._score(*self._from_rasmm(tractogram.streamlines, affine))
+
+    def _score(self, points, offsets, index, affine):
+        n = len(offsets) - 1
+        if n == 0:
+            return {}
+        data, B = self.data, self.data.n_bundles
+        pts = torch.from_numpy(points).to(self.device)
+        off = torch.from_numpy(offsets).to(self.device)
+        bundle, connected = classify(pts, off, data, affine[:3, :3])
+        counts, _ = overlap(pts, off, bundle, data)
+        per_bundle = torch.bincount(bundle.to(torch.int64) + 1, minlength=B + 1)
+        # WPC: the bundles whose ROIs a row without a bundle connects
+        wrong = connected[(bundle < 0) & (connected != 0)]
+        wpc = ((wrong[:, None] >> torch.arange(B, device=self.device)) & 1).sum(0)
+        back = torch.cat([per_bundle[1:], counts.reshape(-1), wpc]).cpu().numpy()
+        invalid_bundles = None
+        pair = torch.full_like(bundle, -1)
+        if self.compute_ic:
+            pair = invalid(pts, off, bundle, data)
+            per_pair = self._per_pair(pair).cpu().numpy()
+            R = data.n_rois
+            invalid_bundles = {
+                f'{self.roi_names[k // R]}__{self.roi_names[k % R]}': int(per_pair[k])
+                for k in np.flatnonzero(per_pair)}
+        out = full_scores(n, self.bundle_names, back[:B], back[B:3 * B].reshape(B, 2),
+                          data.gt_sizes, back[3 * B:], invalid_bundles)
+        out.update(bundle=bundle.cpu().numpy(), pair=pair.cpu().numpy(), index=index)
+        return out
 
 
 __all__ = ['TractometerValidator', 'ScoringData', 'read_config_file', 'compute_endpoint_masks',
-           'dilate', 'pack_bit_planes', 'limits_table', 'metrics', 'classify', 'overlap']
+           'dilate', 'pack_bit_planes', 'limits_table', 'metrics', 'classify', 'overlap',
+           'rois_and_pairs', 'roi_names', 'pack_roi_words', 'pack_valid_words', 'full_scores',
+           'invalid']

@@ -8,7 +8,8 @@ TractOracle on the GPU (experiment/oracle_validator.py: ``Oracle`` and
 ``Coverage``, printed and kept in ``plots/oracle.npy`` / ``coverage.npy``).
 ``--tractometer_validator --scoring_data DIR`` segments it into the bundles of
 ``DIR/scil_scoring_config.json`` on the GPU (experiment/tractometer_validator.py:
-``VC``, ``NC``, ``VB``, ``mean_OL`` ..., kept in ``plots/vc.npy`` etc.).
+``VC``, ``NC``, ``VB``, ``mean_OL`` ..., kept in ``plots/vc.npy`` etc.;
+``--tractometer_compute_ic`` adds the invalid connections, ``IC`` and ``IB``).
 Comet.ml is outside the hot-path scope: ``--use_comet`` is
 accepted and ignored with a notice.
 """
@@ -66,6 +67,7 @@ class TrackToLearnTraining(object):
         self.scoring_data = g['scoring_data']
         self.tractometer_reference = g.get('tractometer_reference')
         self.tractometer_dilate = g.get('tractometer_dilate', 1)
+        self.tractometer_compute_ic = g.get('tractometer_compute_ic', False)
         if self.tractometer_validator:
             from tracktolearn_amd.experiment.tractometer_validator import CONFIG_NAME
             if not self.scoring_data:
@@ -241,7 +243,8 @@ class TrackToLearnTraining(object):
                 TractometerValidator
             self.validators.append(TractometerValidator(
                 self.scoring_data, self.tractometer_reference,
-                dilate_endpoints=self.tractometer_dilate, device=self.device))
+                dilate_endpoints=self.tractometer_dilate, device=self.device,
+                compute_ic=self.tractometer_compute_ic))
             self.score_monitors.update({
                 key: LossHistory(key, key.lower(), p)
                 for key in ('VC', 'IC', 'NC', 'VB', 'IB', 'mean_OL')})
@@ -356,6 +359,9 @@ def add_tractometer_args(parser: ArgumentParser):
                               '--scoring_data).')
     tractom.add_argument('--tractometer_dilate', default=1, type=int,
                          help='Dilation factor for the ROIs of the Tractometer.')
+    tractom.add_argument('--tractometer_compute_ic', action='store_true',
+                         help='Also segment the invalid connections: IC, IS, IB and '
+                              'NC carry real values.')
 
 
 def add_oracle_args(parser: ArgumentParser):
