@@ -72,9 +72,9 @@ def main(argv=None):
 
     from bench_oracle_validator import tractogram
     from tracktolearn_amd.experiment.oracle_validator import corner_voxels_from_tracker, pack
-    from tracktolearn_amd.experiment.tractometer_validator import (ScoringData, classify,
-                                                                   invalid, limits_table,
-                                                                   metrics, overlap)
+    from tracktolearn_amd.experiment.tractometer_validator import (ScoringData, Segmentation,
+                                                                   classify, invalid,
+                                                                   limits_table, metrics, overlap)
 
     dev = torch.device('cuda:0')
     D = 145
@@ -125,24 +125,19 @@ def main(argv=None):
                    'invalid_ms': ev[3].elapsed_time(ev[4])}
             row['device_ms'] = row['classify_ms'] + row['overlap_ms']
             if best is None or row['device_ms'] < best[0]['device_ms']:
-                per = torch.bincount(bundle.to(torch.int64) + 1, minlength=N_BUNDLES + 1)
-                per_pair = torch.bincount(pair.to(torch.int64) + 1, minlength=R * R + 1)[1:]
-                back = torch.cat([per[1:], counts.reshape(-1), per_pair.sum().reshape(1),
-                                  (per_pair > 0).sum().reshape(1),
-                                  (connected == 0).sum().reshape(1)]).cpu().numpy()
-                best = (row, back)
-        row, back = best
+                best = (row, Segmentation(data, bundle, connected, counts, pair).summary(),
+                        int((connected == 0).sum()))
+        row, s, unconnected = best
         M = int(lens.sum())
-        result = metrics(n, back[:N_BUNDLES], back[N_BUNDLES:-3].reshape(N_BUNDLES, 2),
-                         data.gt_sizes, invalid=back[-3:-1])
+        result = metrics(n, s.per_bundle, s.counts, data.gt_sizes, invalid=s.invalid)
         print(json.dumps({
             'object': 'tractometer_validator', 'streamlines': n, 'points': M,
             'bundles': N_BUNDLES, 'rois': R, 'scoring_setup_ms': round(setup_ms, 1),
             **{k: round(v, 3) for k, v in row.items()},
-            'left_after_end_test': round(int(back[-1]) / n, 4),
-            'with_a_bundle': round(int(back[:N_BUNDLES].sum()) / n, 4),
-            'reach_invalid': round(1 - int(back[:N_BUNDLES].sum()) / n, 4),
-            'with_a_pair': round(int(back[-3]) / n, 4),
+            'left_after_end_test': round(unconnected / n, 4),
+            'with_a_bundle': round(int(s.per_bundle.sum()) / n, 4),
+            'reach_invalid': round(1 - int(s.per_bundle.sum()) / n, 4),
+            'with_a_pair': round(int(s.invalid[0]) / n, 4),
             'result': result, 'reps': args.reps,
             'device': torch.cuda.get_device_name(0)}), flush=True)
         if first is None:

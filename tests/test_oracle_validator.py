@@ -90,7 +90,7 @@ def _corner_case_lines():
 def test_file_to_corner_voxels(tmp_path, ext):
     """RAS+mm file -> the reference's voxel space, corner origin: 2 mm
     voxels, an offset origin; streamlines of < 2 points dropped."""
-    from tracktolearn_amd.experiment.oracle_validator import load_corner_voxels
+    from tracktolearn_amd.experiment.oracle_validator import corner_voxels
     from tracktolearn_amd.io import streamlines as sio
     from tracktolearn_amd.tractogram import Tractogram
     aff = np.diag([2.0, 2.0, 2.0, 1.0])
@@ -102,17 +102,16 @@ def test_file_to_corner_voxels(tmp_path, ext):
         sio.save_trk(world, path, sio.create_tractogram_header(aff, (8, 8, 8), (2.0, 2.0, 2.0)))
     else:
         sio.save_tck(world, path)
-    points, offsets = load_corner_voxels(path, aff)
-    assert offsets.tolist() == [0, 3, 5]
+    points, offsets, index = corner_voxels(path, aff)
+    assert offsets.tolist() == [0, 3, 5] and index.tolist() == [0, 1]
     want = np.concatenate(vox[:2]) + np.float32(0.5)
     assert points.dtype == np.float32 and np.array_equal(points, want)
 
 
 def test_tracker_to_corner_voxels():
     from tracktolearn_amd.experiment.oracle_validator import (
-        corner_voxels_from_tracker, keep_streamlines, pack)
-    lines = keep_streamlines(_corner_case_lines())
-    points, offsets = pack(lines)
+        corner_voxels, corner_voxels_from_tracker, pack)
+    points, offsets = pack(_corner_case_lines()[:2])
     assert offsets.tolist() == [0, 3, 5]
     ref_aff = np.diag([2.0, 2.0, 2.0, 1.0])
     ref_aff[:3, 3] = [-10.0, 20.0, 4.0]
@@ -124,19 +123,24 @@ def test_tracker_to_corner_voxels():
     track[:3, 3] = ref_aff[:3, 3]
     half = corner_voxels_from_tracker(points, track, ref_aff)
     assert np.array_equal(half, points * np.float32(0.5) + np.float32(0.5))
+    # the intake: the one-point row dropped, then the same two conversions
+    for own, want in ((ref_aff.copy(), same), (track, half)):
+        got, got_offsets, index = corner_voxels(_corner_case_lines(), ref_aff, own)
+        assert np.array_equal(got, want) and got.dtype == np.float32
+        assert got_offsets.tolist() == [0, 3, 5] and index.tolist() == [0, 1]
 
 
 def test_short_streamlines_dropped(tmp_path):
     """Streamlines of < 2 points are dropped before anything else; none left
     -> {} (no GPU work: the validator runs on a CPU-placed oracle here)."""
-    from tracktolearn_amd.experiment.oracle_validator import (
-        OracleValidator, keep_streamlines)
+    from tracktolearn_amd.experiment.oracle_validator import OracleValidator, corner_voxels
     from tracktolearn_amd.oracles.oracle import OracleSingleton
     from tracktolearn_amd.oracles.transformer_oracle import save_random_checkpoint
     from tracktolearn_amd.tractogram import Tractogram
     lines = [np.zeros((0, 3), np.float32), np.ones((1, 3), np.float32),
              np.ones((2, 3), np.float32)]
-    assert [len(s) for s in keep_streamlines(lines)] == [2]
+    _, offsets, index = corner_voxels(lines, np.eye(4), np.eye(4))
+    assert np.diff(offsets).tolist() == [2] and index.tolist() == [2]
     ck = save_random_checkpoint(str(tmp_path / 'o.ckpt'), n_head=1, n_layers=1)
     OracleSingleton.reset()
     try:

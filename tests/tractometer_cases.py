@@ -9,8 +9,14 @@ swapped index shows.  A set of B bundles has its roles at these bits:
 Every other bit is a filler bundle: a few random ROI voxels in the slab z = 0,
 which the designed rows never end in.  The roles live in slabs of their own
 (AY z 1-2, P z 3, L z 4, W z 5-6) with the head at low x and the tail at high x.
+
+Also the scaffolding that test_tractometer.py, test_tractometer_ic.py and
+tractometer_ic_cases.py share: ``_box``, ``_line``, ``pack``, the end-to-end
+space ``AFFINE`` with its env (``env``) and .trk files (``save_trk``), and the
+trainer runs' dataset and arguments (``_write_dataset``, ``_train_args``).
 """
 import functools
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -18,6 +24,10 @@ import ref_tractometer as ref
 from ref_oracle_validator import random_walks
 
 DIMS = (12, 9, 7)
+AFFINE = np.array([[1.8793852415718169, -0.5130302149885031, 0.0, -11.0],
+                   [0.6840402866513374, 1.4095389311788626, 0.0, 4.5],
+                   [0.0, 0.0, 1.25, -3.0],
+                   [0.0, 0.0, 0.0, 1.0]])      # 20 degrees about z, zooms (2, 1.5, 1.25)
 # not symmetric, so a transposed lin shows; entries multiples of 2^-2
 LIN = np.array([[2.0, 0.5, 0.0], [0.0, 1.5, 0.0], [0.0, 0.0, 1.25]])
 ROLES = {3: {'L': 0, 'AY': 1, 'W': 2},
@@ -82,7 +92,50 @@ def tables(bundles):
 
 
 def _line(*pts):
-    return np.array(pts, np.float32)
+    return np.array(pts, np.float32).reshape(-1, 3)
+
+
+def pack(lines):
+    offsets = np.zeros(len(lines) + 1, np.int64)
+    np.cumsum([len(s) for s in lines], out=offsets[1:])
+    points = np.concatenate([np.asarray(s, np.float32).reshape(-1, 3) for s in lines])
+    return points.astype(np.float32), offsets
+
+
+def env(affine=AFFINE):
+    """What a validator reads of an env whose tracking and reference space is
+    ``affine`` over DIMS."""
+    from tracktolearn_amd.datasets.utils import MRIDataVolume
+    return SimpleNamespace(tracking_mask=MRIDataVolume(np.ones(DIMS, np.uint8), affine),
+                           affine_vox2rasmm=affine, reference={'affine': affine, 'shape': DIMS})
+
+
+def save_trk(streamlines, path, data_per_streamline=None):
+    """Tracker-voxel streamlines of AFFINE's space (centre origin) as a .trk."""
+    from tracktolearn_amd.io import streamlines as sio
+    from tracktolearn_amd.tractogram import Tractogram
+    world = Tractogram(streamlines, data_per_streamline).apply_affine(AFFINE)
+    sio.save_trk(world, path, sio.create_tractogram_header(AFFINE, DIMS, (2.0, 1.5, 1.25)))
+
+
+def _write_dataset(path, D=20):
+    # the synthetic dataset of tests/test_oracle_validator.py
+    from tracktolearn_amd.datasets.SubjectDataset import write_npz_dataset
+    from tracktolearn_amd.utils.synthetic import synthetic_volumes
+    subs = {}
+    for i, sid in enumerate(('sub-a', 'sub-b')):
+        sh, mask, pk = synthetic_volumes(D, 45, seed=50 + i)
+        aff = np.eye(4, dtype=np.float32)
+        subs[sid] = {'input_volume': (sh, aff), 'peaks_volume': (pk, aff),
+                     'tracking_volume': (mask, aff), 'seeding_volume': (mask, aff)}
+    write_npz_dataset(path, {'training': subs})
+
+
+def _train_args(tmp_path, extra):
+    return [str(tmp_path / 'exp'), 'toy', 'run1', str(tmp_path / 'ds.npz'), '--max_ep', '2',
+            '--log_interval', '1', '--n_actor', '512', '--hidden_dims', '32-32',
+            '--batch_size', '64', '--replay_size', '20000', '--npv', '1', '--min_length', '2',
+            '--max_length', '20', '--oracle_bonus', '0', '--rng_seed', '4'] + extra
 
 
 def arc(n, sagitta, seed, z=5.9):
@@ -175,9 +228,7 @@ def case(B):
     roles = ROLES[B]
     want = [None if r[2] is None else (-1 if r[2] == '-' else roles[r[2]]) for r in rows]
     want += [None] * len(walks)
-    offsets = np.zeros(len(lines) + 1, np.int64)
-    np.cumsum([len(s) for s in lines], out=offsets[1:])
-    points = np.concatenate(lines).astype(np.float32)
+    points, offsets = pack(lines)
     bundles = scoring_set(B)
     return {'points': points, 'offsets': offsets, 'names': names, 'want': want,
             'bundles': bundles, 'score': ref.score(points, offsets, DIMS, bundles, LIN)}
@@ -212,9 +263,7 @@ def grid_case():
             p[0] = (rng.uniform(0, 2), rng.uniform(0, 9), 4.5)
             p[-1] = (rng.uniform(10, 12), rng.uniform(0, 9), 4.5)
         lines.append(p.astype(np.float32))
-    offsets = np.zeros(len(lines) + 1, np.int64)
-    np.cumsum([len(s) for s in lines], out=offsets[1:])
-    points = np.concatenate(lines).astype(np.float32)
+    points, offsets = pack(lines)
     bundles = scoring_set(B)
     return {'points': points, 'offsets': offsets, 'bundles': bundles,
             'score': ref.score(points, offsets, DIMS, bundles, LIN)}

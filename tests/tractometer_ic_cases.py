@@ -16,6 +16,7 @@ import numpy as np
 
 import ref_tractometer_ic as ric
 from ref_oracle_validator import random_walks
+from tractometer_cases import _line, pack
 
 DIMS = (12, 9, 7)
 SETS = (2, 3, 64, 65, 128)
@@ -65,10 +66,6 @@ def own(k, y=1.5, z=1.5):
 def shared(k):
     """A point in the k-th and the (k + 1)-th deciding ROI."""
     return (k + 0.5, 4.5, 1.5)
-
-
-def _line(*pts):
-    return np.array(pts, np.float32).reshape(-1, 3)
 
 
 def designed_rows(R):
@@ -140,13 +137,6 @@ def designed_rows(R):
             add(f'own_{S[p]}_to_{S[q]}', [own(p), own(q)],
                 None if p == q or valid else (i, j))
     return rows
-
-
-def pack(lines):
-    offsets = np.zeros(len(lines) + 1, np.int64)
-    np.cumsum([len(s) for s in lines], out=offsets[1:])
-    points = np.concatenate([np.asarray(s, np.float32).reshape(-1, 3) for s in lines])
-    return points.astype(np.float32), offsets
 
 
 @functools.lru_cache(maxsize=None)

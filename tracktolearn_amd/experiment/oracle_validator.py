@@ -18,6 +18,11 @@ The voxel walk that defines "visited" is stated in include/ttl_hip.h
 DESIGN 3.8).  ``__call__`` takes the reference's filename (.trk / .tck) or the
 in-memory ``Tractogram`` of ``Tracker.track_and_validate`` (tracker voxel
 coordinates), which skips the file round trip.
+
+Both validators take their tractogram through the one intake here,
+``corner_voxels`` (file or memory, rows of >= 2 points, packed, corner-origin
+voxels of the scoring space), read files through ``load_tractogram`` and launch
+the library's ragged-row entries through ``launch_ragged``.
 """
 import ctypes as C
 import os
@@ -60,11 +65,6 @@ def _affine_corner(pts, M):
     return out
 
 
-def keep_streamlines(lines):
-    """The streamlines with >= 2 points, as float arrays (both input paths)."""
-    return [np.asarray(s) for s in lines if len(s) >= 2]
-
-
 def pack(lines):
     """Ragged layout: points (M, 3) float32 and offsets (n + 1,) int64."""
     offsets = np.zeros(len(lines) + 1, np.int64)
@@ -93,56 +93,76 @@ def corner_voxels_from_tracker(points_vox, vox2rasmm, ref_affine):
     return _affine_corner(points_vox, np.linalg.inv(ref) @ own)
 
 
-def load_corner_voxels(filename, ref_affine):
-    """The streamlines (>= 2 points) of a .trk / .tck in the reference's voxel
-    space, corner origin, packed: (points, offsets)."""
+FILENAME = (str, bytes, os.PathLike)
+
+
+def load_tractogram(filename):
+    """The one reader of a tractogram file: (tractogram in RAS+mm, the .trk's
+    header dict, or None for a .tck)."""
     from tracktolearn_amd.io import streamlines as sio
-    lower = str(filename).lower()
+    filename = os.fsdecode(filename)
+    lower = filename.lower()
     if lower.endswith('.trk'):
-        tract, _ = sio.load_trk(filename)
-    elif lower.endswith('.tck'):
-        tract, _ = sio.load_tck(filename)
-    else:
-        raise ValueError(f'{filename}: the oracle validator reads .trk or .tck')
-    points, offsets = pack(keep_streamlines(tract.streamlines))
-    return corner_voxels_from_rasmm(points, ref_affine), offsets
+        return sio.load_trk(filename)
+    if lower.endswith('.tck'):
+        return sio.load_tck(filename)[0], None
+    raise ValueError(f'{filename}: a tractogram is read from a .trk or .tck file')
 
 
-def packed_corner_voxels(tractogram_or_filename, env, ref_affine):
-    """Both input paths of a validator: a .trk / .tck file name, or the
-    in-memory ``Tractogram`` (or list of streamlines) in the tracker's voxel
-    coordinates -> (points, offsets) of the streamlines with >= 2 points in the
-    voxel space of ``ref_affine``, corner origin."""
-    if isinstance(tractogram_or_filename, (str, bytes, os.PathLike)):
-        return load_corner_voxels(os.fsdecode(tractogram_or_filename), ref_affine)
-    lines = tractogram_or_filename.streamlines \
-        if isinstance(tractogram_or_filename, Tractogram) else tractogram_or_filename
-    points, offsets = pack(keep_streamlines(lines))
-    return corner_voxels_from_tracker(points, env.affine_vox2rasmm, ref_affine), offsets
+def corner_voxels(source, ref_affine, tracker_affine=None, in_rasmm=False):
+    """The one intake of a validator: (points (M, 3) float32, offsets (n + 1,)
+    int64, index (n,) int64) of the streamlines with >= 2 points, packed, in
+    the voxel space of ``ref_affine``, corner origin; ``index`` their numbers
+    in the input.  ``source``: a .trk / .tck file name (RAS+mm), or the
+    in-memory ``Tractogram`` (or list of streamlines) of the tracker, in the
+    voxel coordinates of ``tracker_affine``; ``in_rasmm``: an in-memory source
+    that ``load_tractogram`` read."""
+    if isinstance(source, FILENAME):
+        source, in_rasmm = load_tractogram(source)[0], True
+    elif not in_rasmm and tracker_affine is None:
+        raise ValueError('an in-memory tractogram is in the voxel space of its env: '
+                         'give the env')
+    lines = source.streamlines if isinstance(source, Tractogram) else source
+    index = np.flatnonzero(np.fromiter((len(s) >= 2 for s in lines), bool, len(lines)))
+    index = index.astype(np.int64, copy=False)
+    # a tracker's output keeps every row: no second list then
+    points, offsets = pack(lines if len(index) == len(lines) else
+                           [lines[i] for i in index.tolist()])
+    if in_rasmm:
+        return corner_voxels_from_rasmm(points, ref_affine), offsets, index
+    return corner_voxels_from_tracker(points, tracker_affine, ref_affine), offsets, index
+
+
+def launch_ragged(entry, points, offsets, dims, before=(), after=()):
+    """The one launch of a library entry that walks ragged rows:
+    ``entry(points, offsets, n, *before, dims, *after, stream)`` on the
+    device and current stream of ``points``, float32 points and int64 offsets
+    contiguous, n = max(len(offsets) - 1, 0), its status checked."""
+    from tracktolearn_amd import _lib
+    pts = points.to(torch.float32).contiguous()
+    off = offsets.to(torch.int64).contiguous()
+    dims_c = (C.c_int32 * 3)(*(int(v) for v in dims))
+    dev = pts.device
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(getattr(_lib.load(), entry)(
+            pts.data_ptr(), off.data_ptr(), max(int(off.shape[0]) - 1, 0), *before, dims_c,
+            *after, stream), entry)
 
 
 def tract_coverage(points, offsets, dims, scores=None, threshold=0.5, visited=None):
     """``ttl_tract_coverage`` on device tensors: visited (X * Y * Z,) uint8,
     1 where an accepted streamline (scores > threshold; every one when scores
     is None) passes (include/ttl_hip.h).  ``visited`` (zeroed) may be given."""
-    from tracktolearn_amd import _lib
-    lib = _lib.load()
-    dev = points.device
-    n = int(offsets.shape[0]) - 1
     X, Y, Z = (int(v) for v in dims)
     if visited is None:
-        visited = torch.zeros(X * Y * Z, dtype=torch.uint8, device=dev)
-    if n <= 0:
+        visited = torch.zeros(X * Y * Z, dtype=torch.uint8, device=points.device)
+    if len(offsets) <= 1:
         return visited
-    pts = points.to(torch.float32).contiguous()
-    off = offsets.to(torch.int64).contiguous()
     sc = None if scores is None else scores.to(torch.float32).contiguous()
-    dims_c = (C.c_int32 * 3)(X, Y, Z)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.ttl_tract_coverage(
-            pts.data_ptr(), off.data_ptr(), n, None if sc is None else sc.data_ptr(),
-            float(threshold), dims_c, visited.data_ptr(), stream), 'ttl_tract_coverage')
+    launch_ragged('ttl_tract_coverage', points, offsets, dims,
+                  (None if sc is None else sc.data_ptr(), float(threshold)),
+                  (visited.data_ptr(),))
     return visited
 
 
@@ -161,12 +181,10 @@ class OracleValidator(Validator):
         self.device = torch.device(device)
         self.model = OracleSingleton(checkpoint, self.device)
 
-    def _packed(self, tractogram_or_filename, env, ref_affine):
-        return packed_corner_voxels(tractogram_or_filename, env, ref_affine)
-
     def __call__(self, tractogram_or_filename, env):
         ref_affine, dims = reference_space(env)
-        points, offsets = self._packed(tractogram_or_filename, env, ref_affine)
+        points, offsets, _ = corner_voxels(tractogram_or_filename, ref_affine,
+                                           env.affine_vox2rasmm)
         n = len(offsets) - 1
         if n == 0:
             return {}

@@ -28,18 +28,23 @@ invalid connection, and IC / IS / IB / NC are filled.  ``score`` returns the
 full result (per-bundle VS, WPC, TP, FP, FN, OL, OR, f1, the invalid bundles and
 the per-streamline ``bundle`` / ``pair`` arrays) that
 ``ttl_score_tractogram.py`` writes.
+
+``__call__`` and ``score`` share the intake of experiment/oracle_validator.py
+(``corner_voxels``) and the one device pass here: ``segment`` (classify, overlap,
+invalid) and its ``summary``, the single read-back, which names what it holds.
 """
 import ctypes as C
 import json
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from tracktolearn_amd.experiment.oracle_validator import (corner_voxels_from_rasmm,
-                                                          corner_voxels_from_tracker, pack,
-                                                          packed_corner_voxels, reference_space,
-                                                          tract_coverage)
+from tracktolearn_amd.experiment.oracle_validator import (FILENAME, corner_voxels,
+                                                          corner_voxels_from_rasmm,
+                                                          launch_ragged, load_tractogram, pack,
+                                                          reference_space, tract_coverage)
 from tracktolearn_amd.experiment.validators import Validator
 
 def_len = [0, np.inf]
@@ -363,25 +368,15 @@ class ScoringData(object):
 def classify(points, offsets, data, lin):
     """``ttl_tractometer_classify`` on device tensors: (bundle int32 [n],
     connected int64 [n] holding the uint64 bit sets)."""
-    from tracktolearn_amd import _lib
-    lib = _lib.load()
-    dev = points.device
-    n = int(offsets.shape[0]) - 1
-    bundle = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
-    connected = torch.empty(max(n, 0), dtype=torch.int64, device=dev)
-    if n <= 0:
-        return bundle, connected
-    pts = points.to(torch.float32).contiguous()
-    off = offsets.to(torch.int64).contiguous()
-    dims_c = (C.c_int32 * 3)(*data.dims)
-    lin_c = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.ttl_tractometer_classify(
-            pts.data_ptr(), off.data_ptr(), n, dims_c, data.n_bundles, data.head.data_ptr(),
-            data.tail.data_ptr(), data.all.data_ptr(), data.any.data_ptr(), data.has_all,
-            data.has_any, data.limits.data_ptr(), lin_c, bundle.data_ptr(),
-            connected.data_ptr(), stream), 'ttl_tractometer_classify')
+    n = max(len(offsets) - 1, 0)
+    bundle = torch.empty(n, dtype=torch.int32, device=points.device)
+    connected = torch.empty(n, dtype=torch.int64, device=points.device)
+    if n:
+        lin_c = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
+        launch_ragged('ttl_tractometer_classify', points, offsets, data.dims, after=(
+            data.n_bundles, data.head.data_ptr(), data.tail.data_ptr(), data.all.data_ptr(),
+            data.any.data_ptr(), data.has_all, data.has_any, data.limits.data_ptr(), lin_c,
+            bundle.data_ptr(), connected.data_ptr()))
     return bundle, connected
 
 
@@ -389,23 +384,14 @@ def overlap(points, offsets, bundle, data, visited_bits=None):
     """``ttl_tractometer_overlap`` on device tensors: (counts int64 [B][2],
     visited_bits int64 [X * Y * Z] holding the uint64 words).  ``visited_bits``
     (zeroed) may be given."""
-    from tracktolearn_amd import _lib
-    lib = _lib.load()
-    dev = points.device
-    n = int(offsets.shape[0]) - 1
     X, Y, Z = data.dims
     if visited_bits is None:
-        visited_bits = torch.zeros(X * Y * Z, dtype=torch.int64, device=dev)
-    counts = torch.empty((data.n_bundles, 2), dtype=torch.int64, device=dev)
-    pts = points.to(torch.float32).contiguous()
-    off = offsets.to(torch.int64).contiguous()
-    dims_c = (C.c_int32 * 3)(X, Y, Z)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.ttl_tractometer_overlap(
-            pts.data_ptr(), off.data_ptr(), max(n, 0), bundle.data_ptr(), dims_c,
-            data.n_bundles, data.gt.data_ptr(), visited_bits.data_ptr(), counts.data_ptr(),
-            stream), 'ttl_tractometer_overlap')
+        visited_bits = torch.zeros(X * Y * Z, dtype=torch.int64, device=points.device)
+    counts = torch.empty((data.n_bundles, 2), dtype=torch.int64, device=points.device)
+    # no row still launches: the counts are written
+    launch_ragged('ttl_tractometer_overlap', points, offsets, data.dims, (bundle.data_ptr(),),
+                  (data.n_bundles, data.gt.data_ptr(), visited_bits.data_ptr(),
+                   counts.data_ptr()))
     return counts, visited_bits
 
 
@@ -413,26 +399,64 @@ def invalid(points, offsets, bundle, data):
     """``ttl_tractometer_invalid`` on device tensors: pair int32 [n], i * R + j
     of the first invalid pair of ROIs a row without a bundle connects, else -1.
     ``data`` holds the ROI planes (``ScoringData(..., roi_masks, valid)``)."""
-    from tracktolearn_amd import _lib
-    lib = _lib.load()
     if data.roi is None:
         raise ValueError('the scoring data was packed without the ROI planes of the invalid '
                          'connections (compute_ic)')
-    dev = points.device
-    n = int(offsets.shape[0]) - 1
-    pair = torch.empty(max(n, 0), dtype=torch.int32, device=dev)
-    if n <= 0:
-        return pair
-    pts = points.to(torch.float32).contiguous()
-    off = offsets.to(torch.int64).contiguous()
-    dims_c = (C.c_int32 * 3)(*data.dims)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.ttl_tractometer_invalid(
-            pts.data_ptr(), off.data_ptr(), n, bundle.data_ptr(), dims_c, data.n_rois,
-            data.roi.data_ptr(), data.valid.data_ptr(), pair.data_ptr(), stream),
-            'ttl_tractometer_invalid')
+    pair = torch.empty(max(len(offsets) - 1, 0), dtype=torch.int32, device=points.device)
+    if len(pair):
+        launch_ragged('ttl_tractometer_invalid', points, offsets, data.dims, (bundle.data_ptr(),),
+                      (data.n_rois, data.roi.data_ptr(), data.valid.data_ptr(), pair.data_ptr()))
     return pair
+
+
+def segment(points, offsets, data, lin, compute_ic=False):
+    """The one device pass on the intake's arrays: upload, classify, overlap
+    and, when ``compute_ic`` and ``data`` holds the ROI planes, invalid."""
+    points = torch.from_numpy(points).to(data.device)
+    offsets = torch.from_numpy(offsets).to(data.device)
+    bundle, connected = classify(points, offsets, data, lin)
+    counts, _ = overlap(points, offsets, bundle, data)
+    pair = invalid(points, offsets, bundle, data) if compute_ic and data.roi is not None else None
+    return Segmentation(data, bundle, connected, counts, pair)
+
+
+class Segmentation(object):
+    """What the device pass left on the device: ``bundle`` int32 [n],
+    ``connected`` int64 [n], ``counts`` int64 [B][2] and ``pair`` int32 [n], or
+    None when the invalid connections were not computed."""
+
+    def __init__(self, data, bundle, connected, counts, pair=None):
+        self.data, self.bundle, self.connected = data, bundle, connected
+        self.counts, self.pair = counts, pair
+
+    def summary(self, wpc=False, per_pair=False):
+        """The one read-back, as named host integers: ``per_bundle`` [B]
+        streamlines per bundle, ``counts`` [B][2], ``wpc`` [B] (when asked, else
+        None) the rows without a bundle that connect a bundle's ROIs, ``invalid``
+        = (streamlines with an invalid pair, invalid pairs with a streamline) and,
+        when asked, ``per_pair`` [R * R] streamlines per pair i * R + j; both None
+        without ``pair``."""
+        B, R, dev = self.data.n_bundles, self.data.n_rois, self.bundle.device
+        parts = {'per_bundle': torch.bincount(self.bundle.to(torch.int64) + 1,
+                                              minlength=B + 1)[1:],
+                 'counts': self.counts.reshape(-1)}
+        if wpc:
+            wrong = self.connected[(self.bundle < 0) & (self.connected != 0)]
+            parts['wpc'] = ((wrong[:, None] >> torch.arange(B, device=dev)) & 1).sum(0)
+        if self.pair is not None:
+            pairs = torch.bincount(self.pair.to(torch.int64) + 1, minlength=R * R + 1)[1:]
+            if per_pair:
+                parts['per_pair'] = pairs
+            else:
+                parts['invalid'] = torch.stack([pairs.sum(), (pairs > 0).sum()])
+        back = torch.cat(list(parts.values())).cpu().numpy()
+        cuts = np.cumsum([len(part) for part in parts.values()])[:-1]
+        back = dict(zip(parts, np.split(back, cuts)))
+        if per_pair and self.pair is not None:
+            back['invalid'] = (back['per_pair'].sum(), np.count_nonzero(back['per_pair']))
+        return SimpleNamespace(per_bundle=back['per_bundle'], counts=back['counts'].reshape(B, 2),
+                               wpc=back.get('wpc'), invalid=back.get('invalid'),
+                               per_pair=back.get('per_pair'))
 
 
 # ---------------------------------------------------------------- validator
@@ -502,14 +526,13 @@ class TractometerValidator(Validator):
         voxels it passes through (``ttl_tract_coverage``)."""
         if path in cache:
             return cache[path]
-        lower = str(path).lower()
-        if lower.endswith(('.trk', '.tck')):
-            mask = self._mask_from_bundle(path)
-        else:
+        if str(path).lower().endswith(('.nii', '.nii.gz')):
             img = _load_image(path)
             mask = np.asarray(img.dataobj) != 0
             if self.dims is None:
                 self.dims = tuple(int(v) for v in mask.shape[:3])
+        else:
+            mask = self._mask_from_bundle(path)
         if tuple(mask.shape) != tuple(self.dims):
             raise ValueError(f'{path}: dimensions {tuple(mask.shape)} differ from the '
                              f"reference's {tuple(self.dims)}")
@@ -517,18 +540,17 @@ class TractometerValidator(Validator):
         return mask
 
     def _mask_from_bundle(self, path):
-        from tracktolearn_amd.io import streamlines as sio
-        if str(path).lower().endswith('.trk'):   # its own header is its reference
-            tract, header = sio.load_trk(path)
+        tract, header = load_tractogram(path)
+        if header is not None:                   # a .trk: its own header is its reference
             affine = np.asarray(header['voxel_to_rasmm'], np.float64)
             dims = tuple(int(v) for v in header['dimensions'])
+        elif self.ref_affine is None:
+            raise ValueError(f'{path}: a .tck bundle needs --tractometer_reference')
         else:
-            if self.ref_affine is None:
-                raise ValueError(f'{path}: a .tck bundle needs --tractometer_reference')
-            tract, _ = sio.load_tck(path)
             affine, dims = self.ref_affine, self.dims
         if self.dims is None:
             self.dims = dims
+        # not the intake: a one-point row of a bundle still marks its voxel
         points, offsets = pack([np.asarray(s) for s in tract.streamlines if len(s) >= 1])
         points = corner_voxels_from_rasmm(points, affine)
         visited = tract_coverage(torch.from_numpy(points).to(self.device),
@@ -547,43 +569,20 @@ class TractometerValidator(Validator):
 
     def __call__(self, tractogram_or_filename, env):
         ref_affine, _ = self.space(env)
-        points, offsets = packed_corner_voxels(tractogram_or_filename, env, ref_affine)
+        points, offsets, _ = corner_voxels(tractogram_or_filename, ref_affine,
+                                           env.affine_vox2rasmm)
         n = len(offsets) - 1
         if n == 0:
             return {}
-        data = self.data
-        pts = torch.from_numpy(points).to(self.device)
-        off = torch.from_numpy(offsets).to(self.device)
-        bundle, _ = classify(pts, off, data, ref_affine[:3, :3])
-        counts, _ = overlap(pts, off, bundle, data)
-        per_bundle = torch.bincount(bundle.to(torch.int64) + 1, minlength=data.n_bundles + 1)
-        parts = [per_bundle[1:], counts.reshape(-1)]
-        if self.compute_ic:
-            per_pair = self._per_pair(invalid(pts, off, bundle, data))
-            parts += [per_pair.sum().reshape(1), (per_pair > 0).sum().reshape(1)]
-        back = torch.cat(parts).cpu().numpy()
-        B = data.n_bundles
-        return metrics(n, back[:B], back[B:3 * B].reshape(B, 2), data.gt_sizes,
-                       invalid=back[3 * B:] if self.compute_ic else None)
-
-    def _per_pair(self, pair):
-        """Streamlines per pair i * R + j, int64 [R * R] on the device."""
-        R = self.data.n_rois
-        return torch.bincount(pair.to(torch.int64) + 1, minlength=R * R + 1)[1:]
+        s = segment(points, offsets, self.data, ref_affine[:3, :3], self.compute_ic).summary()
+        return metrics(n, s.per_bundle, s.counts, self.data.gt_sizes, invalid=s.invalid)
 
     # ---- the full result
     def load(self, filename):
         """A .trk / .tck for ``score_loaded``: (tractogram in RAS+mm, the .trk's
         header dict or None, the vox -> RAS mm affine it is scored in: the
         reference's when one was given, else the .trk's own)."""
-        from tracktolearn_amd.io import streamlines as sio
-        lower = str(filename).lower()
-        if lower.endswith('.trk'):
-            tract, header = sio.load_trk(filename)
-        elif lower.endswith('.tck'):
-            (tract, _), header = sio.load_tck(filename), None
-        else:
-            raise ValueError(f'{filename}: the Tractometer validator reads .trk or .tck')
+        tract, header = load_tractogram(filename)
         if self.ref_affine is not None:
             return tract, header, self.ref_affine
         if header is None:
@@ -598,24 +597,13 @@ class TractometerValidator(Validator):
         """(points, offsets, index, affine): the streamlines with >= 2 points
         in the voxel space they are scored in, corner origin, packed; ``index``
         their numbers in the input; ``affine`` that space's vox -> RAS mm."""
-        if isinstance(tractogram_or_filename, (str, bytes, os.PathLike)):
+        if isinstance(tractogram_or_filename, FILENAME):
             tract, _, affine = self.load(os.fsdecode(tractogram_or_filename))
-            return self._from_rasmm(tract.streamlines, affine)
-        if env is None:
-            raise ValueError('an in-memory tractogram is in the voxel space of its env: '
-                             'give the env')
-        lines = getattr(tractogram_or_filename, 'streamlines', tractogram_or_filename)
-        affine, _ = self.space(env)
-        index = np.array([i for i, s in enumerate(lines) if len(s) >= 2], np.int64)
-        points, offsets = pack([np.asarray(lines[i]) for i in index])
-        return (corner_voxels_from_tracker(points, env.affine_vox2rasmm, affine), offsets,
-                index, affine)
-
-    @staticmethod
-    def _from_rasmm(lines, affine):
-        index = np.array([i for i, s in enumerate(lines) if len(s) >= 2], np.int64)
-        points, offsets = pack([np.asarray(lines[i]) for i in index])
-        return corner_voxels_from_rasmm(points, affine), offsets, index, affine
+            return corner_voxels(tract, affine, in_rasmm=True) + (affine,)
+        # without an env the intake raises before it looks at the affine
+        affine = None if env is None else self.space(env)[0]
+        return corner_voxels(tractogram_or_filename, affine,
+                             getattr(env, 'affine_vox2rasmm', None)) + (affine,)
 
     def score(self, tractogram_or_filename, env=None):
         """The full result of ``full_scores`` plus ``bundle`` and ``pair`` (int32
@@ -627,38 +615,27 @@ class TractometerValidator(Validator):
 
     def score_loaded(self, tractogram, affine):
         """``score`` of what ``load`` returned."""
-        return self._score(*self._from_rasmm(tractogram.streamlines, affine))
+        return self._score(*corner_voxels(tractogram, affine, in_rasmm=True), affine)
 
     def _score(self, points, offsets, index, affine):
         n = len(offsets) - 1
         if n == 0:
             return {}
-        data, B = self.data, self.data.n_bundles
-        pts = torch.from_numpy(points).to(self.device)
-        off = torch.from_numpy(offsets).to(self.device)
-        bundle, connected = classify(pts, off, data, affine[:3, :3])
-        counts, _ = overlap(pts, off, bundle, data)
-        per_bundle = torch.bincount(bundle.to(torch.int64) + 1, minlength=B + 1)
-        # WPC: the bundles whose ROIs a row without a bundle connects
-        wrong = connected[(bundle < 0) & (connected != 0)]
-        wpc = ((wrong[:, None] >> torch.arange(B, device=self.device)) & 1).sum(0)
-        back = torch.cat([per_bundle[1:], counts.reshape(-1), wpc]).cpu().numpy()
-        invalid_bundles = None
-        pair = torch.full_like(bundle, -1)
-        if self.compute_ic:
-            pair = invalid(pts, off, bundle, data)
-            per_pair = self._per_pair(pair).cpu().numpy()
-            R = data.n_rois
+        seg = segment(points, offsets, self.data, affine[:3, :3], self.compute_ic)
+        s = seg.summary(wpc=True, per_pair=True)
+        invalid_bundles, pair = None, np.full(n, -1, np.int32)
+        if seg.pair is not None:
+            R, pair = self.data.n_rois, seg.pair.cpu().numpy()
             invalid_bundles = {
-                f'{self.roi_names[k // R]}__{self.roi_names[k % R]}': int(per_pair[k])
-                for k in np.flatnonzero(per_pair)}
-        out = full_scores(n, self.bundle_names, back[:B], back[B:3 * B].reshape(B, 2),
-                          data.gt_sizes, back[3 * B:], invalid_bundles)
-        out.update(bundle=bundle.cpu().numpy(), pair=pair.cpu().numpy(), index=index)
+                f'{self.roi_names[k // R]}__{self.roi_names[k % R]}': int(s.per_pair[k])
+                for k in np.flatnonzero(s.per_pair)}
+        out = full_scores(n, self.bundle_names, s.per_bundle, s.counts, self.data.gt_sizes,
+                          s.wpc, invalid_bundles)
+        out.update(bundle=seg.bundle.cpu().numpy(), pair=pair, index=index)
         return out
 
 
 __all__ = ['TractometerValidator', 'ScoringData', 'read_config_file', 'compute_endpoint_masks',
            'dilate', 'pack_bit_planes', 'limits_table', 'metrics', 'classify', 'overlap',
            'rois_and_pairs', 'roi_names', 'pack_roi_words', 'pack_valid_words', 'full_scores',
-           'invalid']
+           'invalid', 'segment', 'Segmentation']
