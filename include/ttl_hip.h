@@ -493,6 +493,71 @@ TTL_API int ttl_scripted_actions(const float *state, int64_t state_pitch,
                          int32_t n, uint32_t seed, uint32_t step, float wobble,
                          float *actions_out, void *hip_stream);
 
+/* fODF policy (TTL_HAS_ODF_POLICY): classical tracking from the
+ * fODF as a policy, state rows -> actions.  Per row i:
+ *   sh[c]  = state[i][c], c < n_coef (the SH coefficients interpolated at the
+ *            streamline's head: block 0 of the neighbourhood);
+ *   p      = state[i][dir_offset .. dir_offset + 2], the newest previous
+ *            direction (zero at the first step of an episode);
+ * per call: sf_matrix [n_coef][n_vertices] f32; dirs [n_vertices][3] f32, unit
+ * vectors of one hemisphere in the env's voxel axes (the library knows no
+ * affine); cos_theta, the cosine of the cone's half angle; rel_threshold; mode;
+ * seed.  All arithmetic in float32, one rounding per multiply and per add, sums
+ * serial (c ascending, then v ascending); tests/ref_odf_policy.py restates it.
+ *   sf[v]      = sum_c sh[c] * B[c][v]; gmax = max_v sf[v], by `>` from -inf (a
+ *                comparison with NaN is false: a NaN never wins);
+ *   cone       only when p != 0: vertex v is in the cone when
+ *                |p . d_v| >= cos_theta * ||p||  (inclusive, two-sided: a
+ *                hemisphere vertex stands for +-d), p . d = (px dx + py dy) + pz dz,
+ *                ||p|| = sqrt((px px + py py) + pz pz);
+ *   admissible in the cone (or p == 0), sf[v] > 0 and sf[v] >= rel_threshold * gmax
+ *                (relative to the whole hemisphere's maximum, not the cone's);
+ *   TTL_ODF_DET  the admissible vertex of largest sf, ties to the lowest index;
+ *   TTL_ODF_PROB cdf[v] = sum of sf over the admissible vertices <= v (serial); the
+ *                pick is the first v with cdf[v] > u * cdf[V - 1];
+ *   u          Philox4x32-10 as for the keyed noise, key = the two halves of
+ *                `seed`, counter = (id low, id high, step, TTL_ODF_STREAM);
+ *                u = (output word 0 >> 8) * 2^-24, in [0, 1);
+ *                id = ids_base + continue_idx[i] (the keyed noise's id), so a
+ *                pick depends on neither batch size, row order nor loop flavour;
+ *   action     d_v, negated when p . d_v < 0 (+ when it is 0 or p == 0);
+ *   fallback   no admissible vertex: the action is p as given (straight on; the
+ *                mask or the curvature test ends the row), dirs[0] when p == 0;
+ *                vertex_out = -1.
+ * state [n][state_pitch] f32, continue_idx [n] int32, actions_out [n][3] f32,
+ * vertex_out [n] int32 or NULL (the chosen vertex), all device.  TTL_ERR_INVALID
+ * for a null pointer, n < 0, n_coef outside 1 .. TTL_ODF_MAX_COEF, n_vertices < 1,
+ * dir_offset < 0, a state_pitch below n_coef or dir_offset + 3, an unknown mode
+ * or ids_base < 0; n == 0 launches nothing.  One lane per row; a launch has at most
+ * TTL_ODF_GRID_CAP workgroups, each taking groups of 256 rows in a loop, with
+ * sf_matrix and dirs staged in LDS (in chunks of vertices where they do not fit:
+ * n_vertices has no upper limit; TTL_ERR_UNSUPPORTED where the device gives a
+ * workgroup too little LDS for one chunk). */
+#define TTL_HAS_ODF_POLICY 1
+#define TTL_ODF_DET 0
+#define TTL_ODF_PROB 1
+#define TTL_ODF_MAX_COEF 64        /* the widest SH record of the deduplicating gather */
+#define TTL_ODF_GRID_CAP 1024
+#define TTL_ODF_STREAM 0x4F444650u /* counter word 3 ("ODFP"); the keyed noise uses 0 and 1 */
+TTL_API int ttl_odf_actions(const float *state, int64_t state_pitch, int32_t n_coef,
+                            int32_t dir_offset, const float *sf_matrix, const float *dirs,
+                            int32_t n_vertices, float cos_theta, float rel_threshold,
+                            int32_t mode, uint64_t seed, int64_t ids_base,
+                            const int32_t *continue_idx, int32_t n, uint32_t step,
+                            float *actions_out, int32_t *vertex_out, void *hip_stream);
+/* The same for a free-running step (capturable in the step's graph): the row
+ * count, the step number (length - 1) and the live continue_idx buffer are
+ * read from the device words; rows 0..min(n_active, n_rows)-1 are written.
+ * n_rows in 1 .. the rows at ttl_env_freerun_begin; TTL_ERR_STATE unless
+ * free-running. */
+TTL_API int ttl_env_freerun_odf_actions(ttl_env *env, const float *state, int64_t state_pitch,
+                                        int32_t n_coef, int32_t dir_offset,
+                                        const float *sf_matrix, const float *dirs,
+                                        int32_t n_vertices, float cos_theta,
+                                        float rel_threshold, int32_t mode, uint64_t seed,
+                                        int64_t ids_base, int32_t n_rows, float *actions_out,
+                                        int32_t *vertex_out, void *hip_stream);
+
 /* fODF peaks of an SH volume (replaces the per-voxel Python loop of
  * TrackToLearn/environments/env.py:405-432: sh_to_sf_matrix + get_maximas per
  * voxel, 5 peaks scaled by value / first value).  sh: [n_voxels][n_coef] f32;

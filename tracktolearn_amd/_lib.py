@@ -30,6 +30,8 @@ TRACT_FILE_TRK, TRACT_FILE_TCK = 0, 1
 TRACTOMETER_LIMITS = 16               # TTL_TRACTOMETER_LIMITS
 TRACTOMETER_MAX_ROIS = 128            # TTL_TRACTOMETER_MAX_ROIS
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4
+ODF_DET, ODF_PROB = 0, 1                # TTL_ODF_DET / TTL_ODF_PROB
+ODF_MAX_COEF, ODF_GRID_CAP = 64, 1024   # TTL_ODF_MAX_COEF / TTL_ODF_GRID_CAP
 
 
 class TTLError(RuntimeError):
@@ -195,6 +197,15 @@ SYMBOLS = {
                                        C.c_void_p, C.c_int32, C.c_uint32,
                                        C.c_uint32, C.c_float, C.c_void_p,
                                        C.c_void_p]),
+    'ttl_odf_actions': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_int32,
+                                  C.c_uint64, C.c_int64, C.c_void_p, C.c_int32, C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_env_freerun_odf_actions': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_float, C.c_float, C.c_int32, C.c_uint64,
+                                              C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
     'ttl_peaks_from_sh': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.c_float, C.c_float,

@@ -216,21 +216,7 @@ __device__ __forceinline__ double spline3_value(const double *__restrict__ coef,
 // four output words of call j make two 53-bit uniforms, Box-Muller in float64
 // turns them into z[2j], z[2j + 1].  tests/ref_noise.py restates it in NumPy.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2,
-                                              uint32_t &c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
+// (philox4x32_10: ttl_internal.h, shared with ttl_odf_policy.hip)
 // ((hi:lo >> 11) + 0.5) * 2^-53
 __device__ __forceinline__ double philox_uniform(uint32_t lo, uint32_t hi) {
     const unsigned long long w = ((unsigned long long)hi << 32) | lo;
@@ -2475,6 +2461,18 @@ int ttl_env_freerun_scripted_actions(ttl_env *env, const float *state, int64_t s
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
+
+}  // extern "C"
+
+// ttl_odf_policy.hip: the device words a free-running policy kernel reads
+void ttl_detail_freerun_view(const ttl_env *env, FreerunView *out) {
+    out->cap = env->fr_cap;
+    out->live = env->P.counts + TTL_FR_LIVE;
+    out->idx_a = env->d.idx_a;
+    out->idx_b = env->d.idx_b;
+}
+
+extern "C" {
 
 int ttl_env_freerun_end(ttl_env *env, int32_t *n_active_out, int32_t *length_out,
                         int32_t *steps_out, void *hip_stream) {

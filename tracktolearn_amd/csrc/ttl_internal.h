@@ -86,6 +86,33 @@ constexpr int TTL_FR_SNAP = 16;
 // aligned: counts is 256-byte aligned), written by ttl_env_freerun_begin
 constexpr int TTL_FR_NOISE = 32;
 
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): the counter-based
+// generator of the keyed action noise (ttl_hip.hip) and of the fODF policy's
+// uniforms (ttl_odf_policy.hip); tests/ref_noise.py restates it in NumPy.
+__device__ __forceinline__ void philox4x32_10(uint32_t &c0, uint32_t &c1, uint32_t &c2,
+                                              uint32_t &c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// What a policy kernel of a free-running step reads (ttl_env_freerun_*): the live
+// words {n_active, length, cur, steps done} and the two continue_idx buffers
+// (cur picks); cap = rows at ttl_env_freerun_begin, 0: not free-running
+struct FreerunView {
+    const int *live, *idx_a, *idx_b;
+    int cap;
+};
+void ttl_detail_freerun_view(const ttl_env *env, FreerunView *out);
+
 // Record index of voxel (x, y, z) = vox_x(x) + vox_y(y) + vox_z(z), for both
 // record orders (separable, so the gather keeps per-axis partial offsets).
 __device__ __forceinline__ unsigned vox_x(const EnvParams &P, int x) {

@@ -336,6 +336,7 @@ class TrackingEnvironment(BaseEnv):
     def nreset(self, n_seeds: int):
         """N random seeds among all seeds (tracking_env.py:47-89; global
         numpy RNG, as the reference)."""
+        self._id_base = 0
         replace = n_seeds > len(self.seeds)
         picks = np.random.choice(
             np.arange(len(self.seeds)), size=n_seeds, replace=replace)
@@ -343,6 +344,7 @@ class TrackingEnvironment(BaseEnv):
 
     def reset(self, start: int, end: int):
         """A given batch of seeds (tracking_env.py:91-133)."""
+        self._id_base = int(start)
         return self._start(self.seeds[start:end])
 
     # ------------------------------------------------------------------ #
@@ -665,6 +667,10 @@ class TrackingEnvironment(BaseEnv):
     #: TTL_FUSE_MAX_ROWS clamped as ttl_env_create clamps it)
     FREERUN_MAX = min(max(int(os.environ.get('TTL_FUSE_MAX_ROWS', '16384')), 256), 65536)
 
+    #: between ttl_env_freerun_begin and _end (``run_free`` / ``run_free_eager``):
+    #: a policy that reads the device words takes its free-running entry point
+    _free_running = False
+
     def _has_action_noise(self):
         return False
 
@@ -736,6 +742,7 @@ class TrackingEnvironment(BaseEnv):
         _lib.check(self._lib.ttl_env_freerun_begin(
             self._handle, self._host_counts.data_ptr(), self._stream()),
             'ttl_env_freerun_begin')
+        self._free_running = True
         try:
             counts = self._host_counts_np
             step_fn, handle, pitch = self._lib.ttl_env_freerun_step, self._handle, self._state_pitch
@@ -759,6 +766,7 @@ class TrackingEnvironment(BaseEnv):
                 steps += 1
                 self._wait_for_gpu(counts, steps - lookahead)
         finally:
+            self._free_running = False
             n_left, length, done_steps = C.c_int32(), C.c_int32(), C.c_int32()
             _lib.check(self._lib.ttl_env_freerun_end(
                 self._handle, C.byref(n_left), C.byref(length), C.byref(done_steps),
@@ -816,6 +824,7 @@ class TrackingEnvironment(BaseEnv):
             return None         # the library has no free-running path here: the caller
             #                     keeps its step-by-step loop (as for a slow policy)
         _lib.check(rc, 'ttl_env_freerun_begin')
+        self._free_running = True
         try:
             if fr is None:      # buffers + one timing of the policy on n rows (the policy
                 # may itself read the free-running words: timed after begin)
@@ -848,6 +857,7 @@ class TrackingEnvironment(BaseEnv):
                 if counts[0] != 0:
                     self._wait_for_gpu(counts, steps - 24)
         finally:
+            self._free_running = False
             n_left, length, done = C.c_int32(), C.c_int32(), C.c_int32()
             _lib.check(self._lib.ttl_env_freerun_end(
                 self._handle, C.byref(n_left), C.byref(length), C.byref(done),
@@ -913,6 +923,66 @@ class TrackingEnvironment(BaseEnv):
             self._handle, state.data_ptr(), state.stride(0), 7 * self._n_coef, n,
             int(seed) & 0xffffffff, float(wobble), out.data_ptr(), self._stream()),
             'ttl_env_freerun_scripted_actions')
+        return out
+
+    # ------------------------------------------------------------------ #
+    # fODF policy (tracking/odf_policy.py; ttl_odf_actions)
+    #: streamline g of the batch is seed ``_id_base + g`` of the run (what
+    #: ``reset(start, end)`` was given; the keyed noise counts the same way)
+    _id_base = 0
+
+    def streamline_id_base(self):
+        """Id of the batch's first streamline: the keyed noise's id base."""
+        return int(getattr(self, 'noise_id_offset', 0)) + int(self._id_base)
+
+    def _odf_args(self, sf_matrix, dirs, cos_theta, rel_threshold, mode, seed, id_base):
+        # (the signal may carry more channels than SH coefficients: --input_wm)
+        C_sh = int(sf_matrix.shape[0])
+        if not 1 <= C_sh <= self._n_coef or dirs.shape != (sf_matrix.shape[1], 3):
+            raise ValueError(f'sf_matrix {tuple(sf_matrix.shape)} / dirs {tuple(dirs.shape)} '
+                             f'do not fit a signal of {self._n_coef} channels')
+        for t in (sf_matrix, dirs):
+            if t.dtype is not torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError('sf_matrix and dirs must be contiguous float32 tensors on '
+                                 'the env\'s device')
+        if id_base is None:
+            id_base = self.streamline_id_base()
+        return (C_sh, 7 * self._n_coef, sf_matrix.data_ptr(), dirs.data_ptr(), int(dirs.shape[0]),
+                float(cos_theta), float(rel_threshold), int(mode),
+                int(seed) & 0xffffffffffffffff, int(id_base))
+
+    def odf_actions(self, state, step, sf_matrix, dirs, cos_theta, rel_threshold=0.1,
+                    mode=_lib.ODF_DET, seed=0, id_base=None, return_vertex=False):
+        """Classical fODF tracking as the policy: (n_active, 3) float32 actions
+        on the GPU from ``ttl_odf_actions`` -- the SH coefficients at the head
+        (the first columns of ``state``) evaluated on the hemisphere ``dirs``
+        (voxel axes) through ``sf_matrix``, the strongest (``ODF_DET``) or a
+        sampled (``ODF_PROB``) direction inside the cone around the previous
+        one.  ``step`` and ``seed`` key the sampling together with the
+        streamline id ``id_base + continue_idx`` (default: the batch's own).
+        ``return_vertex``: also the chosen vertex per row (int32, -1 = none
+        admissible)."""
+        n = self._n_active
+        out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        vert = torch.empty(n, dtype=torch.int32, device=self.device) if return_vertex else None
+        a = self._odf_args(sf_matrix, dirs, cos_theta, rel_threshold, mode, seed, id_base)
+        _lib.check(self._lib.ttl_odf_actions(
+            state.data_ptr(), state.stride(0), *a, self._idx_view(n).data_ptr(), n, int(step),
+            out.data_ptr(), vert.data_ptr() if vert is not None else None, self._stream()),
+            'ttl_odf_actions')
+        return (out, vert) if return_vertex else out
+
+    def odf_actions_free(self, state, sf_matrix, dirs, cos_theta, rel_threshold=0.1,
+                         mode=_lib.ODF_DET, seed=0, id_base=None):
+        """``odf_actions`` as the policy of a free-running episode (``run_free``
+        / ``run_free_eager``): row count, step number and continue_idx are read
+        on the device; actions for ``len(state)`` rows."""
+        n = int(state.shape[0])
+        out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        a = self._odf_args(sf_matrix, dirs, cos_theta, rel_threshold, mode, seed, id_base)
+        _lib.check(self._lib.ttl_env_freerun_odf_actions(
+            self._handle, state.data_ptr(), state.stride(0), *a, n, out.data_ptr(), None,
+            self._stream()), 'ttl_env_freerun_odf_actions')
         return out
 
     #: kernel classes `profile_begin` can bracket (ttl_env_profile_begin's mask bits)

@@ -7,6 +7,11 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--hyperparameters JSON] [--n_actor N] [--npv N] [--min_length m]
         [--max_length M] [--noise s] [--keyed_noise] [--fa_map F] [--bidirectional]
         [--binary_stopping_threshold t] [--rng_seed S] [--direct_output]
+        [--odf_policy {det,prob}] [--theta DEG] [--sf_threshold R] [--step_size MM]
+
+With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
+itself (classical deterministic / probabilistic tracking as one GPU kernel,
+tracking/odf_policy.py).
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -90,17 +95,40 @@ class TrackToLearnTrack(object):
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
-        with open(self.hyperparameters, 'r') as json_file:
-            hyper = json.load(json_file)
-        for key, attr in _HYPER.items():
-            setattr(self, attr, hyper[key])
-        self.step_size = float(hyper['step_size'])
-        self.voxel_size = hyper.get('voxel_size', 2.0)
+        self.odf_policy = track_dto.get('odf_policy')
+        if self.odf_policy:
+            self._odf_settings(track_dto)
+        else:
+            with open(self.hyperparameters, 'r') as json_file:
+                hyper = json.load(json_file)
+            for key, attr in _HYPER.items():
+                setattr(self, attr, hyper[key])
+            self.step_size = float(hyper['step_size'])
+            self.voxel_size = hyper.get('voxel_size', 2.0)
         self.random_seed = track_dto['rng_seed']
         torch.manual_seed(self.random_seed)
         np.random.seed(self.random_seed)
         random.seed(self.random_seed)
         self.rng = np.random.RandomState(seed=self.random_seed)
+
+    #: the env's curvature criterion is this much wider than the policy's cone:
+    #: the cone decides, not the rounding of the segment rebuilt from two points
+    ODF_CURVATURE_MARGIN = 5.0
+
+    def _odf_settings(self, track_dto):
+        """What hyperparameters.json supplies for an agent, for ``--odf_policy``:
+        the SH order of the file, the step in mm as given, the cone."""
+        from tracktolearn_amd.datasets.utils import get_sh_order_and_fullness
+        from tracktolearn_amd.tracking.odf_policy import DEFAULT_THETA
+        self.algorithm, self.hidden_dims = 'OdfTracking', None
+        self.n_dirs = 4
+        self.odf_theta = float(track_dto.get('theta') or DEFAULT_THETA[self.odf_policy])
+        self.sf_threshold = float(track_dto.get('sf_threshold', 0.1))
+        self.theta = min(self.odf_theta + self.ODF_CURVATURE_MARGIN, 180.0)
+        self.target_sh_order = get_sh_order_and_fullness(
+            nifti.load(self.in_odf).shape[-1])[0]
+        self.step_size = float(track_dto.get('step_size') or 0.75)
+        self.voxel_size = None
 
     def get_tracking_env(self):
         """The noisy env over the input files (experiment.py:177-204)."""
@@ -121,6 +149,8 @@ class TrackToLearnTrack(object):
     def _step_for_subject(self, subject_voxel_size):
         """Keep the number of voxels traversed per step of the training: an agent
         trained at another voxel size steps proportionally (ttl_track.py:145-157)."""
+        if self.voxel_size is None:         # --odf_policy: the step is given in mm
+            return self.step_size
         trained = float(self.voxel_size)
         if abs(float(subject_voxel_size) - trained) < 0.1:
             return self.step_size
@@ -132,6 +162,11 @@ class TrackToLearnTrack(object):
         return step_size_mm
 
     def _load_policy(self, env):
+        if self.odf_policy:
+            from tracktolearn_amd.tracking.odf_policy import OdfTracking
+            print('Tracking with the fODF ({}).'.format(self.odf_policy))
+            return OdfTracking(env, self.odf_policy, self.odf_theta, self.sf_threshold,
+                               seed=self.random_seed)
         input_size = env.reset(0, 1).shape[1]
         print('Tracking with {} agent.'.format(self.algorithm))
         alg = {'SACAuto': SACAuto}[self.algorithm](
@@ -254,6 +289,24 @@ def add_track_args(parser):
                          help='Lower limit for interpolation of tracking mask '
                               'value.\nTracking will stop below this '
                               'threshold.')
+    odf_g = parser.add_argument_group(
+        'Classical tracking from the fODF',
+        'Without a trained agent: follow the fODF itself. Makes --agent and '
+        '--hyperparameters\nunnecessary.')
+    odf_g.add_argument('--odf_policy', choices=['det', 'prob'], default=None,
+                       help='det: at each step the strongest direction of the '
+                            'spherical function inside a cone\naround the '
+                            'previous direction; prob: one sampled in '
+                            'proportion to it, as a function of\n(--rng_seed, '
+                            'seed index, step).')
+    odf_g.add_argument('--theta', type=float, default=None, metavar='DEG',
+                       help='Half angle of the cone in degrees. [45 for det, 20 '
+                            'for prob]')
+    odf_g.add_argument('--sf_threshold', type=float, default=None, metavar='R',
+                       help='Directions below this share of the spherical '
+                            'function\'s maximum are not followed. [0.1]')
+    odf_g.add_argument('--step_size', type=float, default=None, metavar='MM',
+                       help='Step size in mm. [0.75]')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -287,7 +340,26 @@ def parse_args(argv=None):
         parser.error('min_length must be >= 0 and <= max_length.')
     if args.compress is not None and not 0.001 <= args.compress <= 1:
         parser.error('The compression threshold must be in [0.001, 1] mm.')
-    verify_agent_option(parser, args)
+    if args.odf_policy:
+        if args.agent is not None or args.hyperparameters is not None:
+            parser.error('--odf_policy tracks without an agent: drop --agent / '
+                         '--hyperparameters.')
+        if args.noise:
+            parser.error('--noise perturbs an agent\'s output; with --odf_policy use '
+                         '--odf_policy prob.')
+        if args.theta is not None and not 0 <= args.theta <= 90:
+            parser.error('--theta must be in [0, 90] degrees.')
+        if args.sf_threshold is not None and not 0 <= args.sf_threshold <= 1:
+            parser.error('--sf_threshold must be in [0, 1].')
+        if args.step_size is not None and not args.step_size > 0:
+            parser.error('--step_size must be positive.')
+        if args.sf_threshold is None:
+            args.sf_threshold = 0.1
+    else:
+        for name in ('theta', 'sf_threshold', 'step_size'):
+            if getattr(args, name) is not None:
+                parser.error('--{} is used only with --odf_policy.'.format(name))
+        verify_agent_option(parser, args)
     return args
 
 
