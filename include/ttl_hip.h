@@ -688,7 +688,10 @@ TTL_API int ttl_tract_coverage(const float *points, const int64_t *offsets, int3
  *             u1, u2 the unit eigenvectors of its two largest eigenvalues (cyclic Jacobi,
  *             a fixed number of sweeps), p_j = (q_j . u1, q_j . u2), winding = (180 / pi)
  *             sum_j acos(clip(p_j . p_j+1 / (|p_j| |p_j+1|), -1, 1)); the bundle passes iff
- *             winding < angle (strict; a NaN fails); angle = +inf: not tested.
+ *             winding < angle (strict: a winding equal to the angle fails, and so does a
+ *             NaN, which a p_j = 0 gives, against every finite angle).  A bundle with
+ *             angle = +inf sets no angle: the criterion is skipped, the winding is not
+ *             computed for it, and a NaN passes.
  *   valid(b)  = connects(b) and every criterion above that bundle b sets.
  * ttl_tractometer_classify writes bundle[s] = the lowest b with valid(b), else -1, and
  * connected[s] = the bit set of b with connects(b) (int32 [n], uint64 [n], device).  A row

@@ -253,3 +253,172 @@ def margin_report(points, dims, bundles, lin):
                         bool(lam[1] - lam[2] >= 1e-3 * lam[0])))
             out.append((b, 'pmin', pmin, 1e-9, bool(pmin >= 1e-9)))
     return out
+
+
+# ------------------------------------ the classify kernel's values (winding and sums)
+# What tests/test_tractometer_values.py measures the kernel against: the
+# header's definition at 50 digits, and ``wave_winding`` of
+# csrc/ttl_tractometer.hip restated in NumPy float64 with named deviations.
+MP_DIGITS = 50
+
+WINDING_MUTANTS = (
+    'no_clip',             # acos of the unclipped quotient
+    'skip_last_segment',   # j < L - 2
+    'radians',             # no 180 / pi
+    'non_strict',          # winding <= angle (a decision, not a value: see winding_passes)
+    'one_sweep',           # one Jacobi sweep instead of eight
+    'drop_largest',        # the plane of the two smallest eigenvalues
+    'rotation_sign',       # s negated in the eigenvector update
+    'stale_offdiag',       # apr / aqr not updated by a rotation
+    'uncentred',           # mean left out
+    'first_64_points',     # no stride loop: one point and one segment per lane
+)
+
+
+def _exact(points):
+    """The float32 points as Python floats (exact), [L][3]."""
+    return np.asarray(points, np.float32).astype(np.float64).reshape(-1, 3).tolist()
+
+
+def winding_mp(points):
+    """The header's winding with mpmath at MP_DIGITS digits, on the float32
+    points read exactly, the plane from ``mp.eigsy``.  A dict of mpf:
+    ``winding`` (degrees; NaN when some p_j is 0), ``lam`` (eigenvalues,
+    descending), ``pmin`` / ``pmax`` (min / max |p_j|) and ``vmin`` / ``vmax``
+    (the extreme acos arguments before the clip; None with fewer than 2 points
+    or a zero p_j)."""
+    import mpmath
+    mp = mpmath.mp
+    with mp.workdps(MP_DIGITS):
+        c = [[mp.mpf(x) for x in row] for row in _exact(points)]
+        L = len(c)
+        mean = [mp.fsum(row[k] for row in c) / L for k in range(3)]
+        q = [[row[k] - mean[k] for k in range(3)] for row in c]
+        S = mp.matrix(3, 3)
+        for a in range(3):
+            for b in range(3):
+                S[a, b] = mp.fsum(row[a] * row[b] for row in q)
+        E, Q = mp.eigsy(S)                               # ascending
+        order = sorted(range(3), key=lambda i: E[i], reverse=True)
+        u = [[Q[k, order[i]] for k in range(3)] for i in range(2)]
+        p = [[mp.fsum(row[k] * u[i][k] for k in range(3)) for i in range(2)] for row in q]
+        norms = [mp.sqrt(a * a + b * b) for a, b in p]
+        out = {'lam': [E[i] for i in order], 'pmin': min(norms), 'pmax': max(norms),
+               'vmin': None, 'vmax': None, 'winding': mp.nan}
+        if L >= 2 and min(norms) > 0:
+            v = [(p[j][0] * p[j + 1][0] + p[j][1] * p[j + 1][1]) / (norms[j] * norms[j + 1])
+                 for j in range(L - 1)]
+            out['vmin'], out['vmax'] = min(v), max(v)
+            out['winding'] = mp.fsum(mp.acos(max(-1, min(1, x))) for x in v) * 180 / mp.pi
+        return out
+
+
+def sums_mp(points, lin):
+    """The header's sums with mpmath at MP_DIGITS digits: a dict of mpf,
+    ``length``, ``dir`` [3] and ``absdir`` [3], from the float32 points and the
+    float64 ``lin`` read exactly."""
+    import mpmath
+    mp = mpmath.mp
+    with mp.workdps(MP_DIGITS):
+        c = [[mp.mpf(x) for x in row] for row in _exact(points)]
+        m = [[mp.mpf(float(x)) for x in row] for row in np.asarray(lin, np.float64).reshape(3, 3)]
+        v = [[mp.fsum(m[k][i] * (c[j + 1][i] - c[j][i]) for i in range(3)) for k in range(3)]
+             for j in range(len(c) - 1)]
+        return {'length': mp.fsum(mp.sqrt(mp.fsum(x * x for x in row)) for row in v),
+                'dir': [abs(mp.fsum(row[k] for row in v)) for k in range(3)],
+                'absdir': [mp.fsum(abs(row[k]) for row in v) for k in range(3)]}
+
+
+_LANES = np.arange(64)
+
+
+def wave_sum(terms):
+    """The kernel's sum of one term per j: lane l adds j = l, l + 64, ... in
+    that order onto 0.0, then the xor butterfly 32, 16, .. 1."""
+    terms = np.asarray(terms, np.float64)
+    rows = -(-len(terms) // 64)
+    padded = np.zeros(max(rows, 1) * 64)
+    padded[:len(terms)] = terms
+    acc = np.zeros(64)
+    for r in range(rows):
+        acc = acc + padded[64 * r:64 * (r + 1)]
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[_LANES ^ off]
+    return float(acc[0])
+
+
+def _jacobi_rotate(a, p, q, r, V, mutant):
+    """One rotation in the (p, q) plane of the symmetric 3x3 ``a`` (a dict
+    keyed by the sorted index pair), r the third index; V[k][i] = component k
+    of eigenvector column i."""
+    pq, pr, qr = (min(p, q), max(p, q)), (min(p, r), max(p, r)), (min(q, r), max(q, r))
+    apq = a[pq]
+    if apq == 0.0:
+        return
+    theta = (a[(q, q)] - a[(p, p)]) / (2.0 * apq)
+    t = (1.0 if theta >= 0.0 else -1.0) / (abs(theta) + math.sqrt(theta * theta + 1.0))
+    c = 1.0 / math.sqrt(t * t + 1.0)
+    s = t * c
+    a[(p, p)] -= t * apq
+    a[(q, q)] += t * apq
+    a[pq] = 0.0
+    if mutant != 'stale_offdiag':
+        x, y = a[pr], a[qr]
+        a[pr] = c * x - s * y
+        a[qr] = s * x + c * y
+    if mutant == 'rotation_sign':
+        s = -s
+    for k in range(3):
+        x, y = V[k][p], V[k][q]
+        V[k][p] = c * x - s * y
+        V[k][q] = s * x + c * y
+
+
+def winding_jacobi(points, mutant=None):
+    """``wave_winding`` (and the centroid of step 2 of the kernel) restated in
+    NumPy float64, operation for operation: (winding in degrees, the slot 0 / 1
+    / 2 whose eigenvector is dropped)."""
+    c = np.asarray(points, np.float32).astype(np.float64).reshape(-1, 3)
+    L = len(c)
+    mean = np.array([wave_sum(c[:, k]) / float(L) for k in range(3)])
+    if mutant == 'uncentred':
+        mean = np.zeros(3)
+    head = c[:64] if mutant == 'first_64_points' else c
+    x, y, z = (head[:, k] - mean[k] for k in range(3))
+    a = {(0, 0): wave_sum(x * x), (0, 1): wave_sum(x * y), (0, 2): wave_sum(x * z),
+         (1, 1): wave_sum(y * y), (1, 2): wave_sum(y * z), (2, 2): wave_sum(z * z)}
+    V = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    for _ in range(1 if mutant == 'one_sweep' else 8):
+        _jacobi_rotate(a, 0, 1, 2, V, mutant)
+        _jacobi_rotate(a, 0, 2, 1, V, mutant)
+        _jacobi_rotate(a, 1, 2, 0, V, mutant)
+    s00, s11, s22 = a[(0, 0)], a[(1, 1)], a[(2, 2)]
+    if mutant == 'drop_largest':
+        drop0 = s00 >= s11 and s00 >= s22
+        drop1 = not drop0 and s11 >= s22
+    else:
+        drop0 = s00 <= s11 and s00 <= s22
+        drop1 = not drop0 and s11 <= s22
+    i1, i2 = (1 if drop0 else 0), (2 if drop0 or drop1 else 1)
+    u1 = [V[k][i1] for k in range(3)]
+    u2 = [V[k][i2] for k in range(3)]
+    last = L - 2 if mutant == 'skip_last_segment' else L - 1
+    if mutant == 'first_64_points':
+        last = min(last, 64)
+    q = c[:last + 1] - mean
+    px = (q[:, 0] * u1[0] + q[:, 1] * u1[1]) + q[:, 2] * u1[2]
+    py = (q[:, 0] * u2[0] + q[:, 1] * u2[1]) + q[:, 2] * u2[2]
+    ax, ay, bx, by = px[:-1], py[:-1], px[1:], py[1:]
+    with np.errstate(invalid='ignore', divide='ignore'):
+        v = (ax * bx + ay * by) / (np.sqrt(ax * ax + ay * ay) * np.sqrt(bx * bx + by * by))
+        if mutant != 'no_clip':
+            v = np.where(v < -1.0, -1.0, np.where(v > 1.0, 1.0, v))      # a NaN stays a NaN
+        turn = wave_sum(np.arccos(v))
+    if mutant != 'radians':
+        turn = turn * (180.0 / 3.14159265358979323846)
+    return turn, (0 if drop0 else 1 if drop1 else 2)
+
+
+def winding_passes(w, angle, mutant=None):
+    """The criterion on a winding: strict, so a NaN and w == angle fail."""
+    return bool(w <= angle) if mutant == 'non_strict' else bool(w < angle)
