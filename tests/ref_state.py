@@ -16,14 +16,18 @@ float32 by the reference exactly as by the kernels and carry no error.
 
   ``k_state``     ``e = 1 - d`` (1), ``(e_x e_y)`` and ``(.) e_z`` (2),
                   ``v w`` (1), seven adds of the 8-term chain (7): 11.
-  ``k_state_dd``  ``e = 1 - d`` (1), ``a b`` of blend4 (1), ``v (a b)`` (1),
-                  three adds of blend4 (3), then the 1-D lerp: ``1 - d'`` (1),
-                  ``lo (1 - d')`` (1), ``hi d'`` (1), one add (1): 10.
+  ``k_state_dd``  ``e = 1 - d`` (1), the weight ``a b`` (1), the first product
+                  ``v (a b)`` (1), three FMAs of the blend (3), then the 1-D
+                  lerp: ``1 - d'`` (1), one product (1), one FMA (1): 9.
 
-Contraction to FMA (the file is compiled with fp contract fast) only removes
-roundings.  16 leaves headroom for a miscount, not for tuning.  The inputs must
-keep every product clear of underflow: |v| >= 2**-20 and every weight 0 or
->= 2**-72 (``check_inputs``).
+``k_state_dd`` states every fused operation in its source (``blend<>`` and
+``lerp<>`` of ttl_state.hip), and ``emulate_k_state_dd`` takes the same order
+with ``fma32``, a float32 FMA of one rounding: the kernel's finite rows equal
+the emulation bit for bit.  ``k_state`` is compiled with fp contract fast and
+its fused operations are the compiler's; ``emulate_k_state`` rounds every
+product and sum, which contraction can only improve on.  16 leaves headroom
+for a miscount, not for tuning.  The inputs must keep every product clear of
+underflow: |v| >= 2**-20 and every weight 0 or >= 2**-72 (``check_inputs``).
 """
 import itertools
 
@@ -166,8 +170,25 @@ def excess(got, value, S):
 
 
 # --------------------------------------------------------------------------- #
-# float32 emulations of the kernels' operation order (no FMA: every product and
-# sum rounds, which the contracted kernels can only improve on)
+# float32 emulations of the kernels' operation order
+def fma32(a, b, c):
+    """float32 ``a * b + c`` with one rounding.  The float64 product of two
+    float32 values is exact; the float64 sum is rounded to odd (TwoSum gives its
+    error: where there is one and the sum's last bit is even, the neighbour on
+    the error's side is taken), and a value rounded to odd at 53 bits rounds to
+    24 bits as the exact one does.  A plain float64 sum can double-round."""
+    p = np.asarray(a, dtype=f32).astype(f64) * np.asarray(b, dtype=f32).astype(f64)
+    c = np.asarray(c, dtype=f32).astype(f64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        s = p + c
+        t = s - p
+        err = (p - (s - t)) + (c - t)
+        even = (s.view(np.int64) & 1) == 0
+        towards = np.where(err > 0, np.inf, -np.inf)
+        s = np.where((err != 0) & even & np.isfinite(s), np.nextafter(s, towards), s)
+        return s.astype(f32)
+
+
 def _clamp_int(fl, lo, hi):
     """(int) fminf(fmaxf(fl, lo), hi): NaN comes out as lo."""
     with np.errstate(invalid='ignore'):
@@ -217,15 +238,22 @@ def emulate_k_state_dd(vol, heads, radius, shift):
     def rec(i, j, k):
         return vol[sl[0][i], sl[1][j], sl[2][k]]
 
-    def blend4(v00, v01, v10, v11, a0, a1, b0, b1):
-        r = (v00 * (a0 * b0).astype(f32)[:, None]).astype(f32)
-        for v, w in ((v01, a0 * b1), (v10, a1 * b0), (v11, a1 * b1)):
-            r = (r + (v * w.astype(f32)[:, None]).astype(f32)).astype(f32)
+    def blend(outer, v00, v01, v10, v11, a0, a1, b0, b1):
+        # a centre slice (f, f+1) starts from v00 w00, an outer one (f-1, f+2) from v01 w01
+        terms = [(v, (a * b).astype(f32)[:, None]) for v, a, b in
+                 ((v00, a0, b0), (v01, a0, b1), (v10, a1, b0), (v11, a1, b1))]
+        if outer:
+            terms[0], terms[1] = terms[1], terms[0]
+        r = (terms[0][0] * terms[0][1]).astype(f32)
+        for v, w in terms[1:]:
+            r = fma32(v, w, r)
         return r
 
-    def lerp4(lo, hi, dd):
-        return ((lo * (f32(1) - dd).astype(f32)[:, None]).astype(f32) +
-                (hi * dd[:, None]).astype(f32)).astype(f32)
+    def lerp(minus, lo, hi, dd):
+        e, dd = (f32(1) - dd).astype(f32)[:, None], dd[:, None]
+        if minus:
+            return fma32(hi, dd, (lo * e).astype(f32))
+        return fma32(lo, e, (hi * dd).astype(f32))
 
     out = np.zeros((N, 7, C), dtype=f32)
     with np.errstate(invalid='ignore'):
@@ -236,14 +264,14 @@ def emulate_k_state_dd(vol, heads, radius, shift):
                 ijk = [0, 0, 0]
                 ijk[a], ijk[b], ijk[c] = s, jb, jc
                 return rec(*ijk)
-            B = [blend4(at(s, 1, 1), at(s, 1, 2), at(s, 2, 1), at(s, 2, 2),
-                        ec[:, b], dc[:, b], ec[:, c], dc[:, c]) for s in range(4)]
+            B = [blend(s in (0, 3), at(s, 1, 1), at(s, 1, 2), at(s, 2, 1), at(s, 2, 2),
+                       ec[:, b], dc[:, b], ec[:, c], dc[:, c]) for s in range(4)]
             if a == 0:
-                out[:, 0] = lerp4(B[1], B[2], dc[:, 0])
+                out[:, 0] = lerp(False, B[1], B[2], dc[:, 0])
             up = (fl[:, 1 + a, a] > fc[:, a])[:, None]
             dn = (fl[:, 4 + a, a] < fc[:, a])[:, None]
-            out[:, 1 + a] = lerp4(np.where(up, B[2], B[1]), np.where(up, B[3], B[2]),
-                                  d[:, 1 + a, a])
-            out[:, 4 + a] = lerp4(np.where(dn, B[0], B[1]), np.where(dn, B[1], B[2]),
-                                  d[:, 4 + a, a])
+            out[:, 1 + a] = lerp(False, np.where(up, B[2], B[1]), np.where(up, B[3], B[2]),
+                                 d[:, 1 + a, a])
+            out[:, 4 + a] = lerp(True, np.where(dn, B[0], B[1]), np.where(dn, B[1], B[2]),
+                                 d[:, 4 + a, a])
     return out.reshape(N, 7 * C)

@@ -22,6 +22,9 @@ tests use, and that every mutation of the reference leaves it.
 """
 import ctypes as C
 import functools
+import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -43,6 +46,13 @@ STEP_C = [7, 33, 34, 35, 45]
 STEP_K = [1, 4, 13, 100]
 STEP_D, STEP_N, STEP_R = 14, 700, 0.75
 POISON = 0x7fc0abcd            # one fixed NaN bit pattern
+EMULATED_C = [4, 5, 8, 28, 33, 45, 64, 65, 129]    # kernel rows == emulate_k_state_dd, bit for bit
+EMULATED_EDGE = (34, 0.5)
+PINNED_MAX_C = 64               # wider records ran looping kernels of unstated order at the fixture's commit
+TRACE_K = 4                     # the K whose episodes the fixture holds
+CONFIGS = ['three_launch', 'one_launch', 'sorted_order', 'free_running']
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden',
+                      'state_rows_trace.json')
 
 
 # --------------------------------------------------------------------------- #
@@ -329,6 +339,41 @@ def _inside(rows, value, S, C_, what, quiet=False):
     return e.max()
 
 
+# --------------------------------------------------------------------------- #
+# GPU: the bits of the rows, against tests/golden/state_rows_trace.json
+# (golden/make_golden_state_rows.py records it with these same functions)
+def digest(*arrays):
+    """SHA-256 over the bytes of the arrays, the first 128 bits in hex."""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:32]
+
+
+def episode_digest(trace):
+    """One digest over the per-step digests of an episode."""
+    return digest(np.frombuffer(''.join(trace).encode(), np.uint8))
+
+
+def edge_name(C_, radius, shift):
+    return f'C={C_} r={radius} shift={shift}'
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def _equals_emulation(rows, C_, heads, radius, shift, what):
+    """The signal block of the finite rows equals emulate_k_state_dd bit for bit."""
+    n = 7 * C_
+    want = rs.emulate_k_state_dd(volume(C_), heads, radius, shift)
+    bad = np.argwhere(rows[:, :n].view(np.uint32) != want.view(np.uint32))
+    print(what, 'elements that are not the emulation\'s bits:', len(bad))
+    assert not len(bad), (what, 'first (row, column)', bad[:8].tolist())
+
+
 _SWEEP_OUT = {}
 
 
@@ -374,7 +419,23 @@ def _sweep_output(C_):
 @pytest.mark.gpu
 @pytest.mark.parametrize('C_', WIDTHS)
 def test_every_record_width(C_):
-    _SWEEP_OUT[C_] = _check_sweep(C_, _sweep_variants(C_))
+    """Inside the float64 bound (``_check_sweep``), and the bits: k_state's rows
+    and k_state_dd's of records up to 64 floats are the fixture's.  Wider records
+    ran looping kernels whose fused operations the compiler chose when the
+    fixture was recorded: those rows are held to the emulation of the stated
+    order instead, bit for bit, and whether the old digest was kept is printed."""
+    out = _SWEEP_OUT[C_] = _check_sweep(C_, _sweep_variants(C_))
+    want = golden()['sweep'][str(C_)]
+    assert digest(out[0]) == want['0'], 'k_state rows moved'
+    for kernel in (4, 3):
+        kept = digest(out[kernel]) == want[str(kernel)]
+        if C_ <= PINNED_MAX_C:
+            assert kept, f'TTL_STATE_KERNEL={kernel} rows moved'
+        else:
+            print(f'C={C_} TTL_STATE_KERNEL={kernel}: the fixture\'s digest was',
+                  'kept' if kept else 'not kept')
+    if C_ in EMULATED_C or C_ > PINNED_MAX_C:
+        _equals_emulation(out[4], C_, sweep_seeds(C_), SWEEP_R, 0.0, f'C={C_}')
 
 
 @pytest.mark.gpu
@@ -383,14 +444,14 @@ def test_all_k_state_dd_runs_are_bit_identical():
     store) and 3 (separate tail stores) are two instantiations of one source
     and must give the same bits at every width.
 
-    They did not before this test existed: ttl_state.hip leaves the
-    contraction of its blends to the compiler, which fused the fourth float
-    of a column differently in the separate-tail kernels (2-4 % of the
-    elements of every C in 4..64 a last bit away, at most 2.81 * 2**-24 * S,
-    inside the bound).  The separate-tail kernels now state the fused
-    operations the merged-tail kernels are compiled to (``blend<>`` /
-    ``lerp<>`` in ttl_state.hip); this test is what notices a compiler that
-    fuses the merged-tail kernels otherwise."""
+    They did not while ttl_state.hip left the contraction of its blends to
+    the compiler, which fused the fourth float of a column differently in
+    the separate-tail kernels (2-4 % of the elements of every C in 4..64 a
+    last bit away, at most 2.81 * 2**-24 * S, inside the bound).  The file is
+    now compiled without contraction and ``blend<>`` / ``lerp<>`` state every
+    fused operation: the order is stated, not found, and every instantiation
+    gives the same bits by construction (``test_every_record_width`` holds
+    them to ``ref_state.emulate_k_state_dd`` and to the fixture)."""
     differ = {}
     for C_ in WIDTHS:
         out = _sweep_output(C_)
@@ -441,6 +502,11 @@ def test_edge_coordinates_and_shift(C_, radius):
         value, S = _reset_reference(volume(C_), heads, radius, shift, SWEEP_K)
         assert np.isnan(value[:, 0]).sum() == 10 and np.isnan(value[-10:, 0]).all()
         _inside(rows, value, S, C_, f'C={C_} r={radius} shift={shift}')
+        # the bits of the finite rows (the NaN payloads of the last 10 are not pinned)
+        assert digest(rows[:-10]) == golden()['edge'][edge_name(C_, radius, shift)], shift
+        if (C_, radius) == EMULATED_EDGE:
+            _equals_emulation(rows[:-10], C_, heads[:-10], radius, shift,
+                              edge_name(C_, radius, shift))
         # the finite rows again in the other layout and in the library's sorted
         # processing order: the same bits
         rig = _Rig(volume(C_), _lib.SH_LINEAR, len(heads) - 10, SWEEP_K)
@@ -480,13 +546,18 @@ def _step_env(monkeypatch, C_, K, config):
 
 
 _STEP_OUT = {}
+_STEP_TRACE = {}
 
 
-def _check_step(env, sh, K, idx, by_streamline, L, what, keep=None, done=None):
+def _check_step(env, sh, K, idx, by_streamline, L, what, keep=None, done=None, trace=None):
     """Rows of the streamlines ``idx`` after the step that left them with L
     points, against the reference computed from the handle's own history.
     ``done``: the step's flags of these rows; the handle's own ``lengths`` of
-    the rows that stopped must say L as well."""
+    the rows that stopped must say L as well.  ``trace`` receives the digest of
+    the step: the streamlines and their rows, in the order of the streamlines."""
+    if trace is not None:
+        by_id = np.argsort(idx, kind='stable')
+        trace.append(digest(np.asarray(idx, np.int64)[by_id], by_streamline[by_id]))
     hist = env.streamlines[idx]
     if done is not None:
         stopped = done.cpu().numpy()[:len(idx)].astype(bool)
@@ -503,8 +574,10 @@ def _episode(monkeypatch, C_, K, config):
     env, sh = _step_env(monkeypatch, C_, K, config)
     what = f'C={C_} K={K} {config}'
     keep = _STEP_OUT.setdefault((C_, K), []) if config == 'one_launch' else None
+    trace = _STEP_TRACE[C_, K, config] = []
     state = env.reset(0, STEP_N)
-    worst = _check_step(env, sh, K, np.arange(STEP_N), state.cpu().numpy(), 1, what + ' reset')
+    worst = _check_step(env, sh, K, np.arange(STEP_N), state.cpu().numpy(), 1, what + ' reset',
+                        trace=trace)
     steps, fills = 0, []
     if config in ('three_launch', 'one_launch'):
         env.profile_begin(64, classes=('prefix', 'state'))      # counts the launches
@@ -516,7 +589,7 @@ def _episode(monkeypatch, C_, K, config):
             full, _, done, info = env.step_device(env.scripted_actions(state, steps, 9, 0.2))
             dest = info['row_dest'].cpu().numpy()
             worst = max(worst, _check_step(env, sh, K, idx, full.cpu().numpy()[dest], env.length,
-                                           f'{what} step {steps}', keep, done))
+                                           f'{what} step {steps}', keep, done, trace))
             state, _ = env.harvest()
             steps += 1
             fills.append((env._library_order()[0], env._n_active))
@@ -549,7 +622,7 @@ def _episode(monkeypatch, C_, K, config):
             n_cont = int(env._host_counts_np[0])
             dest = env._row_dest_view(n).cpu().numpy()
             worst = max(worst, _check_step(env, sh, K, idx, buf[:n].cpu().numpy()[dest], L,
-                                           f'{what} step {steps - 1}', None, done))
+                                           f'{what} step {steps - 1}', None, done, trace))
             nxt = np.empty(n_cont, dtype=idx.dtype)
             nxt[dest[dest < n_cont]] = idx[dest < n_cont]       # survivors first, stable
             idx, n = nxt, n_cont
@@ -561,16 +634,43 @@ def _episode(monkeypatch, C_, K, config):
     return steps
 
 
+def episode_trace(C_, K, config):
+    """The per-step digests of one episode (run now unless it already was)."""
+    if (C_, K, config) not in _STEP_TRACE:
+        with pytest.MonkeyPatch.context() as mp:
+            _episode(mp, C_, K, config)
+    return _STEP_TRACE[C_, K, config]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('config', ['three_launch', 'one_launch', 'sorted_order', 'free_running'])
+@pytest.mark.parametrize('config', CONFIGS)
 @pytest.mark.parametrize('C_', STEP_C)
 def test_every_launch_path_over_an_episode(C_, config):
     """To exhaustion (max_nb_steps = 16: every K sees steps with fewer segments
-    than K, and K = 1, 4, 13 steps with more)."""
+    than K, and K = 1, 4, 13 steps with more).
+
+    The bits, at K = 4: the three-launch and the sorted-order episodes are the
+    fixture's.  The one-launch and the free-running tails take the same
+    scripted actions (a function of the direction block, the step and the
+    streamline), so every step of theirs gives the three-launch episode's rows;
+    they are also the fixture's wherever the fixture's commit had them agree
+    with its three-launch episode."""
     for K in STEP_K:
         with pytest.MonkeyPatch.context() as mp:
             steps = _episode(mp, C_, K, config)
         assert steps >= 6, steps
+    trace = _STEP_TRACE[C_, TRACE_K, config]
+    want = golden()['episodes'][str(C_)]
+    if config in ('three_launch', 'sorted_order'):
+        assert episode_digest(trace) == want[config]
+        return
+    canonical = episode_trace(C_, TRACE_K, 'three_launch')
+    assert trace == canonical, [i for i, (a, b) in enumerate(zip(trace, canonical)) if a != b]
+    agreed = golden()['episodes_equal_three_launch'][str(C_)][config]
+    kept = episode_digest(trace) == want[config]
+    print(f'C={C_} {config}: the fixture\'s commit', 'agreed' if agreed else 'did not agree',
+          'with its three-launch episode; its digest was', 'kept' if kept else 'not kept')
+    assert kept or not agreed
 
 
 # --------------------------------------------------------------------------- #

@@ -7,40 +7,88 @@
 
 #include "ttl_internal.h"
 
-// The state rows are compared with the reference at 1e-5, not bit for bit (the
-// stopping decisions and positions, which are, live in ttl_hip.hip): let the
-// blends contract to FMAs here although the library is built with
-// -ffp-contract=off.  The direction block is plain float32 differences of
-// stored positions and is not affected.
-#pragma clang fp contract(fast)
+// The library is built with -ffp-contract=off and this file keeps it: the
+// deduplicated gather states every fused operation of a state row in its
+// source (blend<> and lerp<> below), so its bits are no compiler's choice.
+// k_state alone lets the compiler contract, inside its own body.
 
 namespace {
 constexpr int BLOCK = TTL_BLOCK;
 
+// The lane groups of the gather kernels: LPS lanes serve one row (lane = one
+// float4 column of the padded voxel record, so a group reads each 16B-aligned
+// record as one contiguous coef_pitch*4-byte segment), 64 / LPS rows per wave.
+// LPS need not be a power of two: with 12 float4 columns per record a wave
+// serves 5 streamlines on 60 lanes instead of 4 on 48; the lanes left over idle.
+template <int LPS>
+struct LaneGroups {
+    static constexpr int PER_WAVE = 64 / LPS;
+    static constexpr int PER_BLOCK = (BLOCK / 64) * PER_WAVE;
+    // one lane group per row
+    static dim3 grid(int n_rows) { return dim3((n_rows + PER_BLOCK - 1) / PER_BLOCK); }
+
+    int grp, sub;   // this thread's group within its wave, its lane within the group
+    __device__ LaneGroups() {
+        const int lane = threadIdx.x & 63;
+        grp = lane / LPS;
+        sub = lane - grp * LPS;
+    }
+    __device__ bool idle() const { return grp >= PER_WAVE; }
+    // the row this thread serves in block `blk` of PER_BLOCK rows
+    __device__ int slot(int blk) const {
+        return blk * PER_BLOCK + (threadIdx.x >> 6) * PER_WAVE + grp;
+    }
+};
+
+__device__ __forceinline__ const float *history_of(const EnvParams &P, int g) {
+    return P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
+}
+
+// Segment j of the direction block of a history h of n_seg segments (n_seg + 1
+// points): the previous directions, most recent first, zero padded (np.diff of
+// the stored float32 positions).  One whole segment (3 floats from 6 contiguous
+// ones) per lane.
+struct seg3 {
+    float x, y, z;
+};
+__device__ __forceinline__ seg3 dir_segment(const float *__restrict__ h, int n_seg, int j) {
+    seg3 v{0.0f, 0.0f, 0.0f};
+    if (j < n_seg) {
+        const float *a = h + (n_seg - 1 - j) * 3;   // points n_seg-1-j and n_seg-j
+        const float ax = a[0], ay = a[1], az = a[2];
+        const float bx = a[3], by = a[4], bz = a[5];
+        v = seg3{bx - ax, by - ay, bz - az};
+    }
+    return v;
+}
+__device__ __forceinline__ void put_segment(float *__restrict__ od, int j, seg3 v) {
+    od[3 * j + 0] = v.x;
+    od[3 * j + 1] = v.y;
+    od[3 * j + 2] = v.z;
+}
+
 // ---------------------------------------------------------------------------
-// k_state: LPS lanes per streamline, lane = one float4 column of the padded
-// voxel record, so a group reads each 16B-aligned voxel record as one
-// contiguous coef_pitch*4-byte segment.  7 points x 8 corners accumulate in
-// registers (no cross-lane traffic); the previous-direction block is written
-// by the same lanes.
+// k_state: the 56-fetch fallback (radius >= 1 voxel or outside (0, 1), volumes
+// of 4 GiB and more).  7 points x 8 corners accumulate in registers (no
+// cross-lane traffic); the previous-direction block is written by the same
+// lanes.  Its rows are compared with the reference within a bound, not bit for
+// bit, and its sums are left to contract to FMAs as the compiler sees fit: the
+// bits of its rows are still the compiler's.
 // ---------------------------------------------------------------------------
 template <int LPS>
 __global__ __launch_bounds__(BLOCK) void k_state(
     EnvParams P, const int *__restrict__ idx, const int *__restrict__ row_dest,
     const int *__restrict__ proc, int n_rows, int L, float *__restrict__ out,
     long long pitch) {
-    constexpr int GPW = 64 / LPS;              // streamlines per wave
-    constexpr int ROWS = (BLOCK / 64) * GPW;
-    const int lane = threadIdx.x & 63;
-    const int grp = lane / LPS;
-    const int slot = blockIdx.x * ROWS + (threadIdx.x >> 6) * GPW + grp;
-    const int sub = lane - grp * LPS;
-    if (grp >= GPW || slot >= n_rows) return;
+#pragma clang fp contract(fast)
+    const LaneGroups<LPS> lanes;
+    const int slot = lanes.slot(blockIdx.x), sub = lanes.sub;
+    if (lanes.idle() || slot >= n_rows) return;
     const int row = proc ? proc[slot] : slot;
     if (row < 0) return;        // a hole of an uncompacted processing order
     const int g = idx ? idx[row] : row;
     const int r = row_dest ? row_dest[row] : row;
-    const float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
+    const float *h = history_of(P, g);
     const float px = h[(L - 1) * 3 + 0];
     const float py = h[(L - 1) * 3 + 1];
     const float pz = h[(L - 1) * 3 + 2];
@@ -110,27 +158,9 @@ __global__ __launch_bounds__(BLOCK) void k_state(
             if (c + 3 < C) o[3] = a.w;
         }
     }
-    // previous directions, most recent first, zero padded (np.diff of the
-    // stored float32 positions)
-    // previous directions, most recent first, zero padded (np.diff of the
-    // stored float32 positions): one whole segment (3 floats from 6
-    // contiguous ones) per lane and iteration
     float *od = orow + 7 * C;
     const int n_seg = L - 1;
-    for (int j = sub; j < P.n_dirs; j += LPS) {
-        float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-        if (j < n_seg) {
-            const float *a = h + (L - 2 - j) * 3;   // points L-2-j and L-1-j
-            const float ax = a[0], ay = a[1], az = a[2];
-            const float bx = a[3], by = a[4], bz = a[5];
-            vx = bx - ax;
-            vy = by - ay;
-            vz = bz - az;
-        }
-        od[3 * j + 0] = vx;
-        od[3 * j + 1] = vy;
-        od[3 * j + 2] = vz;
-    }
+    for (int j = sub; j < P.n_dirs; j += LPS) put_segment(od, j, dir_segment(h, n_seg, j));
 }
 
 // ---------------------------------------------------------------------------
@@ -158,59 +188,63 @@ __device__ __forceinline__ f4 ld4(const char *base, unsigned byte_off) {
 __device__ __forceinline__ f4 scale4(f4 a, float w) {
     return f4{a.x * w, a.y * w, a.z * w, a.w * w};
 }
-__device__ __forceinline__ f4 axpy4(f4 acc, f4 a, float w) {  // acc + a*w
-    return f4{acc.x + a.x * w, acc.y + a.y * w, acc.z + a.z * w, acc.w + a.w * w};
-}
-// bilinear blend of 4 records with weights (a0,a1) x (b0,b1)
-__device__ __forceinline__ f4 blend4(f4 v00, f4 v01, f4 v10, f4 v11, float a0,
-                                     float a1, float b0, float b1) {
-    f4 r = scale4(v00, a0 * b0);
-    r = axpy4(r, v01, a0 * b1);
-    r = axpy4(r, v10, a1 * b0);
-    r = axpy4(r, v11, a1 * b1);
-    return r;
-}
-__device__ __forceinline__ f4 lerp4(f4 lo, f4 hi, float d) {
-    return axpy4(scale4(lo, 1.0f - d), hi, d);
-}
-__device__ __forceinline__ f4 sel4(bool c, f4 a, f4 b) {
-    return f4{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w};
-}
-// PINNED: the blends with every fused operation stated.  The file leaves
-// contraction to the compiler, which is free to fuse `x * a + y * b` either way
-// and does so differently per instantiation: the separate-tail kernels
-// (TTL_STATE_KERNEL=3) came out a last bit away from the merged-tail ones in
-// the fourth float of a column.  These state the order the merged-tail kernels
-// are compiled to (found by matching their rows bit for bit at C = 8, 28, 45
-// and 64; tests/test_state_gather_reference.py holds the two kernels to equal
-// bits, so a compiler that fuses the merged-tail kernels otherwise is noticed):
-//   blend of a centre slice (f, f+1):  fma(v11, fma(v10, fma(v01, v00 w00)))
-//   blend of an outer slice (f-1, f+2): fma(v11, fma(v10, fma(v00, v01 w01)))
-//   centre and plus lerp: fma(lo, 1 - d, hi d);  minus lerp: fma(hi, d, lo (1 - d))
-// The merged-tail kernels themselves (PINNED = false) keep the plain source.
-// To re-derive the order after a compiler update (the test above then fails):
-// benchmarks/micro/fusion_order_probe.py prints, per stencil point, the order
-// that reproduces the merged-tail kernels' rows; restate it here.
-// k_state_dd<4, 4, false, false> is also what the default knob launches for
-// C = 1..3 (the merged tail needs 4 coefficients): before it was pinned only the
-// fourth float of a column differed, which those records never store.
 __device__ __forceinline__ f4 fma4(f4 a, float w, f4 c) {   // a*w + c, one rounding
     return f4{__builtin_fmaf(a.x, w, c.x), __builtin_fmaf(a.y, w, c.y),
               __builtin_fmaf(a.z, w, c.z), __builtin_fmaf(a.w, w, c.w)};
 }
-template <bool PINNED, bool OUTER>
+__device__ __forceinline__ f4 sel4(bool c, f4 a, f4 b) {
+    return f4{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w};
+}
+// The arithmetic of a deduplicated state row, every fused operation stated.
+// This order is the definition: every instantiation of k_state_dd and of the
+// fused tails gives these bits, and tests/ref_state.emulate_k_state_dd takes
+// the same order on the CPU.
+//   bilinear blend of 4 records with weights (a0, a1) x (b0, b1), each weight
+//   one rounded product:
+//     a centre slice (f, f+1):   fma(v11, fma(v10, fma(v01, v00 w00)))
+//     an outer slice (f-1, f+2): fma(v11, fma(v10, fma(v00, v01 w01)))
+//   1-D lerp of two blended slices:
+//     centre and plus point: fma(lo, 1 - d, hi d);  minus point: fma(hi, d, lo (1 - d))
+template <bool OUTER>
 __device__ __forceinline__ f4 blend(f4 v00, f4 v01, f4 v10, f4 v11, float a0, float a1,
                                     float b0, float b1) {
-    if (!PINNED) return blend4(v00, v01, v10, v11, a0, a1, b0, b1);
     f4 r = OUTER ? fma4(v00, a0 * b0, scale4(v01, a0 * b1))
                  : fma4(v01, a0 * b1, scale4(v00, a0 * b0));
     r = fma4(v10, a1 * b0, r);
     return fma4(v11, a1 * b1, r);
 }
-template <bool PINNED, bool MINUS>
+template <bool MINUS>
 __device__ __forceinline__ f4 lerp(f4 lo, f4 hi, float d) {
-    if (!PINNED) return lerp4(lo, hi, d);
     return MINUS ? fma4(hi, d, scale4(lo, 1.0f - d)) : fma4(lo, 1.0f - d, scale4(hi, d));
+}
+// One axis of the stencil.  lo / hi: the centre cell's records in slices f and
+// f+1 of this axis, each as the 2 x 2 footprint of the other two axes in the
+// order 00, 01, 10, 11; q: the byte offsets of that footprint within a slice,
+// below / above: those of slices f-1 and f+2; (a0, a1) x (b0, b1): the other
+// two axes' weights; dn / up: does the minus point sit in the previous cell,
+// the plus point in the next one; d, d_plus, d_minus: the three points'
+// fractions along this axis.  An outer slice is fetched (and reduced to one
+// blended record at once) only where a shifted point really reaches it.
+struct AxisPoints {
+    f4 centre, plus, minus;     // the centre point is the same on every axis: the x call's is used
+};
+__device__ __forceinline__ AxisPoints stencil_axis(
+    const char *vol, const f4 (&lo)[4], const f4 (&hi)[4], const unsigned (&q)[4], unsigned below,
+    unsigned above, float a0, float a1, float b0, float b1, bool dn, bool up, float d,
+    float d_plus, float d_minus) {
+    const f4 zero{0.f, 0.f, 0.f, 0.f};
+    f4 s0 = zero, s3 = zero;
+    if (dn)
+        s0 = blend<true>(ld4(vol, below + q[0]), ld4(vol, below + q[1]), ld4(vol, below + q[2]),
+                         ld4(vol, below + q[3]), a0, a1, b0, b1);
+    if (up)
+        s3 = blend<true>(ld4(vol, above + q[0]), ld4(vol, above + q[1]), ld4(vol, above + q[2]),
+                         ld4(vol, above + q[3]), a0, a1, b0, b1);
+    const f4 s1 = blend<false>(lo[0], lo[1], lo[2], lo[3], a0, a1, b0, b1);
+    const f4 s2 = blend<false>(hi[0], hi[1], hi[2], hi[3], a0, a1, b0, b1);
+    return AxisPoints{lerp<false>(s1, s2, d),
+                      lerp<false>(sel4(up, s2, s1), sel4(up, s3, s2), d_plus),
+                      lerp<true>(sel4(dn, s0, s1), sel4(dn, s1, s2), d_minus)};
 }
 __device__ __forceinline__ int clipi(int v, int n) { return min(max(v, 0), n - 1); }
 // store the float4 column c..c+3 of one point's C coefficients (the last
@@ -307,23 +341,13 @@ __device__ __forceinline__ void put4(int flavour, float *o, f4 a, int c, int C) 
 // float4 column of the 7 stencil points + this lane's share of the direction
 // block.  (px, py, pz) = newest point, h = the streamline's history, orow = the
 // output row.  Shared by k_state_dd and the fused small-batch kernel.
-template <int LPS, bool LOOP, bool MERGE_TAIL, bool PINNED = false>
+template <int LPS, bool LOOP, bool MERGE_TAIL>
 __device__ __forceinline__ void state_row_dd(const EnvParams &P, float px, float py,
                                              float pz, const float *__restrict__ h, int L,
                                              int sub, float *__restrict__ orow) {
-    // this lane's first direction segment (np.diff of the stored float32
-    // positions): a scattered sector of the history, i.e. the longest latency
-    // of the wave -- fetched now, used after the gather
-    const int n_seg = L - 1;
-    float dvx = 0.0f, dvy = 0.0f, dvz = 0.0f;
-    if (sub < P.n_dirs && sub < n_seg) {
-        const float *a = h + (L - 2 - sub) * 3;   // points L-2-sub and L-1-sub
-        const float ax = a[0], ay = a[1], az = a[2];
-        const float bx = a[3], by = a[4], bz = a[5];
-        dvx = bx - ax;
-        dvy = by - ay;
-        dvz = bz - az;
-    }
+    // this lane's first direction segment: a scattered sector of the history,
+    // i.e. the longest latency of the wave -- fetched now, used after the gather
+    const seg3 first_dir = sub < P.n_dirs ? dir_segment(h, L - 1, sub) : seg3{0.0f, 0.0f, 0.0f};
     const int C = P.n_coef;
     const int C4 = P.coef_pitch >> 2;
     const int X = P.sh_dim[0], Y = P.sh_dim[1], Z = P.sh_dim[2];
@@ -368,95 +392,40 @@ __device__ __forceinline__ void state_row_dd(const EnvParams &P, float px, float
                    y2 = vox_y(P, clipi(iy + 1, Y)) * rec, y3 = vox_y(P, clipi(iy + 2, Y)) * rec;
     const unsigned z0 = vox_z(P, clipi(iz - 1, Z)) * rec, z1 = vox_z(P, clipi(iz, Z)) * rec,
                    z2 = vox_z(P, clipi(iz + 1, Z)) * rec, z3 = vox_z(P, clipi(iz + 2, Z)) * rec;
-#define TTL_VOX(xo, yo, zo) ((xo) + (yo) + (zo))
     // one float4 column per lane when the record fits the lane group (LOOP =
     // false, the usual case: nothing is hoisted and kept live across columns)
     for (int c4 = sub; c4 < C4; c4 += LPS) {
         const unsigned cb = (unsigned)c4 * 16u;
-        // centre cell
-        const f4 v000 = ld4(vol, TTL_VOX(x1, y1, z1) + cb), v001 = ld4(vol, TTL_VOX(x1, y1, z2) + cb);
-        const f4 v010 = ld4(vol, TTL_VOX(x1, y2, z1) + cb), v011 = ld4(vol, TTL_VOX(x1, y2, z2) + cb);
-        const f4 v100 = ld4(vol, TTL_VOX(x2, y1, z1) + cb), v101 = ld4(vol, TTL_VOX(x2, y1, z2) + cb);
-        const f4 v110 = ld4(vol, TTL_VOX(x2, y2, z1) + cb), v111 = ld4(vol, TTL_VOX(x2, y2, z2) + cb);
-        const f4 zero{0.f, 0.f, 0.f, 0.f};
         const int c = c4 * 4;
-        // outer slices are fetched (and reduced to one blended record at once)
-        // only where a shifted point really reaches them
-        // --- x axis: slices blended over (y, z) ---
-        {
-            f4 b0 = zero, b3 = zero;
-            if (xdn)
-                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x0, y1, z1) + cb), ld4(vol, TTL_VOX(x0, y1, z2) + cb),
-                            ld4(vol, TTL_VOX(x0, y2, z1) + cb), ld4(vol, TTL_VOX(x0, y2, z2) + cb),
-                            ey, dy, ez, dz);
-            if (xup)
-                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x3, y1, z1) + cb), ld4(vol, TTL_VOX(x3, y1, z2) + cb),
-                            ld4(vol, TTL_VOX(x3, y2, z1) + cb), ld4(vol, TTL_VOX(x3, y2, z2) + cb),
-                            ey, dy, ez, dz);
-            const f4 b1 = blend<PINNED, false>(v000, v001, v010, v011, ey, dy, ez, dz);
-            const f4 b2 = blend<PINNED, false>(v100, v101, v110, v111, ey, dy, ez, dz);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 0 * C + c, lerp<PINNED, false>(b1, b2, dx), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 1 * C + c, lerp<PINNED, false>(sel4(xup, b2, b1), sel4(xup, b3, b2), dxp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 4 * C + c, lerp<PINNED, true>(sel4(xdn, b0, b1), sel4(xdn, b1, b2), dxm), c, C);
-        }
-        // --- y axis: slices blended over (x, z) ---
-        {
-            f4 b0 = zero, b3 = zero;
-            if (ydn)
-                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y0, z1) + cb), ld4(vol, TTL_VOX(x1, y0, z2) + cb),
-                            ld4(vol, TTL_VOX(x2, y0, z1) + cb), ld4(vol, TTL_VOX(x2, y0, z2) + cb),
-                            ex, dx, ez, dz);
-            if (yup)
-                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y3, z1) + cb), ld4(vol, TTL_VOX(x1, y3, z2) + cb),
-                            ld4(vol, TTL_VOX(x2, y3, z1) + cb), ld4(vol, TTL_VOX(x2, y3, z2) + cb),
-                            ex, dx, ez, dz);
-            const f4 b1 = blend<PINNED, false>(v000, v001, v100, v101, ex, dx, ez, dz);
-            const f4 b2 = blend<PINNED, false>(v010, v011, v110, v111, ex, dx, ez, dz);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 2 * C + c, lerp<PINNED, false>(sel4(yup, b2, b1), sel4(yup, b3, b2), dyp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 5 * C + c, lerp<PINNED, true>(sel4(ydn, b0, b1), sel4(ydn, b1, b2), dym), c, C);
-        }
-        // --- z axis: slices blended over (x, y) ---
-        {
-            f4 b0 = zero, b3 = zero;
-            if (zdn)
-                b0 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y1, z0) + cb), ld4(vol, TTL_VOX(x1, y2, z0) + cb),
-                            ld4(vol, TTL_VOX(x2, y1, z0) + cb), ld4(vol, TTL_VOX(x2, y2, z0) + cb),
-                            ex, dx, ey, dy);
-            if (zup)
-                b3 = blend<PINNED, true>(ld4(vol, TTL_VOX(x1, y1, z3) + cb), ld4(vol, TTL_VOX(x1, y2, z3) + cb),
-                            ld4(vol, TTL_VOX(x2, y1, z3) + cb), ld4(vol, TTL_VOX(x2, y2, z3) + cb),
-                            ex, dx, ey, dy);
-            const f4 b1 = blend<PINNED, false>(v000, v010, v100, v110, ex, dx, ey, dy);
-            const f4 b2 = blend<PINNED, false>(v001, v011, v101, v111, ex, dx, ey, dy);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 3 * C + c, lerp<PINNED, false>(sel4(zup, b2, b1), sel4(zup, b3, b2), dzp), c, C);
-            put4<MERGE_TAIL>(P.store_flavour, orow + 6 * C + c, lerp<PINNED, true>(sel4(zdn, b0, b1), sel4(zdn, b1, b2), dzm), c, C);
-        }
+        // this column's byte offsets of the centre cell's 2 x 2 footprint within
+        // a slice of each axis, and the centre cell's 8 records v[x][y][z]
+        const unsigned qx[4] = {y1 + z1 + cb, y1 + z2 + cb, y2 + z1 + cb, y2 + z2 + cb};
+        const unsigned qy[4] = {x1 + z1 + cb, x1 + z2 + cb, x2 + z1 + cb, x2 + z2 + cb};
+        const unsigned qz[4] = {x1 + y1 + cb, x1 + y2 + cb, x2 + y1 + cb, x2 + y2 + cb};
+        const f4 v000 = ld4(vol, x1 + qx[0]), v001 = ld4(vol, x1 + qx[1]);
+        const f4 v010 = ld4(vol, x1 + qx[2]), v011 = ld4(vol, x1 + qx[3]);
+        const f4 v100 = ld4(vol, x2 + qx[0]), v101 = ld4(vol, x2 + qx[1]);
+        const f4 v110 = ld4(vol, x2 + qx[2]), v111 = ld4(vol, x2 + qx[3]);
+        // x: slices blended over (y, z); y: over (x, z); z: over (x, y)
+        const AxisPoints ax = stencil_axis(vol, {v000, v001, v010, v011}, {v100, v101, v110, v111},
+                                           qx, x0, x3, ey, dy, ez, dz, xdn, xup, dx, dxp, dxm);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 0 * C + c, ax.centre, c, C);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 1 * C + c, ax.plus, c, C);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 4 * C + c, ax.minus, c, C);
+        const AxisPoints ay = stencil_axis(vol, {v000, v001, v100, v101}, {v010, v011, v110, v111},
+                                           qy, y0, y3, ex, dx, ez, dz, ydn, yup, dy, dyp, dym);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 2 * C + c, ay.plus, c, C);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 5 * C + c, ay.minus, c, C);
+        const AxisPoints az = stencil_axis(vol, {v000, v010, v100, v110}, {v001, v011, v101, v111},
+                                           qz, z0, z3, ex, dx, ey, dy, zdn, zup, dz, dzp, dzm);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 3 * C + c, az.plus, c, C);
+        put4<MERGE_TAIL>(P.store_flavour, orow + 6 * C + c, az.minus, c, C);
         if (!LOOP) break;
     }
-#undef TTL_VOX
-    // previous directions, most recent first, zero padded (np.diff of the
-    // stored float32 positions): one whole segment (3 floats from 6
-    // contiguous ones) per lane and iteration
     float *od = orow + 7 * C;
-    if (sub < P.n_dirs) {
-        od[3 * sub + 0] = dvx;
-        od[3 * sub + 1] = dvy;
-        od[3 * sub + 2] = dvz;
-    }
-    for (int j = sub + LPS; j < P.n_dirs; j += LPS) {   // K > lane group size
-        float vx = 0.0f, vy = 0.0f, vz = 0.0f;
-        if (j < n_seg) {
-            const float *a = h + (L - 2 - j) * 3;   // points L-2-j and L-1-j
-            const float ax = a[0], ay = a[1], az = a[2];
-            const float bx = a[3], by = a[4], bz = a[5];
-            vx = bx - ax;
-            vy = by - ay;
-            vz = bz - az;
-        }
-        od[3 * j + 0] = vx;
-        od[3 * j + 1] = vy;
-        od[3 * j + 2] = vz;
-    }
+    if (sub < P.n_dirs) put_segment(od, sub, first_dir);
+    for (int j = sub + LPS; j < P.n_dirs; j += LPS)     // K > lane group size
+        put_segment(od, j, dir_segment(h, L - 1, j));
 }
 
 // A rider workgroup of the gather launch (see TailRiders): `wg` counts from the
@@ -475,6 +444,63 @@ __device__ __forceinline__ void tail_rider(const EnvParams &P, const TailRiders 
                  R.order, R.n_pts, R.idx_next);
 }
 
+// Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one;
+// speed only, never correctness): give every XCD one contiguous range of the
+// spatially sorted processing order, so that a voxel is fetched into ONE XCD's
+// L2 instead of all eight.  Bijective for any grid size
+// (cdna_hip_programming.md, T1).
+__device__ __forceinline__ int xcd_block(const EnvParams &P, int blk, int nwg) {
+    const int q = nwg >> 3, rr = nwg & 7, xcd = blk & 7;
+    if (P.xcd_rot == 0)
+        return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (blk >> 3);
+    // XCD x takes range (x + rot) & 7 of the order; a range has as many
+    // workgroups as its XCD receives (q or q + 1), so the map stays bijective
+    // for any grid size
+    const int mine = (xcd + P.xcd_rot) & 7;
+    int start = 0;
+    for (int r = 0; r < mine; ++r) start += q + ((((r - P.xcd_rot) & 7) < rr) ? 1 : 0);
+    return start + (blk >> 3);
+}
+
+// What a slot of k_state_dd gathers: streamline g with history h, newest point
+// (px, py, pz), output row r.
+struct SlotRow {
+    int g, r;
+    float px, py, pz;
+    const float *h;
+};
+// false: a hole of an uncompacted processing order, nothing to gather
+__device__ __forceinline__ bool resolve_slot(const EnvParams &P, const int *__restrict__ idx,
+                                             const int *__restrict__ row_dest,
+                                             const int *__restrict__ proc, int slot, int L,
+                                             SlotRow &s) {
+    if (proc && idx && P.slot_rec) {
+        // a step in processing order: k_proc_scatter (or k_tail) resolved row,
+        // idx[row], row_dest[row] and the new point into the slot's record
+        const float4 hp = *reinterpret_cast<const float4 *>(P.slot_head + 4 * (size_t)slot);
+        s = SlotRow{__float_as_int(hp.w), P.slot_dest[slot], hp.x, hp.y, hp.z, nullptr};
+        if (s.r < 0) return false;
+        s.h = history_of(P, s.g);
+        return true;
+    }
+    const int row = proc ? proc[slot] : slot;
+    if (row < 0) return false;
+    s.g = idx ? idx[row] : row;
+    s.r = row_dest ? row_dest[row] : row;
+    s.h = history_of(P, s.g);
+    if (idx) {      // a step: k_advance left the new point in row order
+        const float4 hp = *reinterpret_cast<const float4 *>(P.head + 4 * (size_t)row);
+        s.px = hp.x;
+        s.py = hp.y;
+        s.pz = hp.z;
+    } else {        // reset: the seed
+        s.px = s.h[(L - 1) * 3 + 0];
+        s.py = s.h[(L - 1) * 3 + 1];
+        s.pz = s.h[(L - 1) * 3 + 2];
+    }
+    return true;
+}
+
 template <int LPS, int MINW, bool LOOP, bool MERGE_TAIL>
 __global__ __launch_bounds__(BLOCK, MINW) void k_state_dd(
     EnvParams P, const int *__restrict__ idx, const int *__restrict__ row_dest,
@@ -486,76 +512,17 @@ __global__ __launch_bounds__(BLOCK, MINW) void k_state_dd(
         tail_rider(P, riders, (int)blockIdx.x - n_vblocks);
         return;
     }
-    // LPS lanes per streamline, 64 / LPS streamlines per wave (LPS need not be
-    // a power of two: with 12 float4 columns per record a wave serves 5
-    // streamlines on 60 lanes instead of 4 on 48)
-    constexpr int GPW = 64 / LPS;
-    constexpr int ROWS = (BLOCK / 64) * GPW;
-    const int lane = threadIdx.x & 63;
-    const int grp = lane / LPS;
-    const int sub = lane - grp * LPS;
-    if (grp >= GPW) return;
-    // n_vblocks == gridDim.x: one workgroup per block of ROWS slots.  A launch
-    // with fewer workgroups (TTL_GATHER_PERSIST_ROWS: one resident round) walks
-    // the blocks with a stride of gridDim.x.
+    const LaneGroups<LPS> lanes;
+    if (lanes.idle()) return;
+    // n_vblocks == gridDim.x: one workgroup per block of slots.  A launch with
+    // fewer workgroups (TTL_GATHER_PERSIST_ROWS: one resident round) walks the
+    // blocks with a stride of gridDim.x.
     for (int vb = blockIdx.x; vb < n_vblocks; vb += gridDim.x) {
-        int blk = vb;
-        if (proc && P.xcd_remap) {
-            // workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8
-            // share one; speed only, never correctness): give every XCD one
-            // contiguous range of the spatially sorted processing order, so that
-            // a voxel is fetched into ONE XCD's L2 instead of all eight.
-            // Bijective for any grid size (cdna_hip_programming.md, T1).
-            const int nwg = n_vblocks, q = nwg >> 3, rr = nwg & 7, xcd = blk & 7;
-            if (P.xcd_rot == 0) {
-                blk = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (blk >> 3);
-            } else {
-                // XCD x takes range (x + rot) & 7 of the order; a range has as many
-                // workgroups as its XCD receives (q or q + 1), so the map stays
-                // bijective for any grid size
-                const int mine = (xcd + P.xcd_rot) & 7;
-                int start = 0;
-                for (int r = 0; r < mine; ++r)
-                    start += q + ((((r - P.xcd_rot) & 7) < rr) ? 1 : 0);
-                blk = start + (blk >> 3);
-            }
-        }
-        const int slot = blk * ROWS + (threadIdx.x >> 6) * GPW + grp;
-        if (slot >= n_rows) continue;
-        int row, g, r;
-        float px, py, pz;
-        const bool slot_records = proc && idx && P.slot_rec;   // a step in processing order
-        if (slot_records) {     // k_proc_scatter resolved row, idx[row], row_dest[row]
-            const float4 hp = *reinterpret_cast<const float4 *>(P.slot_head + 4 * (size_t)slot);
-            px = hp.x;
-            py = hp.y;
-            pz = hp.z;
-            g = __float_as_int(hp.w);
-            r = P.slot_dest[slot];
-            row = 0;
-            if (r < 0) continue;    // a hole of the uncompacted order (k_tail): nothing to gather
-        } else {
-            row = proc ? proc[slot] : slot;
-            if (row < 0) continue;  // a hole of an uncompacted processing order
-            g = idx ? idx[row] : row;
-            r = row_dest ? row_dest[row] : row;
-        }
-        const float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
-        if (slot_records) {
-        } else if (idx) {      // a step: k_advance left the new point in row order
-            const float4 hp = *reinterpret_cast<const float4 *>(P.head + 4 * (size_t)row);
-            px = hp.x;
-            py = hp.y;
-            pz = hp.z;
-        } else {        // reset: the seed
-            px = h[(L - 1) * 3 + 0];
-            py = h[(L - 1) * 3 + 1];
-            pz = h[(L - 1) * 3 + 2];
-        }
-        // the separate-tail kernels of one-column-per-lane records state their fused
-        // operations (see blend<>): the same bits as the merged-tail kernels
-        state_row_dd<LPS, LOOP, MERGE_TAIL, !MERGE_TAIL && !LOOP>(
-            P, px, py, pz, h, L, sub, out + (size_t)r * (size_t)pitch);
+        const int slot = lanes.slot(proc && P.xcd_remap ? xcd_block(P, vb, n_vblocks) : vb);
+        SlotRow s;
+        if (slot >= n_rows || !resolve_slot(P, idx, row_dest, proc, slot, L, s)) continue;
+        state_row_dd<LPS, LOOP, MERGE_TAIL>(P, s.px, s.py, s.pz, s.h, L, lanes.sub,
+                                            out + (size_t)s.r * (size_t)pitch);
     }
 }
 
@@ -576,8 +543,6 @@ __device__ __forceinline__ void prefix_state_body(
     const EnvParams &P, const int *__restrict__ idx, int *__restrict__ idx_next, int n_active,
     int n_blocks, int order, int n_pts, float *__restrict__ out, long long pitch,
     int *__restrict__ host_word, int seq, int cur) {
-    constexpr int GPW = 64 / LPS;
-    constexpr int ROWS = (BLOCK / 64) * GPW;
     // exclusive prefix over the <= TTL_FUSE_MAX_BLOCKS per-block survivor counts
     // of k_advance: one wave, four counts per lane
     __shared__ int s_before[TTL_FUSE_MAX_BLOCKS + 1];
@@ -616,10 +581,9 @@ __device__ __forceinline__ void prefix_state_body(
         }
         step_publish_counts(P, total, n_active, host_word, seq);
     }
-    const int grp = lane / LPS;
-    const int row = blockIdx.x * ROWS + (threadIdx.x >> 6) * GPW + grp;
-    const int sub = lane - grp * LPS;
-    if (grp >= GPW || row >= n_active) return;
+    const LaneGroups<LPS> lanes;
+    const int row = lanes.slot(blockIdx.x), sub = lanes.sub;
+    if (lanes.idle() || row >= n_active) return;
     const float4 hp = *reinterpret_cast<const float4 *>(P.head + 4 * (size_t)row);
     const int g = __float_as_int(hp.w);
     const bool stop = P.stop[row] != 0;
@@ -627,8 +591,7 @@ __device__ __forceinline__ void prefix_state_body(
     // every lane of the group needs the state row, one of them writes the row map
     const int dest = step_row_dest(order, row, stop, pos, total);
     if (sub == 0) step_map_row(P, row, g, stop, pos, total, order, n_pts, idx_next);
-    const float *h = P.hist + (size_t)g * (size_t)(P.max_nb_steps + 1) * 3;
-    state_row_dd<LPS, false, MERGE_TAIL>(P, hp.x, hp.y, hp.z, h, n_pts, sub,
+    state_row_dd<LPS, false, MERGE_TAIL>(P, hp.x, hp.y, hp.z, history_of(P, g), n_pts, sub,
                                          out + (size_t)dest * (size_t)pitch);
 }
 
@@ -679,11 +642,12 @@ void for_lanes_per_streamline(const EnvParams &P, F &&f) {
     else f(std::integral_constant<int, MAX_LPS>{});
 }
 
-// one lane group per row
-template <int LPS>
-dim3 gather_grid(int n_rows) {
-    constexpr int rows_per_block = (BLOCK / 64) * (64 / LPS);
-    return dim3((n_rows + rows_per_block - 1) / rows_per_block);
+// The register-deduplicated gather needs the shifted points to stay within one
+// cell of the centre -- 0 < radius < 1 voxel -- and 32-bit byte offsets into
+// the volume.
+bool dedupe_applies(const EnvParams &P) {
+    const size_t vol_bytes = ttl_detail_sh_records(P) * P.coef_pitch * sizeof(float);
+    return P.radius > 0.0f && P.radius < 1.0f && vol_bytes < (1ull << 32);
 }
 
 }  // namespace
@@ -693,9 +657,7 @@ dim3 gather_grid(int n_rows) {
 // at most 64 advance blocks.
 bool ttl_detail_can_fuse_tail(const EnvParams &P, int n_active) {
     const int C4 = P.coef_pitch >> 2;
-    const size_t vol_bytes = ttl_detail_sh_records(P) * P.coef_pitch * sizeof(float);
-    return n_active <= P.fuse_max_rows && P.radius > 0.0f && P.radius < 1.0f &&
-           vol_bytes < (1ull << 32) && C4 <= 16 && P.n_coef >= 4;
+    return n_active <= P.fuse_max_rows && dedupe_applies(P) && C4 <= 16 && P.n_coef >= 4;
 }
 
 int ttl_detail_launch_fused_tail(const EnvParams &P, const int *idx, int *idx_next,
@@ -704,7 +666,7 @@ int ttl_detail_launch_fused_tail(const EnvParams &P, const int *idx, int *idx_ne
     const int n_blocks = (n_active + BLOCK - 1) / BLOCK;
     for_lanes_per_streamline<16>(P, [&](auto lps) {
         constexpr int LPS = decltype(lps)::value;
-        hipLaunchKernelGGL((k_prefix_state<LPS, true>), gather_grid<LPS>(n_active), dim3(BLOCK), 0,
+        hipLaunchKernelGGL((k_prefix_state<LPS, true>), LaneGroups<LPS>::grid(n_active), dim3(BLOCK), 0,
                            s, P, idx, idx_next, n_active, n_blocks, order, n_pts, out,
                            (long long)pitch, host_word, seq);
     });
@@ -718,19 +680,17 @@ int ttl_detail_launch_fused_tail_fr(const EnvParams &P, int *idx_a, int *idx_b, 
     const int n_blocks = (n_cap + BLOCK - 1) / BLOCK;
     for_lanes_per_streamline<16>(P, [&](auto lps) {
         constexpr int LPS = decltype(lps)::value;
-        hipLaunchKernelGGL((k_prefix_state_fr<LPS, true>), gather_grid<LPS>(n_cap), dim3(BLOCK), 0,
+        hipLaunchKernelGGL((k_prefix_state_fr<LPS, true>), LaneGroups<LPS>::grid(n_cap), dim3(BLOCK), 0,
                            s, P, idx_a, idx_b, n_blocks, out, (long long)pitch, host_word);
     });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }
 
-// the register-deduplicated kernel (the one that reads the per-slot records of a
-// processing order) needs the shifted points to stay within one cell of the
-// centre -- 0 < radius < 1 voxel -- and 32-bit byte offsets into the volume
+// whether the launch below takes k_state_dd (the kernel that reads the per-slot
+// records of a processing order)
 bool ttl_detail_state_dedupes(const EnvParams &P, int state_kernel) {
-    const size_t vol_bytes = ttl_detail_sh_records(P) * P.coef_pitch * sizeof(float);
-    return state_kernel != 0 && P.radius > 0.0f && P.radius < 1.0f && vol_bytes < (1ull << 32);
+    return state_kernel != 0 && dedupe_applies(P);
 }
 
 int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx,
@@ -746,7 +706,7 @@ int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx
         return fail(TTL_ERR_INVALID, "state gather: this launch cannot carry riders");
     for_lanes_per_streamline<32>(P, [&](auto lps) {
         constexpr int LPS = decltype(lps)::value;
-        const int n_vb = (int)gather_grid<LPS>(n_rows).x;
+        const int n_vb = (int)LaneGroups<LPS>::grid(n_rows).x;
         // TTL_GATHER_PERSIST_ROWS (experiment, off by default): batches of at
         // most that many rows that need more than one resident round (4
         // workgroups per CU x 256 CUs) run as ONE round of workgroups that
@@ -757,13 +717,17 @@ int ttl_detail_launch_state(const EnvParams &P, int state_kernel, const int *idx
         if (!dedupe)
             hipLaunchKernelGGL((k_state<LPS>), grid, dim3(BLOCK), 0, s, P, idx, row_dest, proc,
                                n_rows, L, out, (long long)pitch);
-        else if (LPS < 32 && P.n_coef >= 4 && state_kernel != 3)
-            hipLaunchKernelGGL((k_state_dd<LPS, 4, (LPS >= 32), (LPS < 32)>), grid, dim3(BLOCK), lds,
-                               s, P, idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb, R);
-        else
-            hipLaunchKernelGGL((k_state_dd<LPS, (LPS >= 32 ? 2 : 4), (LPS >= 32), false>), grid,
-                               dim3(BLOCK), lds, s, P, idx, row_dest, proc, n_rows, L, out,
-                               (long long)pitch, n_vb, R);
+        else if constexpr (LPS < 32) {      // one column per lane
+            if (P.n_coef >= 4 && state_kernel != 3)
+                hipLaunchKernelGGL((k_state_dd<LPS, 4, false, true>), grid, dim3(BLOCK), lds, s, P,
+                                   idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb, R);
+            else
+                hipLaunchKernelGGL((k_state_dd<LPS, 4, false, false>), grid, dim3(BLOCK), lds, s, P,
+                                   idx, row_dest, proc, n_rows, L, out, (long long)pitch, n_vb, R);
+        } else {                            // wider records: the lanes loop over the columns
+            hipLaunchKernelGGL((k_state_dd<LPS, 2, true, false>), grid, dim3(BLOCK), lds, s, P, idx,
+                               row_dest, proc, n_rows, L, out, (long long)pitch, n_vb, R);
+        }
     });
     HIP_TRY(hipGetLastError());
     return TTL_OK;
