@@ -128,6 +128,7 @@ def pairs(kind=0):
     rows?  Five volume allocations x five ring allocations (fresh allocations
     each), the gather's time for every pair."""
     from tracktolearn_amd import _lib
+    from tracktolearn_amd.environments.state_pool import StatePool
     os.environ['TTL_VOLUME_CANDIDATES'] = '1'
     subject = bench.make_subject()
     env = make_bench_env(subject)
@@ -151,7 +152,7 @@ def pairs(kind=0):
         row = []
         env._sh_packed = vol
         for ring in rings + [None]:
-            env._state_ring, env._state_ring_pos = ring, 0
+            env._state_pool = StatePool(ring or (), rotate=env.STATE_RING_ROTATE)
             rehandle(env)
             row.append(round(timed(env, rounds=2), 4))
         print(json.dumps(dict(volume=vi, ptr=hex(vol.data_ptr()), gather_ms_by_ring=row[:-1],

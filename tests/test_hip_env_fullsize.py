@@ -247,14 +247,16 @@ def test_volume_placement_tuning_changes_no_result_and_draws_nothing(monkeypatch
     assert np.array_equal(env_t.rng.get_state()[1], env_1.rng.get_state()[1])
     # ... and the device-resident loop writes its state rows into a ring of
     # four buffers in an allocation chosen the same way
-    if env_t._state_ring is None:           # the allocator's blocks won: install a ring
+    if not len(env_t._state_pool):          # the allocator's blocks won: install a ring
         from tracktolearn_amd import _lib
+        from tracktolearn_amd.environments.state_pool import StatePool
         mems = [_lib.DeviceVolume(0, N * env_t._state_pitch * 4) for _ in range(4)]
-        env_t._state_ring_memory = mems
-        env_t._state_ring = [torch.as_tensor(m, device='cuda:0').view(torch.float32)
-                             .view(N, env_t._state_pitch)[:, :env_t._state_width] for m in mems]
-    assert len(env_t._state_ring) == 4
-    spans = [(m.ptr, m.ptr + m.nbytes) for m in env_t._state_ring_memory]
+        env_t._state_pool = StatePool(
+            [torch.as_tensor(m, device='cuda:0').view(torch.float32)
+             .view(N, env_t._state_pitch)[:, :env_t._state_width] for m in mems], mems,
+            rotate=env_t.STATE_RING_ROTATE)
+    assert len(env_t._state_pool) == 4
+    spans = [(m.ptr, m.ptr + m.nbytes) for m in env_t._state_pool.memory]
 
     def in_ring(t):
         t = getattr(t, '_rows', t)          # step() hands out lazily gathered rows

@@ -260,6 +260,30 @@ def test_in_kernel_draw_equals_the_pointer_path():
     assert rc == _lib.ERR_INVALID
 
 
+@pytest.mark.gpu
+def test_keyed_noise_counts_from_the_batchs_one_id_base():
+    """``reset(start, end)`` on a shard whose seeds begin at ``noise_id_offset``:
+    streamline g of the batch draws as seed ``streamline_id_base() + g`` of the
+    run -- the one id base, which the fODF policy keys on as well."""
+    import torch
+    n_seeds, K, start, offset = 12, 4, 5, 1000
+    env, _ = _keyed_env(n_seeds, K, export=True, id_offset=offset)
+    state = env.reset(start, n_seeds)
+    n = n_seeds - start
+    assert env.streamline_id_base() == offset + start
+    L = env.length
+    env.step_device(_policy(K)(state))
+    got = env.noise_out.cpu().numpy()
+    want = SIGMA * _gpu_normals(SEED, env.streamline_id_base() + np.arange(n), L)
+    print(f'max |exported - sigma * library normals| = {np.abs(got - want).max():.3e}')
+    assert got.shape == (n, 3) and np.array_equal(got, want)
+    env.harvest()
+    # nreset counts from the offset alone
+    env.nreset(3)
+    assert env.streamline_id_base() == offset
+    torch.cuda.synchronize()
+
+
 def _track(env, policy, start, end):
     state = env.reset(start, end)
     while state.shape[0] > 0:

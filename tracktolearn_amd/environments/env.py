@@ -13,12 +13,15 @@ library raises.
 """
 import ctypes as C
 import os
+import time
 
 import numpy as np
 import torch
 
 from tracktolearn_amd import _lib
 from tracktolearn_amd.datasets.utils import convert_length_mm2vox
+from tracktolearn_amd.environments.placement import pick_ring, placement_plan
+from tracktolearn_amd.environments.state_pool import StatePool
 from tracktolearn_amd.environments.stopping_criteria import (
     curvature_dot_threshold, mask_spline_coefficients)
 
@@ -51,19 +54,70 @@ class BaseEnv(object):
     #: direction arithmetic forced to float64 by subclasses that add float64
     #: noise to the action (NoisyTrackingEnvironment)
     _force_f64_directions = False
+    #: sigma of the action noise where a subclass draws some
+    #: (NoisyTrackingEnvironment sets it before this constructor runs); the
+    #: placement search silences it for its probe steps
+    noise = None
+
+    #: placements tried at the first large reset: this many allocations of the
+    #: packed SH volume x this many allocations of the state ring
+    #: (TTL_VOLUME_CANDIDATES, TTL_STATE_RING_CANDIDATES; 1 and 0 = keep the first
+    #: allocation of the volume and fresh state tensors per step)
+    VOLUME_CANDIDATES = 3
+    STATE_RING_CANDIDATES = 16
+    #: device memory the search may hold on top of the env's own (the extra
+    #: copies of the volume + the candidate state buffers): at most this much and
+    #: at most PLACEMENT_SEARCH_FREE_FRACTION of what hipMemGetInfo reports free
+    PLACEMENT_SEARCH_BYTES = 8 << 30
+    PLACEMENT_SEARCH_FREE_FRACTION = 0.10
+    #: the search stops after its first three pairs when their gather times agree
+    #: within this fraction (a box without placement classes: nothing to find)
+    PLACEMENT_EARLY_EXIT = 0.02
+    #: volumes below this sit in the caches wherever they are
+    VOLUME_TUNE_MIN_BYTES = 64 << 20
+    #: batches below this are bound by launches, not by the gather
+    VOLUME_TUNE_MIN_ROWS = 65536
+    #: state rows of large batches live in memory whose placement was measured: a
+    #: pool of this many buffers (TTL_STATE_RING=0: a fresh ``torch.empty`` per
+    #: step).  A buffer is handed out again only when no tensor refers to it any
+    #: more, so every state tensor stays intact for as long as the caller holds
+    #: it, exactly like a fresh allocation; when the caller holds them all, the
+    #: step falls back to a fresh allocation (state_pool.py)
+    STATE_RING = 4
+    #: TTL_STATE_RING_ROTATE=1 (and a torch without the storage use count): the
+    #: round-2 behaviour, a plain ring -- a tensor is overwritten STATE_RING steps
+    #: after it was handed out, referenced or not, and ``step()`` allocates
+    STATE_RING_ROTATE = os.environ.get('TTL_STATE_RING_ROTATE', '0') == '1' or \
+        not hasattr(torch._C, '_storage_Use_Count')
 
     def __init__(self, subject_data, split_id: str, env_dto: dict):
+        # idle values of everything the classes read later (a constructor that
+        # raises half way leaves an object ``__del__`` can still take)
+        self._handle = None
+        self._destroy_handle()          # no capacity, no graphs (_free_runs, _free_bufs)
+        self._state_pool = StatePool()
+        self._sh_tuned = self._placement_search = None
+        self._loaded_subject = self._zero_reward_np = self.initial_points = None
+        self.dataset_file = self.subject_id = None
+        # episode bookkeeping of the concrete envs (nothing tracked yet)
+        self._pending = None
+        self._n_active = 0
+        self._n_total = 0
+        self._cur = 0
+        self.length = 0
+        self.not_stopping = None
+        self._init_len = self.flags_forward = self.seed_index = None
+
+        self.split = split_id
         if type(subject_data) is str:
             # env.py:85-94: a dataset file; subjects are visited in a fresh
             # random order every pass (DataLoader(batch_size=1, shuffle=True))
             from tracktolearn_amd.datasets.SubjectDataset import SubjectDataset
             self.dataset_file = subject_data
-            self.split = split_id
             self.dataset = SubjectDataset(self.dataset_file, self.split)
             self._subject_order = iter(())
         else:
             self.subject_data = subject_data
-            self.split = split_id
 
         self.normalize_obs = False
         self.obs_rms = None
@@ -113,22 +167,13 @@ class BaseEnv(object):
                 "oracle_bonus=0 / --oracle_bonus 0 to train without the oracle")
 
         self._lib = _lib.load()
-        self._handle = None
-        self._n_max = 0
-        # episode bookkeeping of the concrete envs (nothing tracked yet)
-        self._pending = None
-        self._n_active = 0
-        self._n_total = 0
-        self._cur = 0
-        self.length = 0
-        self.not_stopping = None
         self.load_subject()
 
     # ------------------------------------------------------------------ #
     def load_subject(self):
         """Per-subject setup, TrackToLearn/environments/env.py:143-281."""
-        if hasattr(self, 'dataset_file'):
-            if hasattr(self, 'subject_id') and len(self.dataset) == 1:
+        if self.dataset_file is not None:
+            if self.subject_id is not None and len(self.dataset) == 1:
                 return
             try:
                 index = next(self._subject_order)
@@ -145,11 +190,8 @@ class BaseEnv(object):
             # min/max length is recomputed when the caller changed them in
             # between (ttl_track.py:146 rescales the step to the subject's
             # voxel size, env.py:196-212 then re-derives the step in voxels)
-            if getattr(self, '_loaded_subject', None) is self.subject_data:
-                if self._tracking_params_key() != self._loaded_params_key:
-                    self._derive_tracking_params()
-                    self._destroy_handle()
-                    self._n_max = 0
+            if self._loaded_subject is self.subject_data:
+                self._rederive_tracking_params()
                 return
             (input_volume, tracking_mask, seeding_mask, peaks,
              reference) = self.subject_data
@@ -232,11 +274,8 @@ class BaseEnv(object):
             # reference anatomy (oracle_reward.py:82-90: vox -> rasmm -> the
             # reference's vox, corner origin; the shift drops out of the
             # segment vectors the oracle consumes)
-            ref_affine = None
-            if isinstance(reference, dict):
-                ref_affine = reference.get('affine')
-            elif hasattr(reference, 'affine'):
-                ref_affine = reference.affine
+            ref_affine = reference.get('affine') if isinstance(reference, dict) \
+                else getattr(reference, 'affine', None)
             lin = np.eye(3)
             if ref_affine is not None:
                 lin = np.linalg.inv(np.asarray(ref_affine, np.float64))[:3, :3] @ \
@@ -248,7 +287,6 @@ class BaseEnv(object):
                 [float(v) for v in lin.T.astype(np.float32).ravel()]
 
         self._destroy_handle()
-        self._n_max = 0
         self._state_width = 7 * C_ + 3 * int(self.n_dirs)
         #: floats between consecutive state rows (= the width: contiguous rows)
         self._state_pitch = self._state_width
@@ -257,25 +295,6 @@ class BaseEnv(object):
     def _tracking_params_key(self):
         return (float(self.step_size_mm), float(self.min_length_mm),
                 float(self.max_length_mm))
-
-    #: placements tried at the first large reset: this many allocations of the
-    #: packed SH volume x this many allocations of the state ring
-    #: (TTL_VOLUME_CANDIDATES, TTL_STATE_RING_CANDIDATES; 1 and 0 = keep the first
-    #: allocation of the volume and fresh state tensors per step)
-    VOLUME_CANDIDATES = 3
-    STATE_RING_CANDIDATES = 16
-    #: device memory the search may hold on top of the env's own (the extra
-    #: copies of the volume + the candidate state buffers): at most this much and
-    #: at most PLACEMENT_SEARCH_FREE_FRACTION of what hipMemGetInfo reports free
-    PLACEMENT_SEARCH_BYTES = 8 << 30
-    PLACEMENT_SEARCH_FREE_FRACTION = 0.10
-    #: the search stops after its first three pairs when their gather times agree
-    #: within this fraction (a box without placement classes: nothing to find)
-    PLACEMENT_EARLY_EXIT = 0.02
-    #: volumes below this sit in the caches wherever they are
-    VOLUME_TUNE_MIN_BYTES = 64 << 20
-    #: batches below this are bound by launches, not by the gather
-    VOLUME_TUNE_MIN_ROWS = 65536
 
     def _place_sh_volume(self, dims, n_coef, pitch, n_rec, mask_data):
         """Pack the SH volume into device memory of its own (``ttl_volume_alloc``,
@@ -289,7 +308,7 @@ class BaseEnv(object):
             self._sh_layout, self._stream()), 'ttl_pack_sh_volume')
         self._sh_tuned = None          # the matrix of candidate times once tuned
         self._placement_search = None  # what the search did (see _tune_placement)
-        self._state_ring, self._state_ring_pos, self._state_ring_memory = None, 0, None
+        self._state_pool = StatePool()
         return vol, mem
 
     def _tune_placement(self, seeds):
@@ -304,150 +323,142 @@ class BaseEnv(object):
         requests at a longer memory-side latency; address, alignment,
         contiguity, which XCD reads what: none of it predicts the class --
         DESIGN.md 3.3).  So the host measures, once per subject, at the first
-        reset of at least VOLUME_TUNE_MIN_ROWS streamlines: the volume is copied
-        into VOLUME_CANDIDATES allocations, STATE_RING_CANDIDATES state buffers
-        (for the device-resident loop) are allocated one by one, every pair
-        (volume, buffer) runs four steps of the real loop on up to
-        262 144 of the given seeds with the scripted policy, and the pair with
-        the fastest gather wins (51 pairs, ~0.3 s; the same bytes at other
-        addresses: no result changes): its volume is kept, and the STATE_RING
-        buffers that were fastest with that volume form the ring.  The caching
-        allocator's own blocks (no ring: a fresh state tensor per step) are the
-        17th candidate for the rows when the probe runs at the batch's own size.
-
-        Bounded (round 3): the extra volume copies and the candidate buffers
-        together take at most PLACEMENT_SEARCH_BYTES and at most
-        PLACEMENT_SEARCH_FREE_FRACTION of the device memory that is free when
-        the search starts (fewer candidates otherwise, none when even
-        STATE_RING buffers do not fit); when the first three pairs agree within
-        PLACEMENT_EARLY_EXIT the box has no placement classes worth a search
-        and it stops there.  ``_placement_search`` records what was done
-        (seconds, bytes held, pairs timed, early exit)."""
-        import time
+        reset of at least VOLUME_TUNE_MIN_ROWS streamlines: the candidates the
+        memory budget allows (``placement_plan``) are allocated, every pair
+        (volume, buffer) is timed, and the pair with the fastest gather wins
+        (the same bytes at other addresses: no result changes).
+        ``_placement_search`` records what was done (seconds, bytes held, pairs
+        timed, early exit).  On any exit the env is left with a valid volume,
+        no handle, and the ``initial_points`` and ``noise`` it had."""
         t_search = time.perf_counter()
         kv = int(os.environ.get('TTL_VOLUME_CANDIDATES', self.VOLUME_CANDIDATES))
         kr = int(os.environ.get('TTL_STATE_RING_CANDIDATES', self.STATE_RING_CANDIDATES))
         ring_len = int(os.environ.get('TTL_STATE_RING', self.STATE_RING))
-        vol0, mem0 = self._sh_packed, self._sh_memory
-        nbytes = vol0.numel() * 4
+        nbytes = self._sh_packed.numel() * 4
         radius = float(np.float32(self.add_neighborhood_vox or 0.0))
         self._sh_tuned = []
         if kv < 2 or nbytes < self.VOLUME_TUNE_MIN_BYTES or not 0.0 < radius < 1.0 \
                 or self._use_oracle_stopping or self._use_oracle_reward:
             return
-        if ring_len < 2:
-            kr = 0
         n_ring = len(seeds)                     # the batch that triggered the tuning
-        n = min(n_ring, 262144)
         buf_bytes = n_ring * self._state_pitch * 4
         # memory budget of the search, from what the device reports free now
         try:
             free_bytes = int(torch.cuda.mem_get_info(self._device_index)[0])
         except Exception:           # pragma: no cover
             free_bytes = 0
-        budget = int(min(self.PLACEMENT_SEARCH_BYTES,
-                         self.PLACEMENT_SEARCH_FREE_FRACTION * free_bytes))
-        budget = int(os.environ.get('TTL_PLACEMENT_SEARCH_BYTES', budget))
-        kv = max(1, min(kv, 1 + budget // max(2 * nbytes, 1)))   # copies: half of it at most
-        left = budget - (kv - 1) * nbytes
-        if kr > 0:
-            kr = min(kr, left // max(buf_bytes, 1))
-            if kr < ring_len:
-                kr = 0
+        budget, kv, kr = placement_plan(
+            nbytes, buf_bytes, free_bytes, kv, kr, ring_len,
+            cap_bytes=self.PLACEMENT_SEARCH_BYTES,
+            free_fraction=self.PLACEMENT_SEARCH_FREE_FRACTION,
+            budget_override=os.environ.get('TTL_PLACEMENT_SEARCH_BYTES'))
         self._placement_search = dict(budget_bytes=budget, free_bytes_at_start=free_bytes,
                                       volume_candidates=kv, state_buffer_candidates=kr,
                                       pairs_timed=0, early_exit=False, seconds=0.0)
         if kv < 2 and kr == 0:
             return
-        keep = dict(initial_points=getattr(self, 'initial_points', None),
-                    noise=getattr(self, 'noise', None))
-        if keep['noise'] is not None:
+        initial_points, noise = self.initial_points, self.noise
+        if noise is not None:
             self.noise = 0.0           # the probe steps must not draw from the env's generator
-        vols, rings, candidates = [(vol0, mem0)], [], [(None, None)]
-        best = None
+        vols, rings, timed = [(self._sh_packed, self._sh_memory)], [], []
         try:
-            for c in range(1, kv):
-                try:
-                    mem = _lib.DeviceVolume(self._device_index, nbytes, False)
-                except _lib.TTLError:
-                    break               # no room for another copy
-                vol = torch.as_tensor(mem, device=self.device).view(torch.float32) \
-                    .view(vol0.shape)
-                vol.copy_(vol0)
-                vols.append((vol, mem))
-            pitch, width = self._state_pitch, self._state_width
-            for c in range(kr):     # state buffers, one allocation each
-                try:
-                    mem = _lib.DeviceVolume(self._device_index, buf_bytes, False)
-                except _lib.TTLError:
-                    break
-                flat = torch.as_tensor(mem, device=self.device).view(torch.float32)
-                rings.append(([flat.view(n_ring, pitch)[:, :width]], mem))
-            if len(rings) < ring_len:
-                rings = []
-            # the caching allocator's own blocks (fresh state tensors per step, as
-            # without a ring) compete too when the probe runs at the batch's own
-            # size: a step then gets the very blocks it will get later
-            candidates = rings + ([(None, None)] if n == n_ring or not rings else [])
+            vols, rings = self._allocate_candidates(kv, kr, n_ring, ring_len)
             self._placement_search['bytes_held'] = (len(vols) - 1) * nbytes + \
                 len(rings) * buf_bytes
-            timed, settled = [], False
-            for vi, (vol, mem) in enumerate(vols):
-                if settled:
-                    break
-                self._sh_packed, self._sh_memory = vol, mem
-                self._destroy_handle()
-                self._n_max = 0
-                row = []
-                for ri, (ring, rmem) in enumerate(candidates):
-                    # a candidate is a "ring" of one buffer that every step of the
-                    # probe must write, referenced or not
-                    self._state_ring_search = True
-                    self._state_ring, self._state_ring_pos = ring, 0
-                    state = self._start(seeds[:n])
-                    self.profile_begin(16, classes=('state',))
-                    for step in range(4):
-                        if not self._n_active:
-                            break
-                        self.step_device(self.scripted_actions(state, step, 1, 0.05))
-                        state, _ = self.harvest()
-                    total_ms, launches = self.profile_end()['state']
-                    ms = total_ms / max(launches, 1)
-                    row.append(round(ms, 5))
-                    if best is None or ms < best[0]:
-                        best = (ms, vi, ri)
-                    timed.append(ms)
-                    if len(timed) == 3 and min(timed) > 0 and \
-                            max(timed) - min(timed) <= self.PLACEMENT_EARLY_EXIT * min(timed) \
-                            and os.environ.get('TTL_PLACEMENT_EARLY_EXIT', '1') != '0':
-                        settled = True      # no classes on this box: nothing to find
-                        break
-                self._sh_tuned.append(row)
+            settled = self._time_pairs(vols, rings, seeds, timed)
             self._placement_search.update(pairs_timed=len(timed), early_exit=settled)
         finally:
-            self._state_ring_search = False
-            vi, ri = (best[1], best[2]) if best else (0, 0)
-            self._sh_packed, self._sh_memory = vols[vi]
-            self._state_ring, self._state_ring_memory = None, None
-            if best and candidates[ri][0] is not None:
-                # the ring: the ring_len buffers that were fastest with this volume
-                # (buffers the search never timed -- early exit -- rank last, in
-                # allocation order)
-                row = self._sh_tuned[vi]
-                order = sorted(range(len(rings)),
-                               key=lambda r: (row[r] if r < len(row) else float('inf'), r))
-                picked = [rings[r] for r in order[:ring_len]]
-                self._state_ring = [bufs[0] for bufs, _ in picked]
-                self._state_ring_memory = [m for _, m in picked]
-            self._state_ring_pos = 0
+            # min keeps the first of equal times: the pair timed first
+            self._install_placement(vols, rings, min(timed, default=None), ring_len)
+            self.initial_points = initial_points
+            if noise is not None:
+                self.noise = noise
+            self._placement_search['seconds'] = time.perf_counter() - t_search
+
+    def _allocate_candidates(self, kv, kr, n_ring, ring_len):
+        """``([(volume, owner)], [(buffer, owner)])``: the env's own volume and
+        ``kv - 1`` copies, ``kr`` state buffers of ``n_ring`` rows, one allocation
+        each -- fewer where the driver refuses, no buffer when fewer than a ring."""
+        vol0 = self._sh_packed
+        vols, rings = [(vol0, self._sh_memory)], []
+        for c in range(1, kv):
+            try:
+                mem = _lib.DeviceVolume(self._device_index, vol0.numel() * 4, False)
+            except _lib.TTLError:
+                break               # no room for another copy
+            vol = torch.as_tensor(mem, device=self.device).view(torch.float32) \
+                .view(vol0.shape)
+            vol.copy_(vol0)
+            vols.append((vol, mem))
+        for c in range(kr):
+            try:
+                mem = _lib.DeviceVolume(self._device_index, n_ring * self._state_pitch * 4, False)
+            except _lib.TTLError:
+                break
+            flat = torch.as_tensor(mem, device=self.device).view(torch.float32)
+            rings.append((flat.view(n_ring, self._state_pitch)[:, :self._state_width], mem))
+        return vols, rings if len(rings) >= ring_len else []
+
+    def _time_pairs(self, vols, rings, seeds, timed):
+        """Every pair (volume, buffer) runs four steps of the real loop on up to
+        262 144 of the given seeds with the scripted policy (51 pairs at the
+        defaults, ~0.3 s); ``timed`` receives ``(gather ms, volume, buffer)`` per
+        pair as it goes and ``_sh_tuned`` one row of times per volume.  The
+        caching allocator's own blocks (no pool: a fresh state tensor per step)
+        are the 17th candidate for the rows when the probe runs at the batch's
+        own size: a step then gets the very blocks it will get later.  Returns
+        whether it stopped early: the first three pairs agree within
+        PLACEMENT_EARLY_EXIT, a box without placement classes worth a search."""
+        n = min(len(seeds), 262144)
+        # a candidate is a "ring" of one buffer that every step of the probe must
+        # write, referenced or not
+        pools = [StatePool([buf], rotate=True) for buf, _ in rings]
+        if n == len(seeds) or not rings:
+            pools.append(StatePool())
+        for vi, (vol, mem) in enumerate(vols):
+            self._sh_packed, self._sh_memory = vol, mem
             self._destroy_handle()
-            self._n_max = 0
-            self.initial_points = keep['initial_points']
-            if keep['noise'] is not None:
-                self.noise = keep['noise']
-            del vols, rings, candidates          # the losers go back to the driver
-            if getattr(self, '_placement_search', None) is not None:
-                self._placement_search['seconds'] = time.perf_counter() - t_search
+            row = []
+            self._sh_tuned.append(row)
+            for ri, pool in enumerate(pools):
+                self._state_pool = pool
+                state = self._start(seeds[:n])
+                self.profile_begin(16, classes=('state',))
+                for step in range(4):
+                    if not self._n_active:
+                        break
+                    self.step_device(self.scripted_actions(state, step, 1, 0.05))
+                    state, _ = self.harvest()
+                total_ms, launches = self.profile_end()['state']
+                ms = total_ms / max(launches, 1)
+                row.append(round(ms, 5))
+                timed.append((ms, vi, ri))
+                if len(timed) == 3:
+                    lo, hi = min(timed)[0], max(timed)[0]
+                    if lo > 0 and hi - lo <= self.PLACEMENT_EARLY_EXIT * lo \
+                            and os.environ.get('TTL_PLACEMENT_EARLY_EXIT', '1') != '0':
+                        return True     # no classes on this box: nothing to find
+        return False
+
+    def _install_placement(self, vols, rings, best, ring_len):
+        """Keep the winner ``best = (ms, volume, buffer)`` (None: the first
+        volume, no pool): its volume and -- unless the allocator's own blocks
+        won -- the pool ``pick_ring`` chooses; the losers die with the lists."""
+        _, vi, ri = best if best else (0.0, 0, 0)
+        self._sh_packed, self._sh_memory = vols[vi]
+        self._state_pool = StatePool()
+        if best and ri < len(rings):
+            picked = [rings[r] for r in pick_ring(self._sh_tuned[vi], len(rings), ring_len)]
+            self._state_pool = StatePool([buf for buf, _ in picked], [m for _, m in picked],
+                                         rotate=self.STATE_RING_ROTATE)
+        self._destroy_handle()
+
+    def _rederive_tracking_params(self):
+        # the caller may have changed step size / lengths of the loaded subject:
+        # the handle was built on the old values
+        if self._tracking_params_key() != self._loaded_params_key:
+            self._derive_tracking_params()
+            self._destroy_handle()
 
     def _derive_tracking_params(self):
         """env.py:196-213: step size in voxels, step counts and the
@@ -479,24 +490,8 @@ class BaseEnv(object):
 
     def _new_state(self, n):
         """(n, state width) float32 rows on the device, `_state_pitch` apart."""
-        if self._state_pitch == self._state_width:
-            return torch.empty((n, self._state_width), dtype=torch.float32,
-                               device=self.device)
-        return torch.empty((n, self._state_pitch), dtype=torch.float32,
-                           device=self.device)[:, :self._state_width]
-
-    #: state rows of large batches live in memory whose placement was measured: a
-    #: pool of this many buffers (TTL_STATE_RING=0: a fresh ``torch.empty`` per
-    #: step).  A buffer is handed out again only when no tensor refers to it any
-    #: more (the use count of its storage), so every state tensor stays intact
-    #: for as long as the caller holds it, exactly like a fresh allocation; when
-    #: the caller holds them all, the step falls back to a fresh allocation.
-    STATE_RING = 4
-    #: TTL_STATE_RING_ROTATE=1 (and a torch without the storage use count): the
-    #: round-2 behaviour, a plain ring -- a tensor is overwritten STATE_RING steps
-    #: after it was handed out, referenced or not, and ``step()`` allocates
-    STATE_RING_ROTATE = os.environ.get('TTL_STATE_RING_ROTATE', '0') == '1' or \
-        not hasattr(torch._C, '_storage_Use_Count')
+        rows = torch.empty((n, self._state_pitch), dtype=torch.float32, device=self.device)
+        return rows if self._state_pitch == self._state_width else rows[:, :self._state_width]
 
     @property
     def state_ring_len(self):
@@ -507,39 +502,18 @@ class BaseEnv(object):
         ``reset`` / ``step_device`` / ``harvest`` is overwritten after
         ``state_ring_len - 1`` further state tensors were handed out: clone what
         must live longer."""
-        return len(self._state_ring) if getattr(self, '_state_ring', None) else 0
+        return len(self._state_pool)
 
     @property
     def state_ring_rotates(self):
-        return bool(self.state_ring_len) and (self.STATE_RING_ROTATE or
-                                              getattr(self, '_state_ring_search', False))
-
-    @staticmethod
-    def _storage_users(t):
-        # TensorImpls + Python storage objects alive on this storage (the probe's
-        # own temporary included, in the baseline as well)
-        return torch._C._storage_Use_Count(t.untyped_storage()._cdata)
+        return bool(len(self._state_pool)) and self._state_pool.rotate
 
     def _ring_state(self, n):
         """State rows for a reset / step of a large batch: a placed buffer that
         nothing refers to any more when there is one that fits, a fresh tensor
         otherwise."""
-        ring = self._state_ring
-        if ring is None or n > ring[0].shape[0]:
-            return self._new_state(n)
-        if self.STATE_RING_ROTATE or getattr(self, '_state_ring_search', False):
-            self._state_ring_pos = (self._state_ring_pos + 1) % len(ring)
-            return ring[self._state_ring_pos][:n]
-        if getattr(self, '_state_ring_idle_of', None) is not ring:
-            # first use of this pool: nothing has been handed out yet
-            self._state_ring_idle = [self._storage_users(b) for b in ring]
-            self._state_ring_idle_of = ring
-        for k in range(1, len(ring) + 1):
-            pos = (self._state_ring_pos + k) % len(ring)
-            if self._storage_users(ring[pos]) <= self._state_ring_idle[pos]:
-                self._state_ring_pos = pos
-                return ring[pos][:n]
-        return self._new_state(n)       # the caller still holds a tensor on every buffer
+        state = self._state_pool.rows(n)
+        return state if state is not None else self._new_state(n)
 
     def _stream(self):
         """Raw HIP stream torch currently launches on for this device (the
@@ -548,11 +522,12 @@ class BaseEnv(object):
 
     def _destroy_handle(self):
         # graphs captured over the handle's buffers die with it
-        self._free_runs = {}
-        self._free_bufs = {}
-        if getattr(self, '_handle', None):
+        self._free_runs = {}            # run_free: captured graphs by (n, key, record)
+        self._free_bufs = {}            # run_free_eager: buffers by batch size
+        if self._handle:
             self._lib.ttl_env_destroy(self._handle)
         self._handle = None
+        self._n_max = 0
 
     def __del__(self):
         try:
@@ -691,10 +666,7 @@ class BaseEnv(object):
         ``ttl_track_from_hdf5.py:134`` of the reference calls this name;
         ``ttl_track.py:146`` assigns ``step_size_mm`` and reloads instead."""
         self.step_size_mm = step_size_mm
-        if self._tracking_params_key() != self._loaded_params_key:
-            self._derive_tracking_params()
-            self._destroy_handle()
-            self._n_max = 0
+        self._rederive_tracking_params()
 
     def get_state_size(self):
         """env.py:451-463."""

@@ -29,6 +29,10 @@ from tracktolearn_amd.environments.tracking_env import TrackingEnvironment
 class NoisyTrackingEnvironment(TrackingEnvironment):
 
     _force_f64_directions = True
+    #: the backward pass of a batch draws with ``noise_seed ^ BACKWARD_SEED_XOR``
+    #: and the same ids: other numbers than the forward pass, as independent of
+    #: the batching
+    BACKWARD_SEED_XOR = 0x9E3779B97F4A7C15
 
     def __init__(self, dataset_file, split_id: str, env_dto: dict):
         self.noise = env_dto['noise']
@@ -61,9 +65,8 @@ class NoisyTrackingEnvironment(TrackingEnvironment):
         self.noise_out = None
         self._fa_coef = None
         #: keyed noise: streamline g of ``reset(start, end)`` is seed
-        #: ``noise_id_offset + start + g`` of the run
+        #: ``noise_id_offset + start + g`` of the run (``streamline_id_base``)
         self.noise_id_offset = int(env_dto.get('noise_id_offset', 0))
-        self._noise_id_base = 0
         self.max_action = 1.
         #: generator of the exploration noise; None = ``self.rng`` (the
         #: reference's single stream, noisy_tracking_env.py:73).  A sharded run
@@ -79,34 +82,20 @@ class NoisyTrackingEnvironment(TrackingEnvironment):
 
     def load_subject(self):
         super().load_subject()
-        if getattr(self, 'device_noise', False) == 'keyed':
-            if self.fa_map is not None and self._fa_coef is None:
-                if tuple(self.fa_map.shape) != tuple(self._mask_dim):
-                    raise ValueError(f'fa_map grid {tuple(self.fa_map.shape)} differs from '
-                                     f"the tracking mask's {tuple(self._mask_dim)}")
-                from scipy.ndimage import spline_filter
-                coef = np.ascontiguousarray(
-                    spline_filter(self.fa_map, order=3, output=np.float64))
-                self._fa_coef = torch.from_numpy(coef).to(self.device)
-
-    def reset(self, start: int, end: int):
-        self._noise_id_base = self.noise_id_offset + int(start)
-        return super().reset(start, end)
-
-    def nreset(self, n_seeds: int):
-        self._noise_id_base = self.noise_id_offset
-        return super().nreset(n_seeds)
+        if self.device_noise == 'keyed' and self.fa_map is not None and self._fa_coef is None:
+            if tuple(self.fa_map.shape) != tuple(self._mask_dim):
+                raise ValueError(f'fa_map grid {tuple(self.fa_map.shape)} differs from '
+                                 f"the tracking mask's {tuple(self._mask_dim)}")
+            from scipy.ndimage import spline_filter
+            coef = np.ascontiguousarray(
+                spline_filter(self.fa_map, order=3, output=np.float64))
+            self._fa_coef = torch.from_numpy(coef).to(self.device)
 
     def _start(self, initial_points):
         state = super()._start(initial_points)
         if self.device_noise == 'keyed':
             self._install_keyed_noise()
         return state
-
-    #: the backward pass of a batch draws with ``noise_seed ^ BACKWARD_SEED_XOR``
-    #: and the same ids: other numbers than the forward pass, as independent of
-    #: the batching
-    BACKWARD_SEED_XOR = 0x9E3779B97F4A7C15
 
     def reset_backward(self):
         state = super().reset_backward()
@@ -116,11 +105,11 @@ class NoisyTrackingEnvironment(TrackingEnvironment):
 
     def _install_keyed_noise(self, seed_xor=0):
         """Tell the handle what to draw for this batch: streamline g of the
-        batch is seed ``id_base + g`` of the run."""
+        batch is seed ``streamline_id_base() + g`` of the run."""
         n = self._n_total
         d = _lib.NoiseDesc()
         d.seed = (int(self.noise_seed) ^ seed_xor) & 0xffffffffffffffff
-        d.id_base = self._noise_id_base
+        d.id_base = self.streamline_id_base()
         d.sigma = float(self.noise)
         if self._fa_coef is not None:
             d.fa_coef = self._fa_coef.data_ptr()

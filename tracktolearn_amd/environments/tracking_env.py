@@ -32,184 +32,118 @@ import torch
 
 from tracktolearn_amd import _lib
 from tracktolearn_amd.environments.env import BaseEnv
+from tracktolearn_amd.environments.free_run import (  # noqa: F401 (re-exported)
+    _FreeRun, _FreeRunning, _policy_fingerprint)
+from tracktolearn_amd.environments.lazy_state import _LazyStateRows  # noqa: F401
+from tracktolearn_amd.environments.step_info import _PendingStep, _StepInfo
 from tracktolearn_amd.environments.stopping_criteria import StoppingFlags
 from tracktolearn_amd.tractogram import Tractogram
 
-
-class _StepInfo(dict):
-    """``info`` dict of ``step``; 'continue_idx' is downloaded on first use
-    (the reference puts the host index array there, tracking_env.py:220)."""
-
-    def __init__(self, env, n_active, reward_info):
-        super().__init__(reward_info=reward_info)
-        self._env, self._n = env, n_active
-        self._idx_dev = env._idx_view(n_active)
-
-    def __missing__(self, key):
-        if key == 'continue_idx':
-            val = self._idx_dev.to('cpu').numpy().astype(np.int64)
-            self[key] = val
-            return val
-        raise KeyError(key)
-
-    def __contains__(self, key):
-        return key == 'continue_idx' or super().__contains__(key)
-
-
-class _LazyStateRows(torch.Tensor):
-    """``step()``'s state rows in the reference's row order (one row per active
-    streamline, continue_idx order), gathered on first use.
-
-    The step writes its state rows survivors first, so that ``harvest()`` --
-    whose result the policy needs at once -- is a view and copies nothing.  The
-    reference's own tracking loop never looks at the rows ``step()`` returns
-    (rl.py:95-101 overwrites them with ``harvest()``'s); its training loop does
-    (ddpg.py: the replay buffer's ``next_state``).  This tensor serves both: it
-    has the shape, dtype and device of the real thing and becomes
-    ``rows[row_dest]`` (one gather, what ``harvest()`` used to pay as a copy)
-    the first time anything touches its values: torch operations (through
-    ``__torch_dispatch__``) and the accessors that bypass the dispatcher --
-    ``numpy()``, ``tolist()``, ``__array__``, ``data_ptr()``, storages, dlpack,
-    ``__cuda_array_interface__`` -- alike; conversions that would be no-ops on
-    a real tensor (``float()``, ``contiguous()``, ``to(same device)``,
-    ``detach()``) return the gathered PLAIN tensor.  ``materialize()`` is the
-    explicit form."""
-
-    @staticmethod
-    def __new__(cls, rows, row_dest):
-        t = torch.Tensor._make_wrapper_subclass(
-            cls, (int(row_dest.shape[0]), int(rows.shape[1])), dtype=rows.dtype,
-            device=rows.device)
-        t._rows, t._row_dest, t._value = rows, row_dest, None
-        return t
-
-    def materialize(self):
-        """The gathered rows as a plain ``torch.Tensor`` (cached)."""
-        if self._value is None:
-            self._value = self._rows.index_select(0, self._row_dest.long())
-            self._rows = self._row_dest = None
-        return self._value
-
-    def __repr__(self):
-        return f'_LazyStateRows(shape={tuple(self.shape)}, materialized={self._value is not None})'
-
-    @classmethod
-    def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
-        from torch.utils._pytree import tree_map
-
-        def real(x):
-            return x.materialize() if isinstance(x, _LazyStateRows) else x
-        return func(*tree_map(real, args), **tree_map(real, kwargs or {}))
-
-    @property
-    def data(self):
-        return self.materialize().data
-
-    @property
-    def __cuda_array_interface__(self):
-        return self.materialize().__cuda_array_interface__
-
-
-def _forward_to_gathered(name):
-    def method(self, *args, **kwargs):
-        return getattr(self.materialize(), name)(*args, **kwargs)
-    method.__name__ = name
-    method.__doc__ = f'``torch.Tensor.{name}`` of the gathered rows.'
-    return method
-
-
-# accessors implemented below the dispatcher (a wrapper subclass has no storage
-# of its own: data_ptr() would be 0, numpy() / storage access would raise) and
-# conversions that short-circuit to ``self`` before dispatching
-for _name in ('numpy', 'tolist', '__array__', 'data_ptr', 'untyped_storage', 'storage',
-              '_typed_storage', '__dlpack__', '__dlpack_device__', 'contiguous', 'float',
-              'double', 'half', 'bfloat16', 'to', 'type', 'cuda', 'cpu', 'detach', 'clone',
-              'pin_memory', 'record_stream', 'share_memory_', 'is_pinned', 'item',
-              'storage_offset', 'is_shared', '__reduce_ex__', '__deepcopy__'):
-    setattr(_LazyStateRows, _name, _forward_to_gathered(_name))
-del _name
-
-
-class _FreeRun:
-    """The captured graph of one free-running step (policy + env launches) and
-    the fixed buffers it works on."""
-
-    def __init__(self, env, n, policy, record_actions, owner=None):
-        dev = env.device
-        # the captured graph holds raw pointers to the policy's weights: keep
-        # the owner alive and remember which storages were captured, so that a
-        # replaced network (or another agent recycled at the same id()) is
-        # noticed instead of replayed on freed memory
-        self.owner = owner
-        self.fingerprint = _policy_fingerprint(owner)
-        self.state = env._new_state(n)
-        self.state.zero_()
-        self.done = torch.empty(n, dtype=torch.uint8, device=dev)
-        self.reward = self.reward_sum = None
-        if env.compute_reward:
-            self.reward = torch.empty(n, dtype=torch.float64, device=dev)
-            self.reward_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        self.actions_log = self.step_no = None
-        if record_actions:
-            self.actions_log = torch.zeros((env.max_nb_steps + 2, n, 3),
-                                           dtype=torch.float32, device=dev)
-            self.step_no = torch.zeros(1, dtype=torch.int64, device=dev)
-        # the policy's lazy initialisations (GEMM heuristics, workspaces) must
-        # not happen under capture
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(cur)
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        with torch.cuda.stream(side), torch.no_grad():
-            policy(self.state)
-            policy(self.state)
-            t0.record(side)
-            for _ in range(3):
-                policy(self.state)
-            t1.record(side)
-        cur.wait_stream(side)
-        t1.synchronize()
-        #: GPU + launch time of one policy evaluation on all n rows, microseconds
-        self.policy_us = t0.elapsed_time(t1) / 3 * 1e3
-        self.graph = None
-
-    def capture(self, env, policy):
-        """Between ttl_env_freerun_begin and _end: record policy + step."""
-        n, record_actions = self.state.shape[0], self.actions_log is not None
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            with torch.no_grad():
-                a = policy(self.state)
-            a = a.to(torch.float32).contiguous()
-            if a.shape != (n, 3):
-                raise ValueError(f'policy returned {tuple(a.shape)}, expected ({n}, 3)')
-            if record_actions:
-                self.actions_log.index_copy_(0, self.step_no, a[None])
-                self.step_no += 1
-            _lib.check(env._lib.ttl_env_freerun_step(
-                env._handle, a.data_ptr(), n, self.state.data_ptr(), env._state_pitch,
-                self.reward.data_ptr() if self.reward is not None else None,
-                self.done.data_ptr(), env._stream()), 'ttl_env_freerun_step')
-            if self.reward is not None:
-                self.reward_sum += self.reward.sum()
-            self.actions = a
-        self.graph = graph          # only a capture that went through is replayed
-
-
-def _policy_fingerprint(owner):
-    """Storage addresses of the parameters a captured policy reads (the owner's
-    own and its ``actor``'s when those are torch modules)."""
-    if owner is None:
-        return None
-    mods = []
-    for m in (owner, getattr(owner, 'actor', None), getattr(owner, 'agent', None)):
-        if isinstance(m, torch.nn.Module) and all(m is not k for k in mods):
-            mods.append(m)
-    return tuple(p.data_ptr() for m in mods for p in m.parameters())
+#: TTL_FUSE_MAX_ROWS, clamped as ttl_env_create clamps it: [256, 65536]
+_FUSE_MAX_ROWS = min(max(int(os.environ.get('TTL_FUSE_MAX_ROWS', '16384')), 256), 65536)
 
 
 class TrackingEnvironment(BaseEnv):
     """Tracking environment; also the "tracker" (see the reference class)."""
+
+    #: batches at least this large get a spatially sorted processing order
+    SPATIAL_ORDER_MIN = _FUSE_MAX_ROWS
+    #: False: no processing order at any size (measurements, tests)
+    spatial_order = True
+    #: the order is rebuilt from the current positions every this many steps
+    #: (a streamline crosses an 8-voxel brick in about ten 0.75-voxel steps;
+    #: the gather costs 0.72 ns per streamline in fresh order, 1.15 ns once
+    #: the order has decayed; measured best of 2/4/8/16/32); 0 = never.
+    #: Only where the library does not re-bucket the order inside its own
+    #: steps (TTL_ORDER_INSTEP, default every 2nd step wherever k_tail runs):
+    #: there this period and the low-fill refresh below are not used
+    SPATIAL_ORDER_REFRESH = int(os.environ.get('TTL_ORDER_REFRESH', '16'))
+    #: refresh the processing order early when fewer than this share of its slots
+    #: still hold a streamline
+    ORDER_MIN_FILL = float(os.environ.get('TTL_ORDER_MIN_FILL', '0.8'))
+    #: the oracle path as library calls (``ttl_env_stopped`` ->
+    #: ``ttl_oracle_segments`` -> the fused network -> ``ttl_oracle_bonus``: four
+    #: launches and the wait for the 8-byte counts that ``harvest()`` needs
+    #: anyway) instead of some twenty torch ops behind a ``nonzero`` sync;
+    #: ``TTL_ORACLE_FAST=0`` or a network the fused kernel does not support keep
+    #: the torch path
+    oracle_fast = os.environ.get('TTL_ORACLE_FAST', '1') != '0'
+    #: ``step()`` returns its state rows as a ``_LazyStateRows`` (gathered into the
+    #: reference's row order on first use) and ``harvest()`` copies nothing;
+    #: False (``TTL_LAZY_STEP_STATE=0``): the rows are written in the reference's
+    #: order and ``harvest()`` copies the survivors' rows
+    lazy_step_state = os.environ.get('TTL_LAZY_STEP_STATE', '1') != '0'
+    #: largest batch the free-running step takes (the one-launch step tail)
+    FREERUN_MAX = _FUSE_MAX_ROWS
+    #: inside a free-running episode (``run_free`` / ``run_free_eager``): a
+    #: policy that reads the device words takes its free-running entry point
+    _free_running = False
+    #: streamline g of the batch is seed ``noise_id_offset + _id_base + g`` of the
+    #: run: what ``reset(start, end)`` was given, past the seeds of other shards
+    #: (``env_dto['noise_id_offset']``, NoisyTrackingEnvironment)
+    _id_base = 0
+    noise_id_offset = 0
+    #: kernel classes `profile_begin` can bracket (ttl_env_profile_begin's mask bits)
+    PROFILE_CLASSES = ('advance', 'prefix', 'state', 'proc_scatter')
+
+    # ------------------------------------------------------------------ #
+    # episode state: the fields BaseEnv.__init__ lists change in these methods only.
+    # Of a backward pass: _init_len = the points every reversed forward half holds
+    # (int32 device tensor), flags_forward = the flags the forward pass ended with,
+    # seed_index = the index of the seed in every history row; None otherwise
+    def _batch_armed(self, n):
+        # n rows stand at their first point, none stepped yet (reset, nreset,
+        # reset_backward)
+        self._n_active = n
+        self._cur = 0
+        self.length = 1
+        self.not_stopping = None
+
+    def _forward_pass_armed(self, n):
+        # reset / nreset gave the handle a new batch of n seeds: whatever was
+        # pending or turned round belongs to the batch before
+        self._n_total = n
+        self._pending = None
+        self._init_len = self.flags_forward = self.seed_index = None
+        self._batch_armed(n)
+
+    def _backward_pass_armed(self, init_len, flags_forward):
+        # reset_backward turned the whole batch round (nothing was pending)
+        self._init_len = init_len       # borrowed by the handle until the next reset
+        self.flags_forward = flags_forward
+        self.seed_index = init_len - 1
+        self._batch_armed(self._n_total)
+
+    def _step_launched(self, pending):
+        # the launches of one step are queued; harvest() has yet to take it
+        self.length += 1
+        self._pending = pending
+
+    def _step_harvested(self, n_continue, not_stopping):
+        # harvest() took the pending step: n_continue rows go on, listed in the
+        # other index buffer
+        self.not_stopping = not_stopping
+        self._cur ^= 1
+        self._n_active = n_continue
+        self._pending = None
+
+    def _free_run_handed_back(self, n_left, length):
+        # a free-running episode that ran to its end handed back n_left rows at
+        # this length; steps replayed after the last streamline stopped changed
+        # nothing.  Returns the number of steps it took
+        n_steps = length - self.length
+        if n_steps & 1:
+            self._cur ^= 1
+        self.length = length
+        self._n_active = n_left
+        self._pending = None
+        self.not_stopping = None
+        return n_steps
+
+    def _sorts_rows(self, n):
+        # whether a batch of n rows is gathered in a spatially sorted processing
+        # order (built by the library)
+        return n >= self.SPATIAL_ORDER_MIN and self.spatial_order
 
     # ------------------------------------------------------------------ #
     def _idx_view(self, n):
@@ -228,28 +162,12 @@ class TrackingEnvironment(BaseEnv):
             np.ascontiguousarray(initial_points, dtype=np.float32)
         ).to(self.device)
         state = self._ring_state(n)
-        # batches of SPATIAL_ORDER_MIN rows and more are gathered in a
-        # spatially sorted processing order (built by the library)
-        sort_rows = n >= self.SPATIAL_ORDER_MIN and getattr(self, 'spatial_order', True)
         _lib.check(self._lib.ttl_env_reset(
             self._handle, seeds32.data_ptr(), n,
-            _lib.ORDER_BY_POSITION if sort_rows else None, state.data_ptr(),
+            _lib.ORDER_BY_POSITION if self._sorts_rows(n) else None, state.data_ptr(),
             self._state_pitch, self._stream()), 'ttl_env_reset')
-        self._n_total = n
-        self._n_active = n
-        self._cur = 0
-        self.length = 1
-        self._pending = None
-        self.not_stopping = None
-        self._init_len = self.flags_forward = self.seed_index = None
+        self._forward_pass_armed(n)
         return state
-
-    #: a backward pass is on (``reset_backward``): per-streamline int32 device
-    #: tensor of the points its reversed forward half holds; None otherwise
-    _init_len = None
-    #: after ``reset_backward``: the flags the forward pass ended with, and the
-    #: index of the seed in every history row (device tensors)
-    flags_forward = seed_index = None
 
     def reset_backward(self):
         """Bidirectional tracking (no counterpart in the reference, whose
@@ -268,32 +186,12 @@ class TrackingEnvironment(BaseEnv):
         flags_forward = self._buf_flags[:n].clone()
         init_len = torch.empty(n, dtype=torch.int32, device=self.device)
         state = self._ring_state(n)
-        sort_rows = n >= self.SPATIAL_ORDER_MIN and getattr(self, 'spatial_order', True)
         _lib.check(self._lib.ttl_env_reset_backward(
             self._handle, init_len.data_ptr(),
-            _lib.ORDER_BY_POSITION if sort_rows else None, state.data_ptr(),
+            _lib.ORDER_BY_POSITION if self._sorts_rows(n) else None, state.data_ptr(),
             self._state_pitch, self._stream()), 'ttl_env_reset_backward')
-        self._init_len = init_len       # borrowed by the handle until the next reset
-        self.flags_forward = flags_forward
-        self.seed_index = init_len - 1
-        self._n_active = n
-        self._cur = 0
-        self.length = 1
-        self.not_stopping = None
+        self._backward_pass_armed(init_len, flags_forward)
         return state
-
-    #: batches at least this large get a spatially sorted processing order
-    #: (TTL_FUSE_MAX_ROWS, clamped as ttl_env_create clamps it: [256, 65536])
-    SPATIAL_ORDER_MIN = min(max(int(os.environ.get('TTL_FUSE_MAX_ROWS', '16384')), 256), 65536)
-
-    #: the order is rebuilt from the current positions every this many steps
-    #: (a streamline crosses an 8-voxel brick in about ten 0.75-voxel steps;
-    #: the gather costs 0.72 ns per streamline in fresh order, 1.15 ns once
-    #: the order has decayed; measured best of 2/4/8/16/32); 0 = never.
-    #: Only where the library does not re-bucket the order inside its own
-    #: steps (TTL_ORDER_INSTEP, default every 2nd step wherever k_tail runs):
-    #: there this period and the low-fill refresh below are not used
-    SPATIAL_ORDER_REFRESH = int(os.environ.get('TTL_ORDER_REFRESH', '16'))
 
     def _refresh_processing_order(self, force=False):
         """Every SPATIAL_ORDER_REFRESH steps: re-sort the active rows by where
@@ -303,8 +201,7 @@ class TrackingEnvironment(BaseEnv):
         block of the order by current voxel at each step."""
         every = self.SPATIAL_ORDER_REFRESH
         n = self._n_active
-        if n < self.SPATIAL_ORDER_MIN or self._pending is not None or \
-                not getattr(self, 'spatial_order', True):
+        if not self._sorts_rows(n) or self._pending is not None:
             return
         slots, instep = self._library_order()
         if not force and instep:
@@ -330,9 +227,6 @@ class TrackingEnvironment(BaseEnv):
             self._handle, C.byref(slots), C.byref(period)), 'ttl_env_order_slots')
         return slots.value, period.value
 
-    #: refresh the processing order early when fewer than this share of its slots
-    #: still hold a streamline
-    ORDER_MIN_FILL = float(os.environ.get('TTL_ORDER_MIN_FILL', '0.8'))
     def nreset(self, n_seeds: int):
         """N random seeds among all seeds (tracking_env.py:47-89; global
         numpy RNG, as the reference)."""
@@ -366,28 +260,23 @@ class TrackingEnvironment(BaseEnv):
         return self._io
 
     def _actions_to_device(self, actions):
-        if isinstance(actions, torch.Tensor):
+        n, on_device = self._n_active, isinstance(actions, torch.Tensor)
+        if not on_device:
+            actions = np.ascontiguousarray(actions, dtype=np.float32)
+        if actions.shape != (n, 3):
+            raise ValueError(f'actions must be ({n}, 3), got {tuple(actions.shape)}')
+        if on_device:
             a = actions
             if a.dtype is not torch.float32 or a.device != self.device:
                 a = a.to(device=self.device, dtype=torch.float32)
-        else:
-            # a host array (the reference's contract, rl.py:93-94): straight from
-            # the caller's pageable memory into a persistent device buffer.  The
-            # runtime's own chunked staging overlaps the host copy with the DMA
-            # (0.076 ms for 262 144 x 3 floats; through a pinned buffer of ours
-            # 0.047 ms host copy + 0.073 ms DMA one after the other:
-            # benchmarks/micro/h2d_probe.py)
-            actions = np.ascontiguousarray(actions, dtype=np.float32)
-            n = self._n_active
-            if actions.shape != (n, 3):
-                raise ValueError(
-                    f'actions must be ({n}, 3), got {tuple(actions.shape)}')
-            a = self._host_io()['act_dev'][:n]
-            a.copy_(torch.from_numpy(actions))
-        a = a.contiguous()
-        if a.shape != (self._n_active, 3):
-            raise ValueError(
-                f'actions must be ({self._n_active}, 3), got {tuple(a.shape)}')
+            return a.contiguous()
+        # a host array (the reference's contract, rl.py:93-94): straight from the
+        # caller's pageable memory into a persistent device buffer.  The runtime's
+        # own chunked staging overlaps the host copy with the DMA (0.076 ms for
+        # 262 144 x 3 floats; through a pinned buffer of ours 0.047 ms host copy +
+        # 0.073 ms DMA one after the other: benchmarks/micro/h2d_probe.py)
+        a = self._host_io()['act_dev'][:n]
+        a.copy_(torch.from_numpy(actions))
         return a
 
     def _noise_for(self, actions):
@@ -422,45 +311,38 @@ class TrackingEnvironment(BaseEnv):
         noise_ptr = noise.data_ptr() if noise is not None else None
         reward_ptr = reward.data_ptr() if reward is not None else None
         early = host_outputs and not self._use_oracle_stopping and not self._use_oracle_reward
-        if early:
-            io = self._host_io()
-            _lib.check(self._lib.ttl_env_step_begin(
-                self._handle, a.data_ptr(), noise_ptr, n, reward_ptr,
-                done.data_ptr(), self._stream()), 'ttl_env_step_begin')
-            io['done_pin'][:n].copy_(done, non_blocking=True)
-            if reward is not None:
-                io['reward_pin'][:n].copy_(reward, non_blocking=True)
-            io['event'].record()
-            _lib.check(self._lib.ttl_env_step_end(
-                self._handle, None, order, state.data_ptr(), self._state_pitch,
-                self._host_counts.data_ptr(), self._stream()), 'ttl_env_step_end')
-        elif not self._use_oracle_stopping:
+        if not early and not self._use_oracle_stopping:
             _lib.check(self._lib.ttl_env_step(
                 self._handle, a.data_ptr(), noise_ptr, n, order,
                 state.data_ptr(), self._state_pitch, reward_ptr,
                 done.data_ptr(), self._host_counts.data_ptr(), self._stream()),
                 'ttl_env_step')
         else:
-            # the oracle criterion sits between the point update and the
-            # compaction (criteria order LENGTH, CURVATURE, ORACLE, MASK;
-            # env.py:233-260 -- the flags are OR-ed, so the order is moot)
+            # between the point update and the compaction: the copies of dones /
+            # reward to the host, or the oracle criterion (criteria order LENGTH,
+            # CURVATURE, ORACLE, MASK; env.py:233-260 -- the flags are OR-ed, so
+            # the order is moot)
+            io = self._host_io() if early else None
             _lib.check(self._lib.ttl_env_step_begin(
                 self._handle, a.data_ptr(), noise_ptr, n, reward_ptr,
                 done.data_ptr(), self._stream()), 'ttl_env_step_begin')
-            extra = self._oracle_stopping_flags(n, self.length + 1)
+            extra = None
+            if early:
+                io['done_pin'][:n].copy_(done, non_blocking=True)
+                if reward is not None:
+                    io['reward_pin'][:n].copy_(reward, non_blocking=True)
+                io['event'].record()
+            else:
+                extra = self._keep_alive = self._oracle_stopping_flags(n, self.length + 1)
             _lib.check(self._lib.ttl_env_step_end(
                 self._handle, extra.data_ptr() if extra is not None else None,
                 order, state.data_ptr(), self._state_pitch,
-                self._host_counts.data_ptr(), self._stream()),
-                'ttl_env_step_end')
-            self._keep_alive = extra
+                self._host_counts.data_ptr(), self._stream()), 'ttl_env_step_end')
         self._last_oracle_term = None
         if self._use_oracle_reward:
             self._last_oracle_term = self._oracle_reward(
                 n, self.length + 1, done, reward)
-        self.length += 1
-        self._pending = dict(order=order, state=state, n=n, done=done,
-                             keep=(a, noise), early=early)
+        self._step_launched(_PendingStep(order, state, n, done, (a, noise), early))
         return state, reward, done
 
     # -- oracle criterion / reward: torch ops between the library calls ----- #
@@ -487,7 +369,6 @@ class TrackingEnvironment(BaseEnv):
                 self._oracle_lin_host)
         else:
             scores = self._oracle.predict(self._oracle_points(None, n_points))
-        from tracktolearn_amd.environments.stopping_criteria import StoppingFlags
         stop = scores < 0.5
         if self._init_len is not None:
             # a backward pass: a row still on its way back to the seed is not
@@ -513,21 +394,12 @@ class TrackingEnvironment(BaseEnv):
         reward += term
         return term
 
-    #: the oracle path as library calls (``ttl_env_stopped`` ->
-    #: ``ttl_oracle_segments`` -> the fused network -> ``ttl_oracle_bonus``: four
-    #: launches and the wait for the 8-byte counts that ``harvest()`` needs
-    #: anyway) instead of some twenty torch ops behind a ``nonzero`` sync;
-    #: ``TTL_ORACLE_FAST=0`` or a network the fused kernel does not support keep
-    #: the torch path
-    oracle_fast = os.environ.get('TTL_ORACLE_FAST', '1') != '0'
-
     def _oracle_fast(self):
         return self.oracle_fast and getattr(self._oracle, 'net', None) is not None
 
     def _oracle_reward_fast(self, n, n_points, reward):
         """``_oracle_reward`` on the rows ``ttl_env_stopped`` lists (the rows
         ``nonzero(done)`` finds, in the same order)."""
-        import ctypes as C
         lst, n_stop = C.c_void_p(), C.c_int32()
         _lib.check(self._lib.ttl_env_stopped(self._handle, C.byref(lst), C.byref(n_stop)),
                    'ttl_env_stopped')
@@ -558,13 +430,14 @@ class TrackingEnvironment(BaseEnv):
         lazy = self.lazy_step_state
         state, reward, done = self._launch_step(
             actions, _lib.ORDER_PARTITION if lazy else _lib.ORDER_ACTIVE, host_outputs=True)
-        n = self._pending['n']
+        pend = self._pending
+        n = pend.n
         if lazy:
             # the rows were written survivors first (harvest() will be a view);
             # the reference's row order is one gather away, paid only by callers
             # that look (the map is copied: the library rewrites it every step)
             state = _LazyStateRows(state, self._row_dest_view(n).clone())
-        if self._pending['early']:
+        if pend.early:
             # dones / reward were copied to pinned memory right behind the
             # step's first kernel: wait for those copies only
             io = self._io
@@ -574,7 +447,7 @@ class TrackingEnvironment(BaseEnv):
         else:
             dones = done.to('cpu').numpy().astype(bool)      # syncs the stream
             reward_np = reward.to('cpu').numpy() if reward is not None else None
-        self._pending['dones_host'] = dones
+        pend.dones_host = dones
         reward_info = {}
         if reward is not None:
             # reward.py:73-75: mean of each weighted factor
@@ -588,21 +461,15 @@ class TrackingEnvironment(BaseEnv):
             # step, so one array per batch size (never written by the callers,
             # which sum it: rl.py:97, ddpg.py:209)
             reward_np = self._zero_reward(self._n_total)
-        info = _StepInfo(self, self._pending['n'], reward_info)
+        info = _StepInfo(self, n, reward_info)
         return state, reward_np, dones, info
 
     def _zero_reward(self, n):
-        z = getattr(self, '_zero_reward_np', None)
+        z = self._zero_reward_np
         if z is None or z.shape[0] != n:
             z = self._zero_reward_np = np.zeros(n)
             z.flags.writeable = False       # shared between steps: writing it raises
         return z
-
-    #: ``step()`` returns its state rows as a ``_LazyStateRows`` (gathered into the
-    #: reference's row order on first use) and ``harvest()`` copies nothing;
-    #: False (``TTL_LAZY_STEP_STATE=0``): the rows are written in the reference's
-    #: order and ``harvest()`` copies the survivors' rows
-    lazy_step_state = os.environ.get('TTL_LAZY_STEP_STATE', '1') != '0'
 
     def step_device(self, actions):
         """Device-resident step: no host copy, no sync.  ``state`` rows are
@@ -612,9 +479,8 @@ class TrackingEnvironment(BaseEnv):
         tensors in active-row order.  ``harvest()`` afterwards returns the
         leading rows of ``state`` without copying."""
         state, reward, done = self._launch_step(actions, _lib.ORDER_PARTITION)
-        n = self._pending['n']
-        info = {'row_dest': self._row_dest_view(n), 'reward_info': {}}
-        return state, reward, done, info
+        return state, reward, done, {'row_dest': self._row_dest_view(self._pending.n),
+                                     'reward_info': {}}
 
     def _row_dest_view(self, n):
         """int32 view of the library's active-row -> state-row map."""
@@ -633,12 +499,8 @@ class TrackingEnvironment(BaseEnv):
         if self._pending is None:
             raise RuntimeError('no step to harvest')
         pend = self._pending
-        n = pend['n']
-        order = pend['order']
-        state_in = pend['state']
-        out = None
-        if order == _lib.ORDER_ACTIVE:
-            out = self._new_state(state_in.shape[0])
+        state_in = pend.state
+        out = self._new_state(state_in.shape[0]) if pend.order == _lib.ORDER_ACTIVE else None
         # the survivor count left the GPU right after the stopping decisions
         # (written by the step's kernel into pinned memory): this wait does not
         # cover the state gather
@@ -648,29 +510,13 @@ class TrackingEnvironment(BaseEnv):
             out.data_ptr() if out is not None else None, self._state_pitch,
             self._stream(), n_out), 'ttl_env_harvest')
         n_cont = n_out.value
-        if order == _lib.ORDER_ACTIVE:
-            new_state = out[:n_cont]
-        else:
-            new_state = state_in[:n_cont]
-        if 'dones_host' in pend:
-            self.not_stopping = np.logical_not(pend['dones_host'])
-        else:
-            self.not_stopping = None
-        self._cur ^= 1
-        self._n_active = n_cont
-        self._pending = None
+        new_state = (out if out is not None else state_in)[:n_cont]
+        self._step_harvested(n_cont, np.logical_not(pend.dones_host)
+                             if pend.dones_host is not None else None)
         return new_state, self.not_stopping
 
     # ------------------------------------------------------------------ #
     # free-running episode: policy + step in one HIP graph, no host in the loop
-    #: largest batch the free-running step takes (the one-launch step tail;
-    #: TTL_FUSE_MAX_ROWS clamped as ttl_env_create clamps it)
-    FREERUN_MAX = min(max(int(os.environ.get('TTL_FUSE_MAX_ROWS', '16384')), 256), 65536)
-
-    #: between ttl_env_freerun_begin and _end (``run_free`` / ``run_free_eager``):
-    #: a policy that reads the device words takes its free-running entry point
-    _free_running = False
-
     def _has_action_noise(self):
         return False
 
@@ -690,8 +536,8 @@ class TrackingEnvironment(BaseEnv):
     def _wait_for_gpu(counts, step_no, timeout_s=20.0):
         """Spin until the GPU has reported step ``step_no`` in the pinned words
         (free-running loops: keeps the host a bounded number of steps ahead).
-        Bounded: a GPU that stopped answering surfaces as an error in
-        ``ttl_env_freerun_end`` instead of a hang here."""
+        Bounded: a GPU that stopped answering surfaces as an error at the
+        episode's end (``_FreeRunning.__exit__``) instead of a hang here."""
         if int(counts[2]) >= step_no:
             return
         t0 = time.perf_counter()
@@ -725,10 +571,8 @@ class TrackingEnvironment(BaseEnv):
             raise RuntimeError('run_free_eager: not available for this configuration')
         n = self._n_active
         dev = self.device
-        buf = self._free_bufs.get(n) if hasattr(self, '_free_bufs') else None
+        buf = self._free_bufs.get(n)
         if buf is None:
-            if not hasattr(self, '_free_bufs'):
-                self._free_bufs = {}
             reward = torch.empty(n, dtype=torch.float64, device=dev) \
                 if self.compute_reward else None
             if len(self._free_bufs) >= 4:       # batch sizes normally repeat
@@ -739,11 +583,7 @@ class TrackingEnvironment(BaseEnv):
         state_buf[:n].copy_(state)
         reward_sum = torch.zeros((), dtype=torch.float64, device=dev) \
             if reward is not None else None
-        _lib.check(self._lib.ttl_env_freerun_begin(
-            self._handle, self._host_counts.data_ptr(), self._stream()),
-            'ttl_env_freerun_begin')
-        self._free_running = True
-        try:
+        with _FreeRunning.begin(self) as episode:
             counts = self._host_counts_np
             step_fn, handle, pitch = self._lib.ttl_env_freerun_step, self._handle, self._state_pitch
             reward_ptr = reward.data_ptr() if reward is not None else None
@@ -765,19 +605,7 @@ class TrackingEnvironment(BaseEnv):
                     reward_sum += reward[:cap].sum()
                 steps += 1
                 self._wait_for_gpu(counts, steps - lookahead)
-        finally:
-            self._free_running = False
-            n_left, length, done_steps = C.c_int32(), C.c_int32(), C.c_int32()
-            _lib.check(self._lib.ttl_env_freerun_end(
-                self._handle, C.byref(n_left), C.byref(length), C.byref(done_steps),
-                self._stream()), 'ttl_env_freerun_end')
-        n_steps = length.value - self.length
-        if n_steps & 1:
-            self._cur ^= 1
-        self.length = length.value
-        self._n_active = n_left.value
-        self._pending = None
-        self.not_stopping = None
+        n_steps = self._free_run_handed_back(episode.n_left, episode.length)
         return reward_sum, n_steps
 
     def run_free(self, policy, state, key=None, record_actions=False, max_policy_us=None,
@@ -818,14 +646,13 @@ class TrackingEnvironment(BaseEnv):
             fr = None
         if fr is not None and max_policy_us is not None and fr.policy_us > max_policy_us:
             return None         # a replayed graph would lose to the shrinking batches
-        rc = self._lib.ttl_env_freerun_begin(
-            self._handle, self._host_counts.data_ptr(), self._stream())
-        if rc == _lib.ERR_UNSUPPORTED:
+        episode = _FreeRunning.begin(self, or_none=True)
+        if episode is None:
             return None         # the library has no free-running path here: the caller
             #                     keeps its step-by-step loop (as for a slow policy)
-        _lib.check(rc, 'ttl_env_freerun_begin')
-        self._free_running = True
-        try:
+        with episode:
+            # (the two ``return None`` below end the episode in the library and
+            # leave the env's bookkeeping alone, as an exception does)
             if fr is None:      # buffers + one timing of the policy on n rows (the policy
                 # may itself read the free-running words: timed after begin)
                 if len(self._free_runs) >= 8:       # keys normally repeat (batch size, agent)
@@ -854,23 +681,9 @@ class TrackingEnvironment(BaseEnv):
                     break
                 # the host runs ahead of the GPU; keep the distance bounded so
                 # that few empty steps are queued behind the last real one
-                if counts[0] != 0:
-                    self._wait_for_gpu(counts, steps - 24)
-        finally:
-            self._free_running = False
-            n_left, length, done = C.c_int32(), C.c_int32(), C.c_int32()
-            _lib.check(self._lib.ttl_env_freerun_end(
-                self._handle, C.byref(n_left), C.byref(length), C.byref(done),
-                self._stream()), 'ttl_env_freerun_end')
-        # the host view catches up with what the device did; steps replayed
-        # after the last streamline stopped changed nothing
-        n_steps = length.value - self.length
-        if n_steps & 1:
-            self._cur ^= 1
-        self.length = length.value
-        self._n_active = n_left.value
-        self._pending = None
-        self.not_stopping = None
+                self._wait_for_gpu(counts, steps - 24)
+        # the host view catches up with what the device did
+        n_steps = self._free_run_handed_back(episode.n_left, episode.length)
         reward = fr.reward_sum.clone() if fr.reward_sum is not None else None
         if record_actions:
             return reward, n_steps, fr.actions_log[:n_steps].clone()
@@ -927,13 +740,10 @@ class TrackingEnvironment(BaseEnv):
 
     # ------------------------------------------------------------------ #
     # fODF policy (tracking/odf_policy.py; ttl_odf_actions)
-    #: streamline g of the batch is seed ``_id_base + g`` of the run (what
-    #: ``reset(start, end)`` was given; the keyed noise counts the same way)
-    _id_base = 0
-
     def streamline_id_base(self):
-        """Id of the batch's first streamline: the keyed noise's id base."""
-        return int(getattr(self, 'noise_id_offset', 0)) + int(self._id_base)
+        """Streamline g of this batch is seed number ``streamline_id_base() + g``
+        of the run: the id the keyed noise and the fODF policy key on."""
+        return int(self.noise_id_offset) + int(self._id_base)
 
     def _odf_args(self, sf_matrix, dirs, cos_theta, rel_threshold, mode, seed, id_base):
         # (the signal may carry more channels than SH coefficients: --input_wm)
@@ -985,9 +795,6 @@ class TrackingEnvironment(BaseEnv):
             self._stream()), 'ttl_env_freerun_odf_actions')
         return out
 
-    #: kernel classes `profile_begin` can bracket (ttl_env_profile_begin's mask bits)
-    PROFILE_CLASSES = ('advance', 'prefix', 'state', 'proc_scatter')
-
     def profile_begin(self, max_launches=4096, classes=('state',)):
         """Bracket the step kernels of the given classes (PROFILE_CLASSES) with
         HIP events on the launch stream."""
@@ -997,7 +804,6 @@ class TrackingEnvironment(BaseEnv):
 
     def profile_end(self):
         """{class: (total_ms, n_launches)} for every class of PROFILE_CLASSES."""
-        import ctypes as C
         k = len(self.PROFILE_CLASSES)
         ms = (C.c_double * k)()
         n = (C.c_int32 * k)()
