@@ -558,6 +558,62 @@ TTL_API int ttl_env_freerun_odf_actions(ttl_env *env, const float *state, int64_
                                         int64_t ids_base, int32_t n_rows, float *actions_out,
                                         int32_t *vertex_out, void *hip_stream);
 
+/* Anatomically constrained stopping (TTL_HAS_ACT): the tissue-map
+ * criteria of ACT (dipy's ActStoppingCriterion) and CMC (Girard 2014, dipy's
+ * CmcStoppingCriterion) as stopping bits for ttl_env_step_end(extra_flags).
+ * include / exclude: device f32 [X][Y][Z] maps of equal dims (z fastest), e.g.
+ * grey matter and CSF.  tests/ref_act.py restates the definition.
+ * Sampling, for row r < n:
+ *   g    = ids[r] (r when ids is NULL); p = point n_points - 1 of history row g
+ *          (history [.][row_pitch] f32, three floats per point);
+ *   x_c  = (double)p_c + coord_shift;
+ *   inside iff x_c >= -0.5 and x_c < dim_c - 0.5 for every c (NaN compares false:
+ *          NaN and +-Inf are outside).  Outside: include = exclude = 0 and no bit
+ *          (the tracking mask ends such a row);
+ *   inside: i_c = floor(x_c), f_c = x_c - i_c, lo_c = clamp(i_c, 0, dim_c - 1),
+ *          hi_c = clamp(i_c + 1, 0, dim_c - 1); all in float64, every multiply and
+ *          every add rounded once, in this order:
+ *            along z: c_ab = v[a][b][lo_z] * (1 - f_z) + v[a][b][hi_z] * f_z,
+ *                     a in {lo_x, hi_x}, b in {lo_y, hi_y};
+ *            along y: c_a  = c_a,lo * (1 - f_y) + c_a,hi * f_y;
+ *            along x: val  = c_lo * (1 - f_x) + c_hi * f_x;
+ *   values_out (or NULL) [r][0] = include, [r][1] = exclude, for every row.
+ * Suppression: with init_len != NULL a row with n_points <= init_len[g] gets
+ *   flags_out[r] = 0: in a backward pass (ttl_env_reset_backward) only points the
+ *   pass itself created are judged, never the replayed half or the seed (`<=`, where
+ *   the oracle criterion has `>`: a seed inside grey matter must not end its own
+ *   backward half).
+ * TTL_ACT_THRESHOLD: TTL_FLAG_TARGET iff include > 0.5, otherwise TTL_FLAG_EXCLUDE
+ *   iff exclude > 0.5, otherwise 0: include first, never both bits.
+ * TTL_ACT_CMC: s = include + exclude; not s > 0: 0.  num = 1 - s, 0 when negative;
+ *   den = num + s; rho = num / den; P = pow(rho, exponent) in float64 (rho itself
+ *   for exponent == 1).  Philox4x32-10 as at ttl_env_set_noise, key = the two halves
+ *   of `seed`, counter = (id low, id high, n_points, TTL_ACT_STREAM), id = ids_base
+ *   + g; u1 = (word 0 >> 8) * 2^-24, u2 = (word 1 >> 8) * 2^-24.  The row stops iff
+ *   u1 >= P (s >= 1 always stops); a stopped row is TTL_FLAG_TARGET iff
+ *   u2 < include / s, else TTL_FLAG_EXCLUDE.
+ * TTL_ERR_INVALID before any launch, flags_out untouched: a null desc, map, history
+ * or flags pointer, a dim < 1, an unknown mode, n < 0, n_points < 1, row_pitch <
+ * 3 * n_points, ids_base < 0, in CMC mode an exponent not finite and positive.
+ * n == 0 launches nothing.  One lane per row, workgroups of 256. */
+#define TTL_HAS_ACT 1
+#define TTL_FLAG_TARGET  8      /* StoppingFlags.STOPPING_TARGET: ended by the include map */
+#define TTL_FLAG_EXCLUDE 128    /* no StoppingFlags member: ended by the exclude map       */
+#define TTL_ACT_THRESHOLD 0
+#define TTL_ACT_CMC       1
+#define TTL_ACT_STREAM 0x41435420u   /* Philox counter word 3; noise uses 0/1, the fODF policy 0x4F444650 */
+typedef struct ttl_act_desc {
+    const float *include, *exclude;  /* device f32 [X][Y][Z], same dims */
+    int32_t dim[3]; int32_t mode;
+    double coord_shift;              /* added to a coordinate before sampling; 0: voxel i centred at i */
+    double exponent;                 /* CMC: step_size_mm / mean voxel size; > 0, finite */
+    uint64_t seed; int64_t ids_base;
+} ttl_act_desc;
+TTL_API int ttl_act_flags(const ttl_act_desc *desc, const float *history, int64_t row_pitch,
+                          const int32_t *ids, const int32_t *init_len, int32_t n,
+                          int32_t n_points, uint8_t *flags_out, double *values_out,
+                          void *hip_stream);
+
 /* fODF peaks of an SH volume (replaces the per-voxel Python loop of
  * TrackToLearn/environments/env.py:405-432: sh_to_sf_matrix + get_maximas per
  * voxel, 5 peaks scaled by value / first value).  sh: [n_voxels][n_coef] f32;

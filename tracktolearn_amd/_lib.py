@@ -32,6 +32,9 @@ TRACTOMETER_MAX_ROIS = 128            # TTL_TRACTOMETER_MAX_ROIS
 ERR_INVALID, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4
 ODF_DET, ODF_PROB = 0, 1                # TTL_ODF_DET / TTL_ODF_PROB
 ODF_MAX_COEF, ODF_GRID_CAP = 64, 1024   # TTL_ODF_MAX_COEF / TTL_ODF_GRID_CAP
+FLAG_TARGET, FLAG_EXCLUDE = 8, 128      # TTL_FLAG_TARGET / TTL_FLAG_EXCLUDE
+ACT_THRESHOLD, ACT_CMC = 0, 1           # TTL_ACT_THRESHOLD / TTL_ACT_CMC
+ACT_STREAM = 0x41435420                 # TTL_ACT_STREAM
 
 
 class TTLError(RuntimeError):
@@ -113,6 +116,21 @@ class TractFileDesc(C.Structure):
         ('pre_scale', C.c_double),
         ('maps', (C.c_double * 12) * 2),
         ('post_scale', C.c_double * 3),
+    ]
+
+
+class ActDesc(C.Structure):
+    """struct ttl_act_desc (include/ttl_hip.h): tissue maps and mode of the
+    ACT / CMC stopping criterion."""
+    _fields_ = [
+        ('include', C.c_void_p),
+        ('exclude', C.c_void_p),
+        ('dim', C.c_int32 * 3),
+        ('mode', C.c_int32),
+        ('coord_shift', C.c_double),
+        ('exponent', C.c_double),
+        ('seed', C.c_uint64),
+        ('ids_base', C.c_int64),
     ]
 
 
@@ -206,6 +224,9 @@ SYMBOLS = {
                                               C.c_float, C.c_float, C.c_int32, C.c_uint64,
                                               C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
+    'ttl_act_flags': (C.c_int, [C.POINTER(ActDesc), C.c_void_p, C.c_int64, C.c_void_p,
+                                C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
     'ttl_peaks_from_sh': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.c_float, C.c_float,

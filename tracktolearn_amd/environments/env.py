@@ -146,6 +146,18 @@ class BaseEnv(object):
         #: interpolation it replaces could not be inspected offline
         self.sh_coord_shift = float(env_dto.get('sh_coord_shift', 0.0))
 
+        # anatomically constrained stopping: tissue maps on the
+        # tracking grid, given both or neither; 'act' thresholds them, 'cmc' draws
+        self._act_maps = self._act_desc = None
+        self._act_include_host = env_dto.get('act_include')
+        self._act_exclude_host = env_dto.get('act_exclude')
+        if (self._act_include_host is None) != (self._act_exclude_host is None):
+            raise ValueError("env_dto['act_include'] and env_dto['act_exclude'] go together")
+        self.act_mode = env_dto.get('act_mode', 'act')
+        if self.act_mode not in ('act', 'cmc'):
+            raise ValueError(f"act_mode must be 'act' or 'cmc', not {self.act_mode!r}")
+        self.act_seed = int(env_dto.get('act_seed') or 0)
+
         self._device_index = self.device.index if self.device.index is not None \
             else (torch.cuda.current_device() if self.device.type == 'cuda' else 0)
         if self.device.type != 'cuda':
@@ -251,6 +263,8 @@ class BaseEnv(object):
                 self._mask_coef.data_ptr(), dims,
                 float(self.binary_stopping_threshold),
                 self._mask_cls.data_ptr(), stream), 'ttl_mask_classes')
+
+        self._load_act_maps(mask_data.shape)
 
         self._peaks_dev = None
         self._peaks_dim = (0, 0, 0)
@@ -453,6 +467,32 @@ class BaseEnv(object):
                                          rotate=self.STATE_RING_ROTATE)
         self._destroy_handle()
 
+    def _load_act_maps(self, mask_shape):
+        """The include / exclude maps of the ACT / CMC criterion, uploaded once
+        per subject as float32 on the tracking mask's grid, and the descriptor
+        ``TrackingEnvironment.act_flags`` hands to ``ttl_act_flags``.  Voxel i
+        is centred at coordinate i (``coord_shift`` 0), as for the SH gather and
+        the file writers."""
+        self._act_maps = self._act_desc = None
+        if self._act_include_host is None:
+            return
+        maps = []
+        for key, vol in (('act_include', self._act_include_host),
+                         ('act_exclude', self._act_exclude_host)):
+            arr = np.asarray(getattr(vol, 'data', vol))
+            if tuple(arr.shape) != tuple(mask_shape):
+                raise ValueError(f"env_dto['{key}'] has grid {tuple(arr.shape)}, the tracking "
+                                 f"mask {tuple(mask_shape)}")
+            maps.append(torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+                        .to(self.device))
+        self._act_maps = tuple(maps)
+        d = _lib.ActDesc()
+        d.include, d.exclude = maps[0].data_ptr(), maps[1].data_ptr()
+        d.dim[:] = [int(v) for v in mask_shape]
+        d.mode = _lib.ACT_CMC if self.act_mode == 'cmc' else _lib.ACT_THRESHOLD
+        d.coord_shift = 0.0
+        self._act_desc = d
+
     def _rederive_tracking_params(self):
         # the caller may have changed step size / lengths of the loaded subject:
         # the handle was built on the old values
@@ -486,6 +526,10 @@ class BaseEnv(object):
             self._mode = _lib.MODE_F32NORM
         else:
             self._mode = _lib.MODE_F32
+        # CMC: the per-step probabilities are stated per voxel crossed (the mean
+        # voxel size the Tracker scales its lengths by)
+        self._act_exponent = float(self.step_size_mm) / float(
+            np.mean(np.abs(np.asarray(self.affine_vox2rasmm))[np.diag_indices(4)][:3]))
         self._loaded_params_key = self._tracking_params_key()
 
     def _new_state(self, n):

@@ -24,6 +24,11 @@ class StoppingFlags(Enum):
     STOPPING_ORACLE = int('01000000', 2)
 
 
+#: ended by the exclude map of the ACT / CMC criterion (TTL_FLAG_EXCLUDE): a
+#: plain constant, not a member -- the reference's enum is iterated as it is
+ACT_EXCLUDE_FLAG = 128
+
+
 def is_flag_set(flags, ref_flag):
     """Which entries of ``flags`` have ``ref_flag`` set
     (stopping_criteria.py:23-28)."""

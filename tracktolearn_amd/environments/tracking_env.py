@@ -310,8 +310,10 @@ class TrackingEnvironment(BaseEnv):
             reward = torch.empty(n, dtype=torch.float64, device=self.device)
         noise_ptr = noise.data_ptr() if noise is not None else None
         reward_ptr = reward.data_ptr() if reward is not None else None
-        early = host_outputs and not self._use_oracle_stopping and not self._use_oracle_reward
-        if not early and not self._use_oracle_stopping:
+        use_act = self._act_desc is not None
+        early = host_outputs and not self._use_oracle_stopping and \
+            not self._use_oracle_reward and not use_act
+        if not early and not self._use_oracle_stopping and not use_act:
             _lib.check(self._lib.ttl_env_step(
                 self._handle, a.data_ptr(), noise_ptr, n, order,
                 state.data_ptr(), self._state_pitch, reward_ptr,
@@ -319,9 +321,10 @@ class TrackingEnvironment(BaseEnv):
                 'ttl_env_step')
         else:
             # between the point update and the compaction: the copies of dones /
-            # reward to the host, or the oracle criterion (criteria order LENGTH,
-            # CURVATURE, ORACLE, MASK; env.py:233-260 -- the flags are OR-ed, so
-            # the order is moot)
+            # reward to the host, or the criteria computed outside the step -- the
+            # oracle's and the tissue maps' (criteria order LENGTH, CURVATURE,
+            # ORACLE, MASK; env.py:233-260 -- the flags are OR-ed, so the order is
+            # moot)
             io = self._host_io() if early else None
             _lib.check(self._lib.ttl_env_step_begin(
                 self._handle, a.data_ptr(), noise_ptr, n, reward_ptr,
@@ -333,7 +336,12 @@ class TrackingEnvironment(BaseEnv):
                     io['reward_pin'][:n].copy_(reward, non_blocking=True)
                 io['event'].record()
             else:
-                extra = self._keep_alive = self._oracle_stopping_flags(n, self.length + 1)
+                if self._use_oracle_stopping:
+                    extra = self._oracle_stopping_flags(n, self.length + 1)
+                if use_act:
+                    act = self.act_flags(n, self.length + 1)
+                    extra = act if extra is None else extra | act
+                self._keep_alive = extra
             _lib.check(self._lib.ttl_env_step_end(
                 self._handle, extra.data_ptr() if extra is not None else None,
                 order, state.data_ptr(), self._state_pitch,
@@ -375,6 +383,34 @@ class TrackingEnvironment(BaseEnv):
             # judged (it would lose points the forward pass kept)
             stop &= ~(self._init_len[self._idx_view(n).long()] > n_points)
         return stop.to(torch.uint8) * StoppingFlags.STOPPING_ORACLE.value
+
+    # -- tissue maps: ACT / CMC stopping (ttl_act_flags) -------- #
+    #: the backward pass of a batch draws with ``act_seed ^ BACKWARD_SEED_XOR``, as
+    #: the keyed noise and the fODF policy do
+    BACKWARD_SEED_XOR = 0x9E3779B97F4A7C15
+
+    def act_flags(self, n, n_points):
+        """The tissue-map criterion on the newest of the ``n_points`` points of
+        the ``n`` active rows: uint8 (n,) with ``STOPPING_TARGET`` where the
+        include map ends a row and ``ACT_EXCLUDE_FLAG`` where the exclude map
+        does.  In a backward pass only points the pass itself created are
+        judged.  The CMC draw is keyed by (``act_seed``, global index of the
+        streamline's seed, n_points): independent of the batching."""
+        d = self._act_desc
+        if d is None:
+            raise RuntimeError("no tissue maps: env_dto['act_include'] / ['act_exclude']")
+        backward = self._init_len is not None
+        d.exponent = self._act_exponent
+        d.seed = (self.act_seed ^ (self.BACKWARD_SEED_XOR if backward else 0)) & \
+            0xffffffffffffffff
+        d.ids_base = self.streamline_id_base()
+        out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        hist = self._buf_streamlines
+        _lib.check(self._lib.ttl_act_flags(
+            C.byref(d), hist.data_ptr(), hist.stride(0), self._idx_view(n).data_ptr(),
+            self._init_len.data_ptr() if backward else None, n, int(n_points),
+            out.data_ptr(), None, self._stream()), 'ttl_act_flags')
+        return out
 
     def _oracle_reward(self, n, n_points, done, reward):
         """OracleReward.__call__ (oracle_reward.py:70-93): +oracle_bonus for the
@@ -523,10 +559,11 @@ class TrackingEnvironment(BaseEnv):
     def freerun_supported(self):
         """Whether ``run_free`` can take the episode from here: a batch of at
         most FREERUN_MAX rows between steps, no oracle criterion / bonus
-        (torch code between the step's launches), no Gaussian action noise
-        (drawn on the host per step) and no backward pass (``reset_backward``)."""
+        (torch code between the step's launches), no tissue-map criterion (a
+        host-issued launch between them), no Gaussian action noise (drawn on the
+        host per step) and no backward pass (``reset_backward``)."""
         return (self._pending is None and 1 <= self._n_active <= self.FREERUN_MAX
-                and self._init_len is None
+                and self._init_len is None and self._act_desc is None
                 and not self._use_oracle_stopping and not self._use_oracle_reward
                 and not self._has_action_noise()
                 and self.add_neighborhood_vox

@@ -94,15 +94,29 @@ def tract_survivors(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     return hist, sel, mask
 
 
+def _check_reject(reject, n):
+    if reject is not None and (reject.dtype is not torch.bool or tuple(reject.shape) != (n,)):
+        raise ValueError(f'reject must be a bool tensor of shape ({n},)')
+
+
+def _drop_rejected(sel, reject):
+    """Between ``tract_survivors`` and the scans: a rejected row keeps no point
+    and is not accepted (the emit kernels skip unaccepted rows)."""
+    if reject is not None:
+        sel.masked_fill_(reject.to(sel.device)[None, :], 0)
+
+
 def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
-                  max_segment_length=10.0):
+                  max_segment_length=10.0, reject=None):
     """The tracker's output stage over a finished batch: (n, T, 3) float32
     history + the env's int32 lengths / flags -> the streamlines whose arc
     length (voxels, float64) is in [min_arc, max_arc], compressed with
     ``tractogram.compress_streamline(s, tol_error, max_segment_length)`` when
     ``tol_error > 0``.  Returns (packed points (M, 3) f32, points per
     streamline (k,) i64, source rows (k,) i64) on the input's device, accepted
-    rows in row order.  On the GPU: ``ttl_tract_select`` (one wave per row:
+    rows in row order.  ``reject`` (n,) bool or None: rows dropped whatever
+    their length (the tissue-map filter of ``Tracker(act_filter=...)``).
+    On the GPU: ``ttl_tract_select`` (one wave per row:
     kept length, arc, accept, survivor bitmask), a prefix sum, then
     ``ttl_tract_emit`` (one wave per row: the pack); the largest allocation is
     the packed output.  Host tensors (the gloo tests) take the torch filter
@@ -110,13 +124,14 @@ def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     against."""
     n = int(history.shape[0])
     dev = history.device
+    _check_reject(reject, n)
     if n == 0:
         return (torch.zeros((0, 3), dtype=torch.float32, device=dev),
                 torch.zeros(0, dtype=torch.int64, device=dev),
                 torch.zeros(0, dtype=torch.int64, device=dev))
     if not history.is_cuda:
         return _select_tracts_host(history, lengths, flags, min_arc, max_arc,
-                                   tol_error, max_segment_length)
+                                   tol_error, max_segment_length, reject)
     import ctypes as C
     from tracktolearn_amd import _lib
     from tracktolearn_amd.environments.env import _raw_stream
@@ -124,6 +139,7 @@ def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     stream = C.c_void_p(_raw_stream(dev.index or 0))
     hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
                                       tol_error, max_segment_length)
+    _drop_rejected(sel, reject)
     pitch = hist.stride(0)
     # two 1-D scans: torch's scan along the inner dimension of a (2, n) tensor
     # takes 0.6 ms at n = 262 144, longer than both kernels together
@@ -143,10 +159,11 @@ def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
 
 
 def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=None,
-                       tol_error=0.0, max_segment_length=10.0):
+                       tol_error=0.0, max_segment_length=10.0, reject=None):
     """``select_tracts`` whose pack writes the batch's file body instead of the
     packed points: ``desc`` is an ``io.streamlines.BodyDesc``, ``seeds`` the
-    (n, 3) float64 seeds by input row (needed when ``desc.n_props == 3``).
+    (n, 3) float64 seeds by input row (needed when ``desc.n_props == 3``),
+    ``reject`` as for ``select_tracts``.
     Returns (words int32 -- the 4-byte words of the body, on the input's
     device --, accepted rows k, points M).  On the GPU the same
     ``ttl_tract_select``, scans and synchronising copy, then
@@ -157,11 +174,12 @@ def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=No
     dev = history.device
     if desc.n_props == 3 and seeds is None:
         raise ValueError('n_props == 3 needs the seeds')
+    _check_reject(reject, n)
     if n == 0:
         return torch.zeros(0, dtype=torch.int32, device=dev), 0, 0
     if not history.is_cuda:
         points, counts, rows = _select_tracts_host(history, lengths, flags, min_arc, max_arc,
-                                                   tol_error, max_segment_length)
+                                                   tol_error, max_segment_length, reject)
         kept = None if seeds is None else \
             np.asarray(seeds, dtype=np.float64).reshape(-1, 3)[rows.numpy()]
         words = packed_body(points.numpy(), counts.numpy(), kept, desc)
@@ -173,6 +191,7 @@ def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=No
     stream = C.c_void_p(_raw_stream(dev.index or 0))
     hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
                                       tol_error, max_segment_length)
+    _drop_rejected(sel, reject)
     ends = (torch.cumsum(sel[0], 0, dtype=torch.int64),
             torch.cumsum(sel[1], 0, dtype=torch.int64))
     total, k = torch.stack((ends[0][-1], ends[1][-1])).tolist()   # the one synchronising copy
@@ -194,7 +213,7 @@ def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=No
 
 
 def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
-                        max_segment_length):
+                        max_segment_length, reject=None):
     from tracktolearn_amd.tractogram import compress_streamline
     keep_len = kept_lengths(lengths, flags)
     seg = (history[:, 1:] - history[:, :-1]).double()
@@ -202,7 +221,10 @@ def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
     steps = torch.arange(seg_len.shape[1], device=history.device)
     valid = steps[None, :] < (keep_len - 1)[:, None]
     arc = (seg_len * valid).sum(dim=1)
-    rows = torch.nonzero((arc >= min_arc) & (arc <= max_arc)).squeeze(1)
+    ok = (arc >= min_arc) & (arc <= max_arc)
+    if reject is not None:
+        ok &= ~reject
+    rows = torch.nonzero(ok).squeeze(1)
     hist = history.numpy()
     lines = [hist[r, :k] for r, k in zip(rows.tolist(), keep_len[rows].tolist())]
     if tol_error > 0:

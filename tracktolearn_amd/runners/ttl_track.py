@@ -8,10 +8,19 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--max_length M] [--noise s] [--keyed_noise] [--fa_map F] [--bidirectional]
         [--binary_stopping_threshold t] [--rng_seed S] [--direct_output]
         [--odf_policy {det,prob}] [--theta DEG] [--sf_threshold R] [--step_size MM]
+        [--act_include FILE --act_exclude FILE] [--act_mode {act,cmc}]
+        [--act_filter {none,exclude,endpoints}]
 
 With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
 itself (classical deterministic / probabilistic tracking as one GPU kernel,
 tracking/odf_policy.py).
+
+With ``--act_include`` / ``--act_exclude`` (tissue maps on the grid of in_mask,
+e.g. grey matter and CSF) a streamline also ends where it reaches the include
+map -- validly -- or the exclude map -- it is then discarded (ACT), or with the
+per-step probabilities of CMC (``--act_mode cmc``).  in_mask should then be a
+brain mask (white and grey matter): a point that leaves in_mask in the step in
+which it reaches the include map is still dropped.
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -49,15 +58,20 @@ def per_rank_noise_rng(rng_seed, rank):
     return np.random.RandomState((int(rng_seed) + 1 + int(rank)) % (2 ** 32))
 
 
+def load_on_mask_grid(option, volume_file, in_mask):
+    """The volume of ``option`` (float64), which must be on the tracking mask's grid."""
+    vol = nifti.load(volume_file)
+    mask = nifti.load(in_mask)
+    if tuple(vol.shape[:3]) != tuple(mask.shape[:3]) or \
+            not np.allclose(vol.affine, mask.affine, atol=1e-3):
+        raise ValueError('{} {} is not on the grid of the tracking mask {}'.format(
+            option, volume_file, in_mask))
+    return np.asarray(vol.get_fdata(dtype=np.float64)).reshape(vol.shape[:3])
+
+
 def load_fa_map(fa_map_file, in_mask):
     """The FA volume of ``--fa_map`` (float64), on the tracking mask's grid."""
-    fa = nifti.load(fa_map_file)
-    mask = nifti.load(in_mask)
-    if tuple(fa.shape[:3]) != tuple(mask.shape[:3]) or \
-            not np.allclose(fa.affine, mask.affine, atol=1e-3):
-        raise ValueError('--fa_map {} is not on the grid of the tracking mask {}'.format(
-            fa_map_file, in_mask))
-    return np.asarray(fa.get_fdata(dtype=np.float64)).reshape(fa.shape[:3])
+    return load_on_mask_grid('--fa_map', fa_map_file, in_mask)
 
 
 #: track_dto keys copied onto the experiment as they are (argparse names)
@@ -92,6 +106,13 @@ class TrackToLearnTrack(object):
         self.fa_map_file = track_dto.get('fa_map')
         self.keyed_noise = bool(track_dto.get('keyed_noise')) or bool(self.fa_map_file)
         self.bidirectional = bool(track_dto.get('bidirectional'))
+        # tissue maps: ACT / CMC stopping and the filter of the output stage
+        self.act_include_file = track_dto.get('act_include')
+        self.act_exclude_file = track_dto.get('act_exclude')
+        self.act_mode = track_dto.get('act_mode') or 'act'
+        self.act_filter = track_dto.get('act_filter') or 'exclude'
+        if not self.act_include_file:
+            self.act_filter = None
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -144,6 +165,13 @@ class TrackToLearnTrack(object):
             env_dto.update(device_noise='keyed', noise_seed=self.random_seed)
         if self.fa_map_file:
             env_dto['fa_map'] = load_fa_map(self.fa_map_file, self.in_mask)
+        if self.act_include_file:
+            env_dto.update(
+                act_include=load_on_mask_grid('--act_include', self.act_include_file,
+                                              self.in_mask),
+                act_exclude=load_on_mask_grid('--act_exclude', self.act_exclude_file,
+                                              self.in_mask),
+                act_mode=self.act_mode, act_seed=self.random_seed)
         return NoisyTrackingEnvironment.from_files(env_dto)
 
     def _step_for_subject(self, subject_voxel_size):
@@ -182,7 +210,8 @@ class TrackToLearnTrack(object):
         alg = self._load_policy(env)
         tracker = Tracker(alg, self.n_actor, compress=self.compress,
                           min_length=self.min_length, max_length=self.max_length,
-                          save_seeds=self.save_seeds, bidirectional=self.bidirectional)
+                          save_seeds=self.save_seeds, bidirectional=self.bidirectional,
+                          act_filter=self.act_filter)
         # re-derives the step in voxels, the step counts and the neighbourhood
         # radius from the rescaled step (environments/env.py:196-212)
         env.load_subject()
@@ -307,6 +336,26 @@ def add_track_args(parser):
                             'function\'s maximum are not followed. [0.1]')
     odf_g.add_argument('--step_size', type=float, default=None, metavar='MM',
                        help='Step size in mm. [0.75]')
+    act_g = parser.add_argument_group(
+        'Anatomically constrained tracking',
+        'Stop on tissue maps (on the grid of in_mask), as ACT / CMC do. in_mask '
+        'should then be\na brain mask (white and grey matter).')
+    act_g.add_argument('--act_include', type=str, default=None, metavar='FILE',
+                       help='Map (.nii.gz) in which a streamline ends validly, e.g. '
+                            'grey matter.')
+    act_g.add_argument('--act_exclude', type=str, default=None, metavar='FILE',
+                       help='Map (.nii.gz) in which a streamline ends invalidly, '
+                            'e.g. CSF.')
+    act_g.add_argument('--act_mode', choices=['act', 'cmc'], default=None,
+                       help='act: stop where a map exceeds 0.5, include first; cmc: '
+                            'stop with the\nper-step probabilities of continuous map '
+                            'criterion, as a function of\n(--rng_seed, seed index, '
+                            'step). [act]')
+    act_g.add_argument('--act_filter', choices=['none', 'exclude', 'endpoints'],
+                       default=None,
+                       help='exclude: discard streamlines the exclude map ended; '
+                            'endpoints: also those\nwith an end outside the include '
+                            'map; none: keep all. [exclude]')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -340,6 +389,19 @@ def parse_args(argv=None):
         parser.error('min_length must be >= 0 and <= max_length.')
     if args.compress is not None and not 0.001 <= args.compress <= 1:
         parser.error('The compression threshold must be in [0.001, 1] mm.')
+    if (args.act_include is None) != (args.act_exclude is None):
+        parser.error('--act_include and --act_exclude go together.')
+    if args.act_include is None:
+        for name in ('act_mode', 'act_filter'):
+            if getattr(args, name) is not None:
+                parser.error('--{} is used only with --act_include / --act_exclude.'
+                             .format(name))
+    else:
+        for f in (args.act_include, args.act_exclude):
+            if not os.path.isfile(f):
+                parser.error('Input file {} does not exist.'.format(f))
+        args.act_mode = args.act_mode or 'act'
+        args.act_filter = args.act_filter or 'exclude'
     if args.odf_policy:
         if args.agent is not None or args.hyperparameters is not None:
             parser.error('--odf_policy tracks without an agent: drop --agent / '

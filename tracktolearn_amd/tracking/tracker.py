@@ -64,7 +64,7 @@ class Tracker(object):
 
     def __init__(self, alg, n_actor, prob=0., compress=0.0, min_length=20,
                  max_length=200, save_seeds=False, device_output=None,
-                 bidirectional=False):
+                 bidirectional=False, act_filter=None):
         self.alg = alg
         self.n_actor = n_actor
         self.prob = prob
@@ -77,6 +77,15 @@ class Tracker(object):
         #: so that a streamline runs through its seed instead of starting there
         #: (never while training)
         self.bidirectional = bool(bidirectional)
+        #: with tissue maps in the env (ACT / CMC stopping): None keeps every
+        #: streamline, 'exclude' drops those the exclude map ended at either end,
+        #: 'endpoints' additionally wants every tracked half ended by the include map
+        if act_filter == 'none':
+            act_filter = None
+        if act_filter not in (None, 'exclude', 'endpoints'):
+            raise ValueError(f"act_filter must be None, 'exclude' or 'endpoints', "
+                             f'not {act_filter!r}')
+        self.act_filter = act_filter
         #: filter + compression + pack by the HIP output stage; None: whenever
         #: the env's buffers are on the GPU.  False: the host path
         self.device_output = device_output
@@ -93,6 +102,26 @@ class Tracker(object):
             return bool(env._buf_streamlines.is_cuda)
         return bool(self.device_output)
 
+    def _act_reject(self, env):
+        """(n,) bool on the env's device: the rows of the finished batch that
+        ``act_filter`` drops, from the flags the batch ended with and, after a
+        backward pass, those its forward pass ended with.  None: no filter."""
+        n = env._n_total
+        if self.act_filter is None or n == 0:
+            return None
+        from tracktolearn_amd.environments.stopping_criteria import (
+            ACT_EXCLUDE_FLAG, StoppingFlags)
+        target = StoppingFlags.STOPPING_TARGET.value
+        ends = [env._buf_flags[:n]]
+        if env.flags_forward is not None:
+            ends.append(env.flags_forward[:n])
+        reject = torch.zeros(n, dtype=torch.bool, device=ends[0].device)
+        for flags in ends:
+            reject |= (flags & ACT_EXCLUDE_FLAG) != 0
+            if self.act_filter == 'endpoints':
+                reject |= (flags & target) == 0
+        return reject
+
     def _batch_arrays(self, env, scaled_min, scaled_max, tol_vox=0.0):
         """Streamlines of the finished batch whose arc length (voxels) is in
         [scaled_min, scaled_max] (the filter of tracker.py:120-121), compressed
@@ -104,7 +133,7 @@ class Tracker(object):
         n = env._n_total
         points, counts, rows = select_tracts(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
-            scaled_min, scaled_max, tol_vox)
+            scaled_min, scaled_max, tol_vox, reject=self._act_reject(env))
         if n == 0:              # an empty shard of a sharded batch
             seeds = np.zeros((0, 3), dtype=np.float64)
         else:
@@ -131,6 +160,9 @@ class Tracker(object):
         valid = steps[None, :] < (keep_len - 1)[:, None]
         arc = (seg_len * valid).sum(dim=1)
         ok = (arc >= scaled_min) & (arc <= scaled_max)
+        reject = self._act_reject(env)
+        if reject is not None:
+            ok &= ~reject
         sel = torch.nonzero(ok).squeeze(1)
         keep_sel = keep_len[sel]
         points = pack_points(hist[sel], keep_sel)
@@ -293,7 +325,8 @@ class Tracker(object):
         words, k, _ = select_tracts_file(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
             self.min_length / vox_size, self.max_length / vox_size, desc, seeds,
-            tol_error=self.compress / vox_size if self.compress else 0.0)
+            tol_error=self.compress / vox_size if self.compress else 0.0,
+            reject=self._act_reject(env))
         if self.group_size > 1:
             from tracktolearn_amd.parallel import (all_gather_counts,
                                                    gather_ragged_to_root)
