@@ -14,10 +14,15 @@ One JSON line per measurement:
 ``act_tracking``  ``Tracker.track`` of one seed batch with ``OdfTracking('det')``
     and with a SAC ``64-64`` network of random weights (a policy cheap enough for
     the loop to be bound by its launches) on utils/synthetic.py's volume (D^3 x 45
-    SH, step 0.75 mm), three ways, interleaved: without tissue maps and
+    SH, step 0.75 mm), five ways, interleaved: without tissue maps and
     free-running (the graphed loop), without tissue maps step by step
-    (``TTL_GRAPH_EPISODE=0``), and with tissue maps (step by step by necessity).  Third minus second is what ACT itself costs;
-    second minus first is what a free-running ACT step would win back.
+    (``TTL_GRAPH_EPISODE=0``), with tissue maps between the two halves of the
+    step (``ttl_act_flags``; step by step by necessity), with tissue maps in the
+    step (``env_dto['act_in_step']``, ``ttl_env_set_act``) step by step, and with
+    tissue maps in the step graphed.  Third minus second is what ACT itself
+    costs outside the step, fourth minus second inside it; fifth against first is
+    what the graphed loop pays for the maps, fifth against third what putting
+    them into the step wins.
 """
 import argparse
 import ctypes as C
@@ -134,7 +139,7 @@ def kernel_rows(rows, D, reps):
                 'device': torch.cuda.get_device_name(0)}), flush=True)
 
 
-def make_env(D, N, maps=None):
+def make_env(D, N, maps=None, in_step=False):
     """bench_odf_policy.py's env, with tissue maps on request."""
     from tracktolearn_amd.environments import NoisyTrackingEnvironment
     from tracktolearn_amd.utils.synthetic import synthetic_seeds, synthetic_subject
@@ -144,7 +149,8 @@ def make_env(D, N, maps=None):
                oracle_bonus=0.0, rng=np.random.RandomState(0), device=DEV, target_sh_order=8,
                noise=0.0, fa_map=None)
     if maps is not None:
-        dto.update(act_include=maps[0], act_exclude=maps[1], act_mode='act', act_seed=1)
+        dto.update(act_include=maps[0], act_exclude=maps[1], act_mode='act', act_seed=1,
+                   act_in_step=in_step)
     env = NoisyTrackingEnvironment(subject, 'testing', dto)
     env.seeds = synthetic_seeds(subject[1].data, N, seed=100)
     return env
@@ -169,19 +175,22 @@ def tracking_rows(D, track_rows, reps):
     from tracktolearn_amd.tracking.odf_policy import OdfTracking
     maps = tissue_maps(D)
     for N in track_rows:
-        plain, act = make_env(D, N), make_env(D, N, maps)
+        plain, act, instep = make_env(D, N), make_env(D, N, maps), make_env(D, N, maps, True)
         seeds = plain.seeds.copy()
         torch.manual_seed(0)
         # the fODF policy, whose kernel bounds a step at this size, and a network
         # small enough for the loop to be bound by its launches (random weights)
         small = SACAuto(plain.get_state_size(), 3, '64-64', n_actors=N, rng=None, device=DEV)
         small.graph_policy_us = 1e9         # the graph whenever the env allows it
-        for policy, on_plain, on_act in (
-                ('odf_det', OdfTracking(plain, 'det', seed=1), OdfTracking(act, 'det', seed=1)),
-                ('64-64', small, small)):
+        for policy, on_plain, on_act, on_instep in (
+                ('odf_det', OdfTracking(plain, 'det', seed=1), OdfTracking(act, 'det', seed=1),
+                 OdfTracking(instep, 'det', seed=1)),
+                ('64-64', small, small, small)):
             legs = [('plain_freerun', plain, on_plain, True, None),
                     ('plain_stepwise', plain, on_plain, False, None),
-                    ('act_stepwise', act, on_act, True, 'exclude')]
+                    ('act_stepwise', act, on_act, True, 'exclude'),
+                    ('act_instep_stepwise', instep, on_instep, False, 'exclude'),
+                    ('act_instep_freerun', instep, on_instep, True, 'exclude')]
             runs = {name: [] for name, *_ in legs}
             for rep in range(reps + 1):         # interleaved; the first round warms up
                 for name, env, alg, graph, act_filter in legs:

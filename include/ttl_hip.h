@@ -614,6 +614,41 @@ TTL_API int ttl_act_flags(const ttl_act_desc *desc, const float *history, int64_
                           int32_t n_points, uint8_t *flags_out, double *values_out,
                           void *hip_stream);
 
+/* The same criterion inside the step (TTL_HAS_ACT_IN_STEP): installed on
+ * the handle once, as keyed noise is (ttl_env_set_noise), and applied in-stream by
+ * every flavour of the step -- ttl_env_step, ttl_env_step_begin / _end,
+ * ttl_env_freerun_step, a graph captured from it, a backward pass -- with no host in
+ * between.  The descriptor is copied; the two maps are BORROWED until the next
+ * ttl_env_set_act or ttl_env_destroy.  ttl_env_set_act(env, NULL) switches it off.
+ * With a criterion installed, a step that finds the batch at length L leaves every
+ * buffer of the handle and every output -- flags, dones, lengths, stop, done_out,
+ * reward_out, continue_idx after the harvest, the state rows and their order,
+ * host_counts -- exactly as this sequence leaves them:
+ *   ttl_env_step_begin;
+ *   ttl_act_flags(desc, history, pitch, ids = the live continue_idx, init_len = the
+ *                 handle's in retrack mode else NULL, n = n_active, n_points = L + 1);
+ *   ttl_env_step_end(extra_flags = those bits).
+ * A row that another criterion stopped as well keeps those bits and gets the new ones
+ * (the rule of ttl_env_step_end's extra_flags); rows beyond n_active are not judged;
+ * extra_flags given to ttl_env_step_end are OR-ed on top as without a criterion.  The
+ * criterion is applied by ttl_env_step_begin (one launch behind the one that moves the
+ * points: done_out is final for it when that call's launches have run).
+ * Free-running: n_active, L and the live continue_idx buffer are those the step's
+ * first kernel snapshots; a step launched for fewer rows than are active judges
+ * nothing.  ttl_env_freerun_begin leaves the criterion of the episode -- maps, mode,
+ * exponent, seed, ids_base, or "none" -- in device memory of the handle, where the
+ * step reads it: a graph captured from ttl_env_freerun_step with a criterion installed
+ * stays valid when ttl_env_set_act is called again between episodes, with other values
+ * or with NULL (its hook then changes nothing).  A graph captured with NO criterion
+ * installed holds no hook and does not apply one installed later: capture again.
+ * With nothing installed every entry point issues the launches it issued before.
+ * TTL_ERR_INVALID as ttl_act_flags refuses a descriptor (a null map, a dim < 1, an
+ * unknown mode, ids_base < 0, in CMC mode an exponent not finite and positive);
+ * TTL_ERR_STATE between a step and its harvest and while free-running; a refused call
+ * leaves the installed criterion as it was.  Host state only: no device work. */
+#define TTL_HAS_ACT_IN_STEP 1
+TTL_API int ttl_env_set_act(ttl_env *env, const ttl_act_desc *desc);
+
 /* fODF peaks of an SH volume (replaces the per-voxel Python loop of
  * TrackToLearn/environments/env.py:405-432: sh_to_sf_matrix + get_maximas per
  * voxel, 5 peaks scaled by value / first value).  sh: [n_voxels][n_coef] f32;

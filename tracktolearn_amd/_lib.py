@@ -35,6 +35,7 @@ ODF_MAX_COEF, ODF_GRID_CAP = 64, 1024   # TTL_ODF_MAX_COEF / TTL_ODF_GRID_CAP
 FLAG_TARGET, FLAG_EXCLUDE = 8, 128      # TTL_FLAG_TARGET / TTL_FLAG_EXCLUDE
 ACT_THRESHOLD, ACT_CMC = 0, 1           # TTL_ACT_THRESHOLD / TTL_ACT_CMC
 ACT_STREAM = 0x41435420                 # TTL_ACT_STREAM
+HAS_ACT_IN_STEP = 1                     # TTL_HAS_ACT_IN_STEP (ttl_env_set_act)
 
 
 class TTLError(RuntimeError):
@@ -227,6 +228,7 @@ SYMBOLS = {
     'ttl_act_flags': (C.c_int, [C.POINTER(ActDesc), C.c_void_p, C.c_int64, C.c_void_p,
                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p]),
+    'ttl_env_set_act': (C.c_int, [C.c_void_p, C.POINTER(ActDesc)]),
     'ttl_peaks_from_sh': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.c_float, C.c_float,

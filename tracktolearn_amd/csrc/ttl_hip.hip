@@ -323,37 +323,6 @@ __device__ __forceinline__ int stopping_bits(
     return bits;
 }
 
-// Stable survivor ranks of one 256-thread block: 64-bit ballot per wavefront,
-// popcount of the lanes below, then the 4 wave totals through LDS.  Writes
-// rank[i] (survivors before row i inside the block) and the block's count.
-__device__ __forceinline__ void block_ranks(int *__restrict__ rank_out,
-                                            int *__restrict__ counts_out, int i,
-                                            bool active, bool keep) {
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    __shared__ int wave_total[BLOCK / 64];
-    if (lane == 0) wave_total[wave] = __popcll(m);
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w)
-        if (w < wave) before += wave_total[w];
-    if (active) rank_out[i] = before + below;
-    if (threadIdx.x == 0) {
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < BLOCK / 64; ++w) tot += wave_total[w];
-        counts_out[blockIdx.x] = tot;
-    }
-}
-
-__device__ __forceinline__ void block_survivor_ranks(const EnvParams &P, int i,
-                                                     bool active, bool keep) {
-    block_ranks(P.rank, P.block_counts, i, active, keep);
-}
-
 // low 6 bits of v spread to every third bit (Morton interleave helper)
 __device__ __forceinline__ unsigned spread3(unsigned v) {
     v &= 63u;
@@ -1400,6 +1369,10 @@ struct ttl_env {
     int *fr_host_word = nullptr;  // device address of the pinned words a free-running step reports to
     int keyed = 0;             // ttl_env_set_noise: the steps draw their noise themselves ...
     NoiseParams noise{};       // ... from this
+    int act_on = 0;            // ttl_env_set_act: every step applies the tissue-map criterion ...
+    ActCrit act{};             // ... this one, behind its k_advance*
+    ActRecord *act_rec = nullptr;  // workspace: the criterion as free-running steps read it
+    int act_rec_on = 0;        // *act_rec says "on" (written by the last ttl_env_freerun_begin)
     int n_total = 0;           // rows of the last reset
     const int *init_len = nullptr;  // ttl_env_reset_backward: a backward pass is on, rows replay while
                                     // the length is below init_len[g]; null otherwise
@@ -1482,8 +1455,14 @@ static size_t ttl_env_carve(ttl_env &e, size_t n, void *base) {
     rows(P.stop_list, n, 2 * sizeof(int));
     rows(P.slot_dest, n, sizeof(int));
     rows(P.counts, 64, sizeof(int));
-    e.order_ws_bytes = ttl_detail_order_workspace_bytes(n);
-    rows(e.order_ws, e.order_ws_bytes, 1, 1);       // (as long as ttl_order.hip asks, unrounded)
+    // (as long as ttl_order.hip asks, unrounded; the last 256 bytes of its 4 MiB
+    // margin, 8-byte aligned, hold the tissue-map record of free-running steps:
+    // the size callers allocate for a handle stays what it was)
+    const size_t order_bytes = ttl_detail_order_workspace_bytes(n);
+    static_assert(sizeof(ActRecord) <= 256 && alignof(ActRecord) <= 8, "see above");
+    e.order_ws_bytes = order_bytes - 256;
+    rows(e.order_ws, order_bytes, 1, 1);
+    e.act_rec = e.order_ws ? reinterpret_cast<ActRecord *>(e.order_ws + e.order_ws_bytes) : nullptr;
     rows(e.ord_rec, n, sizeof(int2));
     rows(e.ord_count[0], 1, ttl_detail_order_instep_count_bytes());
     rows(e.ord_count[1], 1, ttl_detail_order_instep_count_bytes());
@@ -2005,6 +1984,10 @@ int ttl_env_step_begin(ttl_env *env, const float *actions, const double *noise,
     });
     prof_mark(env, 0, 1, s);
     HIP_TRY(hipGetLastError());
+    if (env->act_on)
+        if (const int rc = ttl_detail_launch_act_step(env->P, env->act, env->init_len, n_active,
+                                                      L + 1, done_out, s))
+            return rc;
     env->length = L + 1;
     env->stepped = 2;          // advanced, not yet committed
     env->last_n = n_active;
@@ -2414,6 +2397,15 @@ int ttl_env_freerun_begin(ttl_env *env, int32_t *host_counts, void *hip_stream) 
         hipLaunchKernelGGL(k_fr_noise, dim3(1), dim3(1), 0, s, env->P, env->noise);
         HIP_TRY(hipGetLastError());
     }
+    // the tissue-map criterion of this episode; "off" is written only over an
+    // "on" (a graph captured then still holds the hook): a handle that never
+    // had a criterion launches nothing here
+    if (env->act_on || env->act_rec_on) {
+        if (const int rc = ttl_detail_launch_act_record(env->act_rec,
+                                                        env->act_on ? &env->act : nullptr, s))
+            return rc;
+        env->act_rec_on = env->act_on;
+    }
     order_dropped(env);
     env->counts_pending = 0;
     env->fr_cap = env->n_active;
@@ -2443,6 +2435,9 @@ int ttl_env_freerun_step(ttl_env *env, const float *actions, int32_t n_rows, flo
                            done_out);
     });
     HIP_TRY(hipGetLastError());
+    if (env->act_on)
+        if (const int rc = ttl_detail_launch_act_step_fr(env->P, env->act_rec, n_cap, done_out, s))
+            return rc;
     return ttl_detail_launch_fused_tail_fr(env->P, d.idx_a, d.idx_b, n_cap, state_out,
                                            state_pitch, env->fr_host_word, s);
 }
@@ -2532,6 +2527,24 @@ int ttl_env_set_noise(ttl_env *env, const ttl_noise_desc *desc) {
         for (int a = 0; a < 3; ++a) env->noise.fa_dim[a] = desc->fa_coef ? desc->fa_dim[a] : 0;
         env->noise.noise_out = desc->noise_out;
     }
+    return TTL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The tissue-map criterion inside the step: host state only, the kernels are
+// in ttl_act.hip (launched by ttl_env_step_begin / ttl_env_freerun_step).
+// ---------------------------------------------------------------------------
+int ttl_env_set_act(ttl_env *env, const ttl_act_desc *desc) {
+    if (!env) return fail(TTL_ERR_INVALID, "ttl_env_set_act: null handle");
+    if (desc)
+        if (const int rc = ttl_detail_act_check(desc, "ttl_env_set_act")) return rc;
+    if (env->stepped)
+        return fail(TTL_ERR_STATE, "ttl_env_set_act: harvest the pending step first");
+    if (env->fr_cap)
+        return fail(TTL_ERR_STATE, "ttl_env_set_act: free-running steps are enqueued, call "
+                                   "ttl_env_freerun_end first");
+    env->act_on = desc != nullptr;
+    env->act = desc ? ttl_detail_act_crit(*desc) : ActCrit{};
     return TTL_OK;
 }
 

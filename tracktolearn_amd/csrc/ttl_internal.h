@@ -177,6 +177,37 @@ __device__ __forceinline__ void step_publish_counts(const EnvParams &P, int tota
     }
 }
 
+// Stable survivor ranks of one 256-thread block: 64-bit ballot per wavefront,
+// popcount of the lanes below, then the 4 wave totals through LDS.  Writes
+// rank[i] (survivors before row i inside the block) and the block's count.
+__device__ __forceinline__ void block_ranks(int *__restrict__ rank_out,
+                                            int *__restrict__ counts_out, int i,
+                                            bool active, bool keep) {
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int below = __popcll(m & ((1ull << lane) - 1ull));
+    __shared__ int wave_total[TTL_BLOCK / 64];
+    if (lane == 0) wave_total[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0;
+#pragma unroll
+    for (int w = 0; w < TTL_BLOCK / 64; ++w)
+        if (w < wave) before += wave_total[w];
+    if (active) rank_out[i] = before + below;
+    if (threadIdx.x == 0) {
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < TTL_BLOCK / 64; ++w) tot += wave_total[w];
+        counts_out[blockIdx.x] = tot;
+    }
+}
+
+__device__ __forceinline__ void block_survivor_ranks(const EnvParams &P, int i,
+                                                     bool active, bool keep) {
+    block_ranks(P.rank, P.block_counts, i, active, keep);
+}
+
 // ---------------------------------------------------------------------------
 // One wavefront per row (ttl_resample.hip, ttl_coverage.hip, ttl_peaks.hip,
 // ttl_tract.hip): the lanes of a wave hand values to each other through LDS
@@ -508,6 +539,46 @@ int ttl_detail_launch_fused_tail(const EnvParams &P, const int *idx, int *idx_ne
 int ttl_detail_launch_fused_tail_fr(const EnvParams &P, int *idx_a, int *idx_b, int n_cap,
                                     float *out, int64_t pitch, int *host_word,
                                     hipStream_t s);
+// ---------------------------------------------------------------------------
+// The tissue-map criterion inside the step (ttl_env_set_act; ttl_act.hip).
+// ---------------------------------------------------------------------------
+// ttl_act_desc as the kernels receive it
+struct ActCrit {
+    const float *include, *exclude;
+    int dim[3];
+    int mode;
+    double shift, exponent;
+    unsigned long long seed;
+    long long ids_base;
+};
+// The criterion of a free-running episode, in workspace memory of the handle:
+// written by ttl_env_freerun_begin, read by every free-running step -- device
+// memory, not a kernel argument, so that a captured step stays valid when the
+// next batch brings another seed or ids_base, or switches the criterion off
+// (on == 0: the step's hook changes nothing)
+struct ActRecord {
+    ActCrit crit;
+    int on;
+};
+// the refusals ttl_act_flags and ttl_env_set_act share (TTL_ERR_INVALID): a null
+// descriptor or map, a dim < 1, an unknown mode, a negative ids_base, in CMC mode
+// an exponent that is not finite and positive
+int ttl_detail_act_check(const ttl_act_desc *desc, const char *who);
+ActCrit ttl_detail_act_crit(const ttl_act_desc &desc);
+// The hook of a host-stepped step, behind k_advance / k_advance_retrack on their
+// grid: judges the newest point (point n_points - 1, in P.head) of the n_active
+// rows, ORs the bits into the step's decisions by k_restop's rule and redoes the
+// block ranks.  init_len: the handle's in a backward pass, else null
+int ttl_detail_launch_act_step(const EnvParams &P, const ActCrit &crit, const int *init_len,
+                               int n_active, int n_points, uint8_t *done_out, hipStream_t s);
+// The same behind k_advance_fr, on its grid of n_cap rows: the criterion comes
+// from *rec, the row count and the length from P.counts + TTL_FR_SNAP; a record
+// that is off or a step the snapshot marks as skipped judges nothing
+int ttl_detail_launch_act_step_fr(const EnvParams &P, const ActRecord *rec, int n_cap,
+                                  uint8_t *done_out, hipStream_t s);
+// one-thread launch: *rec = {*crit, on} (crit == null: off)
+int ttl_detail_launch_act_record(ActRecord *rec, const ActCrit *crit, hipStream_t s);
+
 // ttl_order.hip: rows 0..n-1 sorted by the 8^3-voxel brick of their newest
 // point (P.last2 of streamline idx[row]) -> order_out[n]; ws = scratch of
 // ttl_detail_order_workspace_bytes(n_max) bytes

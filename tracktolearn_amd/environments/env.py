@@ -157,6 +157,13 @@ class BaseEnv(object):
         if self.act_mode not in ('act', 'cmc'):
             raise ValueError(f"act_mode must be 'act' or 'cmc', not {self.act_mode!r}")
         self.act_seed = int(env_dto.get('act_seed') or 0)
+        #: the criterion is installed on the handle (``ttl_env_set_act``) and applied
+        #: by the step's own launches, free-running and graphed ones included; False:
+        #: ``ttl_act_flags`` between the two halves of every step
+        self.act_in_step = bool(env_dto.get('act_in_step', False))
+        if self.act_in_step and self._act_include_host is None:
+            raise ValueError("env_dto['act_in_step'] needs env_dto['act_include'] / "
+                             "['act_exclude']")
 
         self._device_index = self.device.index if self.device.index is not None \
             else (torch.cuda.current_device() if self.device.type == 'cuda' else 0)

@@ -167,6 +167,7 @@ class TrackingEnvironment(BaseEnv):
             _lib.ORDER_BY_POSITION if self._sorts_rows(n) else None, state.data_ptr(),
             self._state_pitch, self._stream()), 'ttl_env_reset')
         self._forward_pass_armed(n)
+        self._install_act()
         return state
 
     def reset_backward(self):
@@ -191,6 +192,7 @@ class TrackingEnvironment(BaseEnv):
             _lib.ORDER_BY_POSITION if self._sorts_rows(n) else None, state.data_ptr(),
             self._state_pitch, self._stream()), 'ttl_env_reset_backward')
         self._backward_pass_armed(init_len, flags_forward)
+        self._install_act()
         return state
 
     def _refresh_processing_order(self, force=False):
@@ -310,7 +312,8 @@ class TrackingEnvironment(BaseEnv):
             reward = torch.empty(n, dtype=torch.float64, device=self.device)
         noise_ptr = noise.data_ptr() if noise is not None else None
         reward_ptr = reward.data_ptr() if reward is not None else None
-        use_act = self._act_desc is not None
+        # (tissue maps in the step, act_in_step: the handle applies them itself)
+        use_act = self._act_desc is not None and not self.act_in_step
         early = host_outputs and not self._use_oracle_stopping and \
             not self._use_oracle_reward and not use_act
         if not early and not self._use_oracle_stopping and not use_act:
@@ -389,13 +392,9 @@ class TrackingEnvironment(BaseEnv):
     #: the keyed noise and the fODF policy do
     BACKWARD_SEED_XOR = 0x9E3779B97F4A7C15
 
-    def act_flags(self, n, n_points):
-        """The tissue-map criterion on the newest of the ``n_points`` points of
-        the ``n`` active rows: uint8 (n,) with ``STOPPING_TARGET`` where the
-        include map ends a row and ``ACT_EXCLUDE_FLAG`` where the exclude map
-        does.  In a backward pass only points the pass itself created are
-        judged.  The CMC draw is keyed by (``act_seed``, global index of the
-        streamline's seed, n_points): independent of the batching."""
+    def _act_desc_now(self):
+        """The criterion's descriptor for the pass the batch is in: the exponent
+        of the current step size, the pass's seed, the batch's id base."""
         d = self._act_desc
         if d is None:
             raise RuntimeError("no tissue maps: env_dto['act_include'] / ['act_exclude']")
@@ -404,6 +403,27 @@ class TrackingEnvironment(BaseEnv):
         d.seed = (self.act_seed ^ (self.BACKWARD_SEED_XOR if backward else 0)) & \
             0xffffffffffffffff
         d.ids_base = self.streamline_id_base()
+        return d
+
+    def _install_act(self):
+        """``act_in_step``: tell the handle what to judge this pass by
+        (``ttl_env_set_act``), at every reset and ``reset_backward`` -- the id
+        base changes per batch, the seed per pass; a changed step size (the
+        exponent) rebuilds the handle, so the next reset brings it.  In a
+        backward pass the handle uses its own ``init_len``."""
+        if self.act_in_step:
+            _lib.check(self._lib.ttl_env_set_act(self._handle, C.byref(self._act_desc_now())),
+                       'ttl_env_set_act')
+
+    def act_flags(self, n, n_points):
+        """The tissue-map criterion on the newest of the ``n_points`` points of
+        the ``n`` active rows: uint8 (n,) with ``STOPPING_TARGET`` where the
+        include map ends a row and ``ACT_EXCLUDE_FLAG`` where the exclude map
+        does.  In a backward pass only points the pass itself created are
+        judged.  The CMC draw is keyed by (``act_seed``, global index of the
+        streamline's seed, n_points): independent of the batching."""
+        d = self._act_desc_now()
+        backward = self._init_len is not None
         out = torch.empty(n, dtype=torch.uint8, device=self.device)
         hist = self._buf_streamlines
         _lib.check(self._lib.ttl_act_flags(
@@ -559,11 +579,13 @@ class TrackingEnvironment(BaseEnv):
     def freerun_supported(self):
         """Whether ``run_free`` can take the episode from here: a batch of at
         most FREERUN_MAX rows between steps, no oracle criterion / bonus
-        (torch code between the step's launches), no tissue-map criterion (a
-        host-issued launch between them), no Gaussian action noise (drawn on the
-        host per step) and no backward pass (``reset_backward``)."""
+        (torch code between the step's launches), no tissue-map criterion
+        outside the step (a host-issued launch between them; ``act_in_step``
+        puts it inside), no Gaussian action noise (drawn on the host per step)
+        and no backward pass (``reset_backward``)."""
         return (self._pending is None and 1 <= self._n_active <= self.FREERUN_MAX
-                and self._init_len is None and self._act_desc is None
+                and self._init_len is None
+                and (self._act_desc is None or self.act_in_step)
                 and not self._use_oracle_stopping and not self._use_oracle_reward
                 and not self._has_action_noise()
                 and self.add_neighborhood_vox

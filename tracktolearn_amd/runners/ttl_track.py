@@ -9,7 +9,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--binary_stopping_threshold t] [--rng_seed S] [--direct_output]
         [--odf_policy {det,prob}] [--theta DEG] [--sf_threshold R] [--step_size MM]
         [--act_include FILE --act_exclude FILE] [--act_mode {act,cmc}]
-        [--act_filter {none,exclude,endpoints}]
+        [--act_filter {none,exclude,endpoints}] [--act_in_step]
 
 With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
 itself (classical deterministic / probabilistic tracking as one GPU kernel,
@@ -20,7 +20,9 @@ e.g. grey matter and CSF) a streamline also ends where it reaches the include
 map -- validly -- or the exclude map -- it is then discarded (ACT), or with the
 per-step probabilities of CMC (``--act_mode cmc``).  in_mask should then be a
 brain mask (white and grey matter): a point that leaves in_mask in the step in
-which it reaches the include map is still dropped.
+which it reaches the include map is still dropped.  ``--act_in_step`` has the
+step's own launches apply the maps (``ttl_env_set_act``): the same tractogram,
+byte for byte, with the graphed tracking loop.
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -113,6 +115,7 @@ class TrackToLearnTrack(object):
         self.act_filter = track_dto.get('act_filter') or 'exclude'
         if not self.act_include_file:
             self.act_filter = None
+        self.act_in_step = bool(track_dto.get('act_in_step')) and bool(self.act_include_file)
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -171,7 +174,8 @@ class TrackToLearnTrack(object):
                                               self.in_mask),
                 act_exclude=load_on_mask_grid('--act_exclude', self.act_exclude_file,
                                               self.in_mask),
-                act_mode=self.act_mode, act_seed=self.random_seed)
+                act_mode=self.act_mode, act_seed=self.random_seed,
+                act_in_step=self.act_in_step)
         return NoisyTrackingEnvironment.from_files(env_dto)
 
     def _step_for_subject(self, subject_voxel_size):
@@ -356,6 +360,10 @@ def add_track_args(parser):
                        help='exclude: discard streamlines the exclude map ended; '
                             'endpoints: also those\nwith an end outside the include '
                             'map; none: keep all. [exclude]')
+    act_g.add_argument('--act_in_step', action='store_true',
+                       help='Apply the maps inside the tracking step instead of '
+                            'between its two halves:\nthe same streamlines, and the '
+                            'graphed tracking loop stays available.')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -396,6 +404,8 @@ def parse_args(argv=None):
             if getattr(args, name) is not None:
                 parser.error('--{} is used only with --act_include / --act_exclude.'
                              .format(name))
+        if args.act_in_step:
+            parser.error('--act_in_step is used only with --act_include / --act_exclude.')
     else:
         for f in (args.act_include, args.act_exclude):
             if not os.path.isfile(f):
