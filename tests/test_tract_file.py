@@ -457,6 +457,97 @@ def test_degenerate_batches_give_empty_bodies_and_bad_descriptors_are_refused():
     assert bool((out == SENTINEL).all())
 
 
+def walk_rows(T=130):
+    """Hand-written survivor masks for the walk the two emit kernels share:
+    (mask (9, T) bool, accepted (9,) bool).  T = 130 is three mask words, nine
+    rows are three blocks, the last with a single wave."""
+    j = np.arange(T)
+    every_word = j % 3 != 0                     # bit 0 of word 0, bit 2 of word 1 are clear
+    every_word[128:] = (False, True)            # word 2 = 0b10
+    first_word = (j < 64) & (j % 2 == 1) | (j >= 64) & (j < 74)
+    mask = np.stack([j < T,                     # a full prefix
+                     (j == 0) | (j == T - 1),   # the middle word is all zero
+                     every_word,                # a non-prefix pattern in every word
+                     j < 0,                     # not accepted
+                     j < 0,                     # accepted, no survivor
+                     j < 64, j < 65,            # a whole word, a word and a point
+                     first_word,                # non-prefix, then a prefix word
+                     j < 0])                    # not accepted
+    accepted = np.array([1, 1, 1, 0, 1, 1, 1, 1, 0], dtype=bool)
+    return mask, accepted
+
+
+def guarded(words, device):
+    """(an int32 buffer of `words` + 64 words of SENTINEL on the device, a
+    function that downloads it and returns (the words, the guard is untouched))."""
+    import torch
+    buf = torch.full((words + 64,), SENTINEL, dtype=torch.int32, device=device)
+    return buf, lambda: (buf.cpu().numpy()[:words], bool((buf[words:] == SENTINEL).all()))
+
+
+@pytest.mark.gpu
+def test_the_walk_of_both_emit_kernels_on_hand_written_masks():
+    import torch
+    from tracktolearn_amd import _lib
+    from tracktolearn_amd.io import streamlines as sio
+    T = 130
+    mask, accepted = walk_rows(T)
+    n = len(mask)
+    padded = np.zeros((n, 192), dtype=bool)
+    padded[:, :T] = mask
+    words = np.packbits(padded, axis=1, bitorder='little').view('<u8')
+    assert words.shape == (n, 3) and (words[1] == (1, 0, 2)).all()
+    prefix = (words & (words + np.uint64(1))) == 0
+    assert not prefix[2].any() and (words[2] != 0).all()
+    assert list(prefix[7]) == [False, True, True] and list(words[7] != 0) == [True, True, False]
+    counts = mask.sum(axis=1).astype(np.int32)
+    assert list(counts) == [130, 2, counts[2], 0, 0, 64, 65, 42, 0] and counts[2] > 64
+    rng = np.random.RandomState(41)
+    hist = rng.uniform(-20.0, 90.0, (n, T, 3)).astype(np.float32)
+    seeds = rng.uniform(0.0, 90.0, (n, 3))
+    want_points = hist[mask]                        # streamline-major
+    want_counts, want_rows = counts[accepted].astype(np.int64), np.nonzero(accepted)[0]
+    M, k = len(want_points), len(want_rows)
+    assert (M, k) == (int(counts.sum()), 7)
+
+    dev = torch.device('cuda:0')
+    lib = _lib.load()
+    h, sd = torch.from_numpy(hist).to(dev), torch.from_numpy(seeds).to(dev)
+    cnt = torch.from_numpy(counts).to(dev)
+    acc = torch.from_numpy(accepted.astype(np.int32)).to(dev)
+    ends = (torch.cumsum(cnt, 0, dtype=torch.int64), torch.cumsum(acc, 0, dtype=torch.int64))
+    msk = torch.from_numpy(words.view(np.int64)).to(dev)
+    inputs = (h.data_ptr(), h.stride(0), n, cnt.data_ptr(), acc.data_ptr(),
+              ends[0].data_ptr(), ends[1].data_ptr(), msk.data_ptr())
+
+    points, get_points = guarded(3 * M, dev)
+    counts_out, get_counts = guarded(2 * k, dev)        # int64
+    rows_out, get_rows = guarded(k, dev)
+    torch.cuda.synchronize()
+    _lib.check(lib.ttl_tract_emit(*inputs, points.data_ptr(), counts_out.data_ptr(),
+                                  rows_out.data_ptr(), None), 'ttl_tract_emit')
+    torch.cuda.synchronize()
+    for (got, untouched), want in ((get_points(), want_points.view(np.int32).reshape(-1)),
+                                   (get_counts(), want_counts.view(np.int32)),
+                                   (get_rows(), want_rows.astype(np.int32))):
+        assert untouched and np.array_equal(got, want)
+
+    for chain, n_props in (('trk_rotated', 3), ('tck_rotated', 0)):
+        desc = chain_desc(chain, n_props)
+        want = sio.packed_body(want_points, want_counts, seeds[want_rows] if n_props else None,
+                               desc)
+        assert len(want) == sio.body_words(desc, k, M)
+        body, get_body = guarded(len(want), dev)
+        c_desc = desc.to_c()
+        torch.cuda.synchronize()
+        _lib.check(lib.ttl_tract_emit_file(*inputs, sd.data_ptr() if n_props else None,
+                                           C.byref(c_desc), body.data_ptr(), None),
+                   'ttl_tract_emit_file')
+        torch.cuda.synchronize()
+        got, untouched = get_body()
+        assert untouched and np.array_equal(got.view(np.uint32), want)
+
+
 def _tracker(name, compress):
     import torch
     from helpers import load_trace

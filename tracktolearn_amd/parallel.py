@@ -14,10 +14,13 @@ sender uses its own link to the root; gloo in the CPU tests).  No padding, and
 1/R of the bytes an all-gather of the same data would land on every GPU.
 ``all_gather_ragged`` remains for callers that need the data everywhere.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.distributed as dist
 
+from tracktolearn_amd import _lib
 from tracktolearn_amd.environments.stopping_criteria import StoppingFlags
 from tracktolearn_amd.tractogram import Tractogram
 
@@ -38,6 +41,21 @@ def kept_lengths(lengths, flags):
     return lengths.to(torch.int64) - ((flags & cut) != 0).to(torch.int64)
 
 
+def _device_lib(device):
+    """What every launch from this file starts with: (the loaded library, the
+    raw HIP stream of ``device`` that torch is on)."""
+    from tracktolearn_amd.environments.env import _raw_stream
+    return _lib.load(), C.c_void_p(_raw_stream(device.index or 0))
+
+
+def _point_rows(history):
+    """The (n, T, 3) history as the kernels read it: a row's points one after
+    the other; rows may be further apart than their points (a slice of a
+    larger buffer)."""
+    return history if history.stride(2) == 1 and history.stride(1) == 3 \
+        else history.contiguous()
+
+
 def pack_points(history, keep_len):
     """Ragged pack: (n, T, 3) history + kept lengths -> (sum(keep_len), 3)
     points, streamline-major.  On the GPU: one wave per streamline
@@ -47,23 +65,18 @@ def pack_points(history, keep_len):
     if not history.is_cuda:
         steps = torch.arange(history.shape[1], device=history.device)
         return history[steps[None, :] < keep_len[:, None]]
-    from tracktolearn_amd import _lib
-    from tracktolearn_amd.environments.env import _raw_stream
     n = int(history.shape[0])
     keep = keep_len.to(torch.int64).contiguous()
     ends = torch.cumsum(keep, 0)
     total = int(ends[-1].item()) if n else 0
     out = torch.empty((total, 3), dtype=torch.float32, device=history.device)
     if total:
-        # rows may be further apart than their points (a slice of a larger buffer)
-        hist = history if history.stride(2) == 1 and history.stride(1) == 3 \
-            else history.contiguous()
+        lib, stream = _device_lib(history.device)
+        hist = _point_rows(history)
         offsets = ends - keep
-        import ctypes as C
-        _lib.check(_lib.load().ttl_pack_streamlines(
+        _lib.check(lib.ttl_pack_streamlines(
             hist.data_ptr(), hist.stride(0), keep.data_ptr(), offsets.data_ptr(), n,
-            out.data_ptr(), C.c_void_p(_raw_stream(history.device.index or 0))),
-            'ttl_pack_streamlines')
+            out.data_ptr(), stream), 'ttl_pack_streamlines')
     return out
 
 
@@ -74,13 +87,9 @@ def tract_survivors(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     (2, n) int32: surviving points per row -- 0 for a rejected row -- and the
     0 / 1 accept flags, ``mask`` (n, ceil(T / 64)) int64: bit ``j & 63`` of word
     ``j >> 6`` is set iff point j of the row survives)."""
-    import ctypes as C
-    from tracktolearn_amd import _lib
-    from tracktolearn_amd.environments.env import _raw_stream
-    lib = _lib.load()
     n, dev = int(history.shape[0]), history.device
-    hist = history if history.stride(2) == 1 and history.stride(1) == 3 \
-        else history.contiguous()
+    lib, stream = _device_lib(dev)
+    hist = _point_rows(history)
     lengths = lengths.to(torch.int32).contiguous()
     flags = flags.to(torch.int32).contiguous()
     pitch = hist.stride(0)
@@ -89,8 +98,7 @@ def tract_survivors(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     _lib.check(lib.ttl_tract_select(
         hist.data_ptr(), pitch, lengths.data_ptr(), flags.data_ptr(), n,
         float(min_arc), float(max_arc), float(tol_error), float(max_segment_length),
-        sel[0].data_ptr(), sel[1].data_ptr(), mask.data_ptr(),
-        C.c_void_p(_raw_stream(dev.index or 0))), 'ttl_tract_select')
+        sel[0].data_ptr(), sel[1].data_ptr(), mask.data_ptr(), stream), 'ttl_tract_select')
     return hist, sel, mask
 
 
@@ -104,6 +112,32 @@ def _drop_rejected(sel, reject):
     and is not accepted (the emit kernels skip unaccepted rows)."""
     if reject is not None:
         sel.masked_fill_(reject.to(sel.device)[None, :], 0)
+
+
+def _selected(history, lengths, flags, min_arc, max_arc, tol_error, max_segment_length,
+              reject):
+    """The GPU front half of ``select_tracts`` and ``select_tracts_file``:
+    ``tract_survivors``, the rejected rows dropped, the scans and the host's
+    look at their totals.  Returns (``emit``, points M, accepted rows k, the
+    library): ``emit(name, *outputs)`` launches that emit entry point -- the
+    two take the same inputs, held here -- into ``outputs`` unless k is 0."""
+    n = int(history.shape[0])
+    lib, stream = _device_lib(history.device)
+    hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
+                                      tol_error, max_segment_length)
+    _drop_rejected(sel, reject)
+    # two 1-D scans: torch's scan along the inner dimension of a (2, n) tensor
+    # takes 0.6 ms at n = 262 144, longer than both kernels together
+    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64),
+            torch.cumsum(sel[1], 0, dtype=torch.int64))
+    total, k = torch.stack((ends[0][-1], ends[1][-1])).tolist()   # the one synchronising copy
+
+    def emit(name, *outputs):
+        if k:
+            _lib.check(getattr(lib, name)(
+                hist.data_ptr(), hist.stride(0), n, sel[0].data_ptr(), sel[1].data_ptr(),
+                ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(), *outputs, stream), name)
+    return emit, total, k, lib
 
 
 def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
@@ -132,29 +166,12 @@ def select_tracts(history, lengths, flags, min_arc, max_arc, tol_error=0.0,
     if not history.is_cuda:
         return _select_tracts_host(history, lengths, flags, min_arc, max_arc,
                                    tol_error, max_segment_length, reject)
-    import ctypes as C
-    from tracktolearn_amd import _lib
-    from tracktolearn_amd.environments.env import _raw_stream
-    lib = _lib.load()
-    stream = C.c_void_p(_raw_stream(dev.index or 0))
-    hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
-                                      tol_error, max_segment_length)
-    _drop_rejected(sel, reject)
-    pitch = hist.stride(0)
-    # two 1-D scans: torch's scan along the inner dimension of a (2, n) tensor
-    # takes 0.6 ms at n = 262 144, longer than both kernels together
-    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64),
-            torch.cumsum(sel[1], 0, dtype=torch.int64))
-    total, k = torch.stack((ends[0][-1], ends[1][-1])).tolist()   # the one synchronising copy
+    emit, total, k, _ = _selected(history, lengths, flags, min_arc, max_arc, tol_error,
+                                  max_segment_length, reject)
     points = torch.empty((total, 3), dtype=torch.float32, device=dev)
     counts = torch.empty(k, dtype=torch.int64, device=dev)
     rows = torch.empty(k, dtype=torch.int32, device=dev)
-    if k:
-        _lib.check(lib.ttl_tract_emit(
-            hist.data_ptr(), pitch, n, sel[0].data_ptr(), sel[1].data_ptr(),
-            ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(),
-            points.data_ptr(), counts.data_ptr(), rows.data_ptr(), stream),
-            'ttl_tract_emit')
+    emit('ttl_tract_emit', points.data_ptr(), counts.data_ptr(), rows.data_ptr())
     return points, counts, rows.to(torch.int64)
 
 
@@ -184,17 +201,8 @@ def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=No
             np.asarray(seeds, dtype=np.float64).reshape(-1, 3)[rows.numpy()]
         words = packed_body(points.numpy(), counts.numpy(), kept, desc)
         return torch.from_numpy(words.view(np.int32)), len(counts), len(points)
-    import ctypes as C
-    from tracktolearn_amd import _lib
-    from tracktolearn_amd.environments.env import _raw_stream
-    lib = _lib.load()
-    stream = C.c_void_p(_raw_stream(dev.index or 0))
-    hist, sel, mask = tract_survivors(history, lengths, flags, min_arc, max_arc,
-                                      tol_error, max_segment_length)
-    _drop_rejected(sel, reject)
-    ends = (torch.cumsum(sel[0], 0, dtype=torch.int64),
-            torch.cumsum(sel[1], 0, dtype=torch.int64))
-    total, k = torch.stack((ends[0][-1], ends[1][-1])).tolist()   # the one synchronising copy
+    emit, total, k, lib = _selected(history, lengths, flags, min_arc, max_arc, tol_error,
+                                    max_segment_length, reject)
     c_desc = desc.to_c()
     size = lib.ttl_tract_file_words(c_desc.format, c_desc.n_props, k, total)
     if size < 0:
@@ -203,19 +211,16 @@ def select_tracts_file(history, lengths, flags, min_arc, max_arc, desc, seeds=No
     words = torch.empty(size, dtype=torch.int32, device=dev)
     if seeds is not None:
         seeds = torch.as_tensor(seeds, dtype=torch.float64).to(dev).reshape(n, 3).contiguous()
-    if k:
-        _lib.check(lib.ttl_tract_emit_file(
-            hist.data_ptr(), hist.stride(0), n, sel[0].data_ptr(), sel[1].data_ptr(),
-            ends[0].data_ptr(), ends[1].data_ptr(), mask.data_ptr(),
-            seeds.data_ptr() if seeds is not None else None, C.byref(c_desc),
-            words.data_ptr(), stream), 'ttl_tract_emit_file')
+    emit('ttl_tract_emit_file', seeds.data_ptr() if seeds is not None else None,
+         C.byref(c_desc), words.data_ptr())
     return words, k, total
 
 
-def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
-                        max_segment_length, reject=None):
-    from tracktolearn_amd.tractogram import compress_streamline
-    keep_len = kept_lengths(lengths, flags)
+def arc_accept(history, keep_len, min_arc, max_arc, reject=None):
+    """The arc-length filter as torch expressions (the specification of
+    ``ttl_tract_select``'s, and the ``device_output=False`` path): (n,) bool,
+    True where the float64 arc length of a row's first ``keep_len`` points is in
+    [min_arc, max_arc] and ``reject`` (as for ``select_tracts``) is not set."""
     seg = (history[:, 1:] - history[:, :-1]).double()
     seg_len = torch.sqrt((seg ** 2).sum(dim=2))
     steps = torch.arange(seg_len.shape[1], device=history.device)
@@ -224,7 +229,14 @@ def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
     ok = (arc >= min_arc) & (arc <= max_arc)
     if reject is not None:
         ok &= ~reject
-    rows = torch.nonzero(ok).squeeze(1)
+    return ok
+
+
+def _select_tracts_host(history, lengths, flags, min_arc, max_arc, tol_error,
+                        max_segment_length, reject=None):
+    from tracktolearn_amd.tractogram import compress_streamline
+    keep_len = kept_lengths(lengths, flags)
+    rows = torch.nonzero(arc_accept(history, keep_len, min_arc, max_arc, reject)).squeeze(1)
     hist = history.numpy()
     lines = [hist[r, :k] for r, k in zip(rows.tolist(), keep_len[rows].tolist())]
     if tol_error > 0:
@@ -325,25 +337,33 @@ def gather_tract_arrays(env, dst=0, group=None):
     return keep_all, flags_all, pts_all, moved
 
 
+def _seeds_of(env):
+    return torch.from_numpy(np.ascontiguousarray(env.initial_points, dtype=np.float64))
+
+
+def tractogram_of(keep, flags, points, seeds):
+    """``tract_arrays`` (tensors on any device, of one rank or of all) and the
+    seeds of the same rows -> the Tractogram ``get_streamlines()`` returns:
+    one view of the downloaded points per streamline, seeds and flags as
+    ``data_per_streamline``."""
+    keep, flags, points = (t.cpu().numpy() for t in (keep, flags, points))
+    offsets = np.concatenate(([0], np.cumsum(keep)))
+    lines = [points[offsets[i]:offsets[i + 1]] for i in range(len(keep))]
+    return Tractogram(streamlines=lines,
+                      data_per_streamline={
+                          'seeds': seeds.cpu().numpy() if torch.is_tensor(seeds) else seeds,
+                          'flags': flags.astype(np.int64)})
+
+
 def gather_tractogram(env, dst=0, group=None):
     """The sharded ``get_streamlines()``: every rank's finished tracts as one
     Tractogram (rank order, then streamline order) on rank ``dst``; None on
     the other ranks."""
-    seeds = torch.from_numpy(np.ascontiguousarray(env.initial_points,
-                                                  dtype=np.float64))
-    seeds_all, _ = gather_ragged_to_root(seeds, dst, group)
+    seeds_all, _ = gather_ragged_to_root(_seeds_of(env), dst, group)
     got = gather_tract_arrays(env, dst, group)
     if got is None:
         return None
-    keep_all, flags_all, pts_all, _ = got
-    keep_np = keep_all.cpu().numpy()
-    pts_np = pts_all.cpu().numpy()
-    offsets = np.concatenate(([0], np.cumsum(keep_np)))
-    lines = [pts_np[offsets[i]:offsets[i + 1]] for i in range(len(keep_np))]
-    return Tractogram(streamlines=lines,
-                      data_per_streamline={
-                          'seeds': seeds_all.cpu().numpy(),
-                          'flags': flags_all.cpu().numpy().astype(np.int64)})
+    return tractogram_of(*got[:3], seeds_all)
 
 
 def all_gather_tract_index(env, group=None):
@@ -358,21 +378,10 @@ def all_gather_tract_index(env, group=None):
 def all_gather_tractogram(env, group=None):
     """Every rank's finished tracts as one Tractogram (rank order, then
     streamline order) -- the sharded ``get_streamlines()``."""
-    n = env._n_total
-    lengths, flags = env._buf_lengths[:n], env._buf_flags[:n]
-    keep = kept_lengths(lengths, flags)
-    points = pack_points(env._buf_streamlines[:n], keep)
-    keep_all = torch.cat(all_gather_ragged(keep, group)).cpu().numpy()
-    flags_all = torch.cat(all_gather_ragged(flags, group)).cpu().numpy()
-    seeds = torch.from_numpy(np.ascontiguousarray(env.initial_points,
-                                                  dtype=np.float64))
-    seeds_all = torch.cat(all_gather_ragged(seeds, group)).cpu().numpy()
-    pts_all = torch.cat(all_gather_ragged(points, group)).cpu().numpy()
-    offsets = np.concatenate(([0], np.cumsum(keep_all)))
-    lines = [pts_all[offsets[i]:offsets[i + 1]] for i in range(len(keep_all))]
-    return Tractogram(streamlines=lines,
-                      data_per_streamline={'seeds': seeds_all,
-                                           'flags': flags_all.astype(np.int64)})
+    keep, flags, points = tract_arrays(env)
+    keep, flags, seeds, points = (torch.cat(all_gather_ragged(t, group))
+                                  for t in (keep, flags, _seeds_of(env), points))
+    return tractogram_of(keep, flags, points, seeds)
 
 
 # --------------------------------------------------------------------------

@@ -225,18 +225,9 @@ class TrackToLearnTrack(object):
             env.noise_rng = per_rank_noise_rng(self.random_seed, tracker.rank)
         header = sio.create_tractogram_header(
             ref_img.affine, ref_img.shape[:3], ref_img.get_zooms()[:3])
-        if self.direct_output:
-            # the output stage writes the file's records: no per-streamline Python
-            n = tracker.track_to_file(env, self.out_tractogram, header)
-            if tracker.rank != 0:
-                return
-        else:
-            tractogram = tracker.track(env, detect_format(self.out_tractogram))
-            if tracker.rank != 0:
-                for _ in tractogram:        # take part in the collectives only
-                    pass
-                return
-            n = sio.save(tractogram, self.out_tractogram, header=header)
+        n = tracker.save(env, self.out_tractogram, header, direct=self.direct_output)
+        if n is None:           # not rank 0
+            return
         print('Saved {} streamlines to {}'.format(n, self.out_tractogram))
 
 

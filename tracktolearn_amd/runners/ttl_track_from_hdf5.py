@@ -106,7 +106,7 @@ class TrackToLearnValidation(object):
     def run(self):
         from tracktolearn_amd.algorithms.sac_auto import SACAuto
         from tracktolearn_amd.io import streamlines as sio
-        from tracktolearn_amd.tracking.tracker import Tracker, detect_format
+        from tracktolearn_amd.tracking.tracker import Tracker
         env = self.get_valid_env()
         example_state = env.reset(0, 1)
         input_size = example_state.shape[1]
@@ -134,11 +134,7 @@ class TrackToLearnValidation(object):
         zooms = (float(tracking_voxel_size),) * 3
         header = sio.create_tractogram_header(
             ref.get('affine', env.affine_vox2rasmm), shape, zooms)
-        if self.direct_output:
-            n = tracker.track_to_file(env, out, header)
-        else:
-            tractogram = tracker.track(env, detect_format(out))
-            n = sio.save(tractogram, out, header=header)
+        n = tracker.save(env, out, header, direct=self.direct_output)
         print('Saved {} streamlines to {}'.format(n, out))
         return out
 

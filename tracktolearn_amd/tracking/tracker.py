@@ -102,6 +102,23 @@ class Tracker(object):
             return bool(env._buf_streamlines.is_cuda)
         return bool(self.device_output)
 
+    def _geometry(self, env):
+        """The batch geometry of the output stage, stated once: (the voxel size
+        of the env's affine in mm, ``min_length`` and ``max_length`` as arc
+        lengths in voxels, the compression tolerance in voxels -- 0.0: none)."""
+        vox_size = np.mean(np.abs(env.affine_vox2rasmm)[np.diag_indices(4)][:3])
+        return (vox_size, self.min_length / vox_size, self.max_length / vox_size,
+                self.compress / vox_size if self.compress else 0.0)
+
+    @staticmethod
+    def _seeds(env, device):
+        """The finished batch's seeds as an (n, 3) float64 tensor on ``device``."""
+        n = env._n_total
+        if n == 0:              # an empty shard of a sharded batch
+            return torch.zeros((0, 3), dtype=torch.float64, device=device)
+        return torch.from_numpy(np.ascontiguousarray(
+            np.asarray(env.initial_points)[:n], dtype=np.float64).reshape(-1, 3)).to(device)
+
     def _act_reject(self, env):
         """(n,) bool on the env's device: the rows of the finished batch that
         ``act_filter`` drops, from the flags the batch ended with and, after a
@@ -134,41 +151,20 @@ class Tracker(object):
         points, counts, rows = select_tracts(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
             scaled_min, scaled_max, tol_vox, reject=self._act_reject(env))
-        if n == 0:              # an empty shard of a sharded batch
-            seeds = np.zeros((0, 3), dtype=np.float64)
-        else:
-            seeds = np.ascontiguousarray(
-                np.asarray(env.initial_points)[rows.cpu().numpy()], dtype=np.float64)
-        return points, counts, torch.from_numpy(seeds.reshape(-1, 3))
+        return points, counts, self._seeds(env, 'cpu')[rows.cpu()]
 
     def _batch_arrays_host(self, env, scaled_min, scaled_max):
         """``device_output=False``: the length filter as torch expressions on
         the device, no compression.  Returns (packed points (M, 3) f32, kept
         lengths (k,) i64, seeds (k, 3) f64) as device tensors."""
+        from tracktolearn_amd.parallel import arc_accept, kept_lengths, pack_points
         n = env._n_total
-        from tracktolearn_amd.parallel import kept_lengths, pack_points
-        if n == 0:              # an empty shard of a sharded batch
-            dev = env.device
-            return (torch.zeros((0, 3), dtype=torch.float32, device=dev),
-                    torch.zeros(0, dtype=torch.int64, device=dev),
-                    torch.zeros((0, 3), dtype=torch.float64, device=dev))
-        keep_len = kept_lengths(env._buf_lengths[:n], env._buf_flags[:n])
         hist = env._buf_streamlines[:n]
-        seg = (hist[:, 1:] - hist[:, :-1]).double()
-        seg_len = torch.sqrt((seg ** 2).sum(dim=2))
-        steps = torch.arange(seg_len.shape[1], device=hist.device)
-        valid = steps[None, :] < (keep_len - 1)[:, None]
-        arc = (seg_len * valid).sum(dim=1)
-        ok = (arc >= scaled_min) & (arc <= scaled_max)
-        reject = self._act_reject(env)
-        if reject is not None:
-            ok &= ~reject
-        sel = torch.nonzero(ok).squeeze(1)
+        keep_len = kept_lengths(env._buf_lengths[:n], env._buf_flags[:n])
+        sel = torch.nonzero(arc_accept(hist, keep_len, scaled_min, scaled_max,
+                                       self._act_reject(env))).squeeze(1)
         keep_sel = keep_len[sel]
-        points = pack_points(hist[sel], keep_sel)
-        seeds = torch.from_numpy(np.ascontiguousarray(
-            env.initial_points, dtype=np.float64)).to(hist.device)[sel]
-        return points, keep_sel, seeds
+        return pack_points(hist[sel], keep_sel), keep_sel, self._seeds(env, hist.device)[sel]
 
     def _batch_items(self, env, scaled_min, scaled_max, transform=None, tol_vox=0.0):
         """(streamline, seed) pairs of the finished batch on this process;
@@ -205,10 +201,7 @@ class Tracker(object):
         """The output stage over the env's finished batch: the TractogramItems
         ``track`` yields for it (length filter, compression, file space)."""
         affine = env.affine_vox2rasmm
-        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
-        scaled_min_length = self.min_length / vox_size
-        scaled_max_length = self.max_length / vox_size
-        compress_th_vox = self.compress / vox_size
+        vox_size, scaled_min_length, scaled_max_length, compress_th_vox = self._geometry(env)
         # .trk: the file-space conversion is element-wise, so it runs once over
         # the packed batch -- bit for bit what the per-streamline call gives.
         # On the host path only without compression, which there comes after
@@ -217,8 +210,7 @@ class Tracker(object):
         for streamline, seed in self._batch_items(
                 env, scaled_min_length, scaled_max_length,
                 transform=(lambda p: to_file_space(p, TrkFile, affine, vox_size))
-                if whole_batch else None,
-                tol_vox=compress_th_vox if self.compress else 0.0):
+                if whole_batch else None, tol_vox=compress_th_vox):
             if self.compress and not on_device:
                 streamline = compress_streamline(streamline, compress_th_vox)
             if not whole_batch:
@@ -228,6 +220,14 @@ class Tracker(object):
             if self.save_seeds:
                 seed_dict = {'seeds': seed - 0.5}
             yield TractogramItem(streamline, seed_dict, {})
+
+    def _episode(self, env, start, end):
+        """Tracks seeds [start, end) as one batch, and back again from the seeds
+        when ``bidirectional``; returns the summed reward."""
+        reward = self.alg.validation_episode(env.reset(start, end), env, self.prob)
+        if self.bidirectional:
+            reward += self.alg.validation_episode(env.reset_backward(), env, self.prob)
+        return reward
 
     def _tracked_batches(self, env):
         """Tracks the seeds a batch (this rank's shard of it) at a time; yields
@@ -241,11 +241,7 @@ class Tracker(object):
                 lo, hi = shard_bounds(end - start, self.rank, self.group_size)
                 start, end = start + lo, start + hi
             if end > start:
-                state = env.reset(start, end)
-                self.alg.validation_episode(state, env, self.prob)
-                if self.bidirectional:
-                    state = env.reset_backward()
-                    self.alg.validation_episode(state, env, self.prob)
+                self._episode(env, start, end)
             else:           # an empty shard still joins the collectives
                 env._n_total = 0
             yield
@@ -297,36 +293,45 @@ class Tracker(object):
                 writer.close()
         return writer.count if writer is not None else None
 
+    def save(self, env, path, header, direct=False):
+        """This env's tractogram to ``path`` with ``header``: ``track_to_file``
+        when ``direct`` (the output stage writes the file's records: no
+        per-streamline Python), otherwise ``track`` + ``io.streamlines.save``.
+        Returns the number of streamlines written; None off rank 0, whose
+        peers take part in the collectives only."""
+        from tracktolearn_amd.io import streamlines as sio
+        if direct:
+            return self.track_to_file(env, path, header)
+        tractogram = self.track(env, detect_format(path))
+        if self.rank != 0:
+            for _ in tractogram:
+                pass
+            return None
+        return sio.save(tractogram, path, header=header)
+
     def file_desc(self, env, tracts_format, header=None):
         """The ``io.streamlines.BodyDesc`` of the file ``track`` + ``save``
         write for this env: the seeds as properties with ``save_seeds``, in
         .trk only."""
         from tracktolearn_amd.io import streamlines as sio
-        affine = env.affine_vox2rasmm
-        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
         n_props = 3 if self.save_seeds and tracts_format is TrkFile else 0
-        return sio.body_desc(tracts_format.EXT, affine, vox_size, header, n_props)
+        return sio.body_desc(tracts_format.EXT, env.affine_vox2rasmm, self._geometry(env)[0],
+                             header, n_props)
 
     def batch_body(self, env, desc):
         """The output stage of ``track_to_file`` over the env's finished
         batch: (the body's words as a host array, streamlines in it); with a
         process group every rank's, in rank order, on rank 0 and (None, the
         count) elsewhere.  One download."""
-        import torch
         from tracktolearn_amd.parallel import select_tracts_file
-        affine = env.affine_vox2rasmm
-        vox_size = np.mean(np.abs(affine)[np.diag_indices(4)][:3])
+        _, scaled_min, scaled_max, tol_vox = self._geometry(env)
         n = env._n_total
-        seeds = None
-        if desc.n_props:        # the batch's seeds, uploaded once
-            seeds = torch.from_numpy(np.ascontiguousarray(
-                np.asarray(env.initial_points)[:n], dtype=np.float64).reshape(-1, 3)).to(
-                    env._buf_streamlines.device)
         words, k, _ = select_tracts_file(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
-            self.min_length / vox_size, self.max_length / vox_size, desc, seeds,
-            tol_error=self.compress / vox_size if self.compress else 0.0,
-            reject=self._act_reject(env))
+            scaled_min, scaled_max, desc,
+            # the batch's seeds, uploaded once
+            self._seeds(env, env._buf_streamlines.device) if desc.n_props else None,
+            tol_error=tol_vox, reject=self._act_reject(env))
         if self.group_size > 1:
             from tracktolearn_amd.parallel import (all_gather_counts,
                                                    gather_ragged_to_root)
@@ -359,12 +364,7 @@ class Tracker(object):
         tractogram = None
         cummulative_reward = 0
         for start in tqdm(range(0, len(env.seeds), self.n_actor)):
-            end = min(start + self.n_actor, len(env.seeds))
-            state = env.reset(start, end)
-            reward = self.alg.validation_episode(state, env, self.prob)
-            if self.bidirectional:
-                state = env.reset_backward()
-                reward += self.alg.validation_episode(state, env, self.prob)
+            reward = self._episode(env, start, min(start + self.n_actor, len(env.seeds)))
             batch = env.get_streamlines()
             if tractogram is None and len(batch) > 0:
                 tractogram = batch
