@@ -248,7 +248,7 @@ def test_random_episode_against_oracle(noisy, affine, K, reward, step_mm, kernel
         ns_ref, r_ref, d_ref, _ = ref.step(a.copy())
         assert np.array_equal(d_hip, d_ref)
         assert _close(ns_hip.cpu().numpy(), ns_ref)
-        assert _close(r_hip, r_ref)
+        assert np.array_equal(r_hip, r_ref, equal_nan=True)    # bit-identical
         s_hip, _ = env.harvest()
         s_ref, _ = ref.harvest()
         assert np.array_equal(env.continue_idx, ref.continue_idx)
@@ -345,7 +345,7 @@ def test_edge_cases():
         assert np.array_equal(d_hip, d_ref)
         assert d_hip[0]                             # NaN position leaves the mask
         assert _close(ns_hip.cpu().numpy(), ns_ref)
-        assert _close(r_hip, r_ref)
+        assert np.array_equal(r_hip, r_ref, equal_nan=True)    # bit-identical
         env.harvest()
         ref.harvest()
         assert np.array_equal(env.flags, ref.flags)
