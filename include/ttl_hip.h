@@ -850,6 +850,67 @@ TTL_API int ttl_tractometer_invalid(const float *points, const int64_t *offsets,
                                     const uint64_t *roi, const uint64_t *valid, int32_t *pair,
                                     void *hip_stream);
 
+/* The structural connectome (TTL_HAS_CONNECTOME): the node of a parcellation
+ * at either end of every streamline, and the node x node matrices of streamline counts and
+ * summed lengths.  This project's own statement; the reference has no counterpart.  Input
+ * is the ragged layout of ttl_tract_coverage: corner-origin voxel coordinates of the label
+ * image's grid (voxel v spans [v, v + 1), its centre is v + 0.5), dims = {X, Y, Z}, lin
+ * (double [9], row-major linear part of voxel -> RAS mm) and reach (int32 [3]) in host
+ * memory.  labels: device int32 [X * Y * Z], word (x * Y + y) * Z + z; the values 1 .. N =
+ * n_nodes name a node, every other value (negatives and values above N included) is no node.
+ *
+ * ttl_connectome_assign, for streamline s with points c_0 .. c_{L-1} (float32 read as
+ * float64, all arithmetic float64 in the written order):
+ *   not scored  node[s] = (-1, -1), length[s] = 0 when L < 2, when a point is non-finite or
+ *               when the length below is not < 2^40 mm.
+ *   length[s]   = sum_j |v_j|, v_j = lin (c_{j+1} - c_j), each row ((m0 x + m1 y) + m2 z),
+ *               |v| = sqrt((vx^2 + vy^2) + vz^2) (ttl_tractometer_classify's expressions);
+ *               a butterfly sum over the lanes, so the order of the sum over j is the kernel's.
+ *   node of an end p (c_0 for column 0, c_{L-1} for column 1; interior points are not read
+ *               for it), e = floor(p) (floor, not truncation: -0.3 is voxel -1):
+ *               1. e in [0, dims) and labels[e] a node: that node (the point is inside it);
+ *               2. otherwise the candidates are the in-volume voxels v with |v_i - e_i| <=
+ *                  reach_i on every axis, labels[v] a node and d2(v) <= radius_mm^2
+ *                  (inclusive), w = lin (p - (v + 0.5)), d2 = (wx^2 + wy^2) + wz^2; the node
+ *                  is the label of the candidate with the smallest d2, on equal d2 the one
+ *                  with the smallest word index; 0 without a candidate.
+ *               An end outside the volume is neither clamped nor rejected: the voxels within
+ *               reach of it are still candidates; one so far out that no voxel of its box
+ *               is in the volume gets 0 and costs no work (the box is cut to the volume in
+ *               float64, before any conversion to an integer).  radius_mm = 0 with reach =
+ *               {0, 0, 0} is therefore "the label of the end's own voxel".
+ *   node[s]     = (node of c_0, node of c_{L-1}), in streamline order, not sorted (device
+ *               int32 [n][2]; length: device double [n]).
+ * One wavefront per streamline: lanes over the segments, then, for an end that step 1 did
+ * not settle, lanes over the voxels of the box, z fastest, and a wave-wide minimum of
+ * (d2, index) (non-negative doubles order as their bit patterns).  No atomics.
+ *
+ * ttl_connectome_accumulate: count and length_q are device int64 [N + 1][N + 1], ADDED TO,
+ * not overwritten: the caller zeroes them once and streams batches in.  A row with
+ * node[s][0] < 0 is skipped (and so is one that names a node above N); otherwise, with a =
+ * min, b = max of its two nodes (0 = unassigned), count[a][b] += 1 and, when length is
+ * non-null, length_q[a][b] += llrint(length[s] * TTL_CONNECTOME_LENGTH_SCALE), rounded half
+ * to even.  Only the upper triangle (row 0 and the diagonal included) is touched.  Integer
+ * atomics of device scope, exact: the matrices do not depend on the order or the split of
+ * the rows.  One thread per row, grid-stride over at most 2048 workgroups; the rows of a
+ * wavefront that share a cell are summed first: one atomic per distinct cell, wave and matrix.
+ * Both: TTL_ERR_INVALID, before any HIP call, for a null pointer (except length of
+ * accumulate, and hip_stream), n < 0, n_nodes outside 1 .. TTL_CONNECTOME_MAX_NODES, a dim
+ * < 1, a reach_i outside 0 .. TTL_CONNECTOME_MAX_REACH, a radius_mm that is negative or
+ * non-finite; n == 0 is a successful no-op. */
+#define TTL_HAS_CONNECTOME 1
+#define TTL_CONNECTOME_MAX_NODES 4096
+#define TTL_CONNECTOME_MAX_REACH 8
+#define TTL_CONNECTOME_LENGTH_SCALE 1048576.0   /* 2^20 units per mm */
+TTL_API int ttl_connectome_assign(const float *points, const int64_t *offsets, int32_t n,
+                                  const int32_t *labels, const int32_t *dims, int32_t n_nodes,
+                                  const double *lin, double radius_mm, const int32_t *reach,
+                                  int32_t *node /*[n][2]*/, double *length /*[n]*/,
+                                  void *hip_stream);
+TTL_API int ttl_connectome_accumulate(const int32_t *node, const double *length, int32_t n,
+                                      int32_t n_nodes, int64_t *count, int64_t *length_q,
+                                      void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

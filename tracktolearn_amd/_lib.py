@@ -36,6 +36,9 @@ FLAG_TARGET, FLAG_EXCLUDE = 8, 128      # TTL_FLAG_TARGET / TTL_FLAG_EXCLUDE
 ACT_THRESHOLD, ACT_CMC = 0, 1           # TTL_ACT_THRESHOLD / TTL_ACT_CMC
 ACT_STREAM = 0x41435420                 # TTL_ACT_STREAM
 HAS_ACT_IN_STEP = 1                     # TTL_HAS_ACT_IN_STEP (ttl_env_set_act)
+HAS_CONNECTOME = 1                      # TTL_HAS_CONNECTOME (ttl_connectome_assign / _accumulate)
+CONNECTOME_MAX_NODES, CONNECTOME_MAX_REACH = 4096, 8    # TTL_CONNECTOME_MAX_NODES / _MAX_REACH
+CONNECTOME_LENGTH_SCALE = 1048576.0     # TTL_CONNECTOME_LENGTH_SCALE: 2^20 units per mm
 
 
 class TTLError(RuntimeError):
@@ -181,6 +184,12 @@ SYMBOLS = {
     'ttl_tractometer_invalid': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.POINTER(C.c_int32), C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_connectome_assign': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_double),
+                                        C.c_double, C.POINTER(C.c_int32), C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    'ttl_connectome_accumulate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

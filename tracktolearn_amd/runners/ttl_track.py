@@ -10,6 +10,8 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--odf_policy {det,prob}] [--theta DEG] [--sf_threshold R] [--step_size MM]
         [--act_include FILE --act_exclude FILE] [--act_mode {act,cmc}]
         [--act_filter {none,exclude,endpoints}] [--act_in_step]
+        [--connectome LABELS --connectome_out PREFIX] [--connectome_radius MM]
+        [--connectome_only]
 
 With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
 itself (classical deterministic / probabilistic tracking as one GPU kernel,
@@ -23,6 +25,11 @@ brain mask (white and grey matter): a point that leaves in_mask in the step in
 which it reaches the include map is still dropped.  ``--act_in_step`` has the
 step's own launches apply the maps (``ttl_env_set_act``): the same tractogram,
 byte for byte, with the graphed tracking loop.
+
+With ``--connectome`` (a label image on the grid of in_mask) the node x node
+matrices of the streamlines that are written (connectome.py) are
+accumulated on the GPU while tracking; ``--connectome_only`` writes no
+tractogram at all.
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -116,6 +123,13 @@ class TrackToLearnTrack(object):
         if not self.act_include_file:
             self.act_filter = None
         self.act_in_step = bool(track_dto.get('act_in_step')) and bool(self.act_include_file)
+        # the structural connectome of the streamlines that are written
+        self.connectome_file = track_dto.get('connectome')
+        self.connectome_out = track_dto.get('connectome_out')
+        self.connectome_radius = track_dto.get('connectome_radius')
+        if self.connectome_radius is None:
+            self.connectome_radius = 2.0
+        self.connectome_only = bool(track_dto.get('connectome_only'))
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -212,10 +226,16 @@ class TrackToLearnTrack(object):
         env = self.get_tracking_env()
         env.step_size_mm = self._step_for_subject(ref_img.get_zooms()[0])
         alg = self._load_policy(env)
+        connectome = None
+        if self.connectome_file:
+            from tracktolearn_amd.connectome import Connectome
+            connectome = Connectome(
+                load_on_mask_grid('--connectome', self.connectome_file, self.in_mask),
+                ref_img.affine, radius_mm=self.connectome_radius, device=self.device)
         tracker = Tracker(alg, self.n_actor, compress=self.compress,
                           min_length=self.min_length, max_length=self.max_length,
                           save_seeds=self.save_seeds, bidirectional=self.bidirectional,
-                          act_filter=self.act_filter)
+                          act_filter=self.act_filter, connectome=connectome)
         # re-derives the step in voxels, the step counts and the neighbourhood
         # radius from the rescaled step (environments/env.py:196-212)
         env.load_subject()
@@ -225,8 +245,18 @@ class TrackToLearnTrack(object):
             env.noise_rng = per_rank_noise_rng(self.random_seed, tracker.rank)
         header = sio.create_tractogram_header(
             ref_img.affine, ref_img.shape[:3], ref_img.get_zooms()[:3])
-        n = tracker.save(env, self.out_tractogram, header, direct=self.direct_output)
-        if n is None:           # not rank 0
+        if self.connectome_only:
+            tracker.track_connectome(env)
+            n = None
+        else:
+            n = tracker.save(env, self.out_tractogram, header, direct=self.direct_output)
+        if connectome is not None:
+            connectome.save(self.connectome_out)
+            totals = connectome.totals()
+            print('Saved the connectome of {} streamlines ({} nodes, {} connected, {} skipped) '
+                  'to {}'.format(totals['streamlines'], totals['n_nodes'], totals['connected'],
+                                 totals['skipped'], self.connectome_out))
+        if n is None:           # not rank 0, or --connectome_only
             return
         print('Saved {} streamlines to {}'.format(n, self.out_tractogram))
 
@@ -355,6 +385,20 @@ def add_track_args(parser):
                        help='Apply the maps inside the tracking step instead of '
                             'between its two halves:\nthe same streamlines, and the '
                             'graphed tracking loop stays available.')
+    con_g = parser.add_argument_group(
+        'Structural connectome',
+        'The node x node matrices of the streamlines that are written, accumulated on '
+        'the GPU\nwhile tracking (one process only).')
+    con_g.add_argument('--connectome', type=str, default=None, metavar='LABELS',
+                       help='Label image (.nii.gz, integers 1 .. N, on the grid of in_mask).')
+    con_g.add_argument('--connectome_out', type=str, default=None, metavar='PREFIX',
+                       help='Writes PREFIX_count.npy, PREFIX_mean_length.npy, '
+                            'PREFIX_count.csv and PREFIX.json.')
+    con_g.add_argument('--connectome_radius', type=float, default=None, metavar='MM',
+                       help='An end outside every node takes the nearest labelled voxel '
+                            'centre within\nthis distance. [2.0]')
+    con_g.add_argument('--connectome_only', action='store_true',
+                       help='Write the connectome and no tractogram.')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -403,6 +447,23 @@ def parse_args(argv=None):
                 parser.error('Input file {} does not exist.'.format(f))
         args.act_mode = args.act_mode or 'act'
         args.act_filter = args.act_filter or 'exclude'
+    if args.connectome is None:
+        for name in ('connectome_out', 'connectome_radius'):
+            if getattr(args, name) is not None:
+                parser.error('--{} is used only with --connectome.'.format(name))
+        if args.connectome_only:
+            parser.error('--connectome_only is used only with --connectome.')
+    else:
+        if not os.path.isfile(args.connectome):
+            parser.error('Input file {} does not exist.'.format(args.connectome))
+        if args.connectome_out is None:
+            parser.error('--connectome needs --connectome_out PREFIX.')
+        if args.direct_output:
+            parser.error('--connectome reads the packed points, which --direct_output '
+                         'never makes: drop one of them.')
+        if args.connectome_radius is not None and not \
+                (np.isfinite(args.connectome_radius) and args.connectome_radius >= 0):
+            parser.error('--connectome_radius must be >= 0 mm.')
     if args.odf_policy:
         if args.agent is not None or args.hyperparameters is not None:
             parser.error('--odf_policy tracks without an agent: drop --agent / '

@@ -64,7 +64,7 @@ class Tracker(object):
 
     def __init__(self, alg, n_actor, prob=0., compress=0.0, min_length=20,
                  max_length=200, save_seeds=False, device_output=None,
-                 bidirectional=False, act_filter=None):
+                 bidirectional=False, act_filter=None, connectome=None):
         self.alg = alg
         self.n_actor = n_actor
         self.prob = prob
@@ -95,6 +95,17 @@ class Tracker(object):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             self.rank, self.group_size = dist.get_rank(), dist.get_world_size()
+        #: a ``connectome.Connectome`` on the label image of the env's grid: every
+        #: finished batch's ``select_tracts`` result (the streamlines that will be
+        #: written) is also added to it on the device, before anything is downloaded
+        self.connectome = connectome
+        if connectome is not None:
+            if device_output is not None and not device_output:
+                raise ValueError('a connectome is fed by the device output stage: '
+                                 'device_output=False has none')
+            if self.group_size > 1:
+                raise ValueError('a connectome is not summed across ranks: track it with '
+                                 'one process')
 
     # ------------------------------------------------------------------ #
     def _device_output(self, env):
@@ -146,12 +157,34 @@ class Tracker(object):
         ``select_tracts`` over the env's buffers.  Returns (packed points
         (M, 3) f32, points per streamline (k,) i64, seeds (k, 3) f64 -- a host
         tensor: ``env.initial_points`` at the downloaded row indices)."""
+        points, counts, rows = self._selected_batch(env, scaled_min, scaled_max, tol_vox)
+        return points, counts, self._seeds(env, 'cpu')[rows.cpu()]
+
+    def _selected_batch(self, env, scaled_min, scaled_max, tol_vox=0.0):
+        """``select_tracts`` over the env's finished batch (packed points, points
+        per streamline, source rows: device tensors), which a connectome also
+        receives here, still on the device: the env's voxel space has centre
+        origin, the label grid corner origin, so the points get + 0.5 in float32."""
         from tracktolearn_amd.parallel import select_tracts
         n = env._n_total
         points, counts, rows = select_tracts(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
             scaled_min, scaled_max, tol_vox, reject=self._act_reject(env))
-        return points, counts, self._seeds(env, 'cpu')[rows.cpu()]
+        if self.connectome is not None:
+            self._check_connectome(env)
+            offsets = torch.zeros(counts.shape[0] + 1, dtype=torch.int64, device=counts.device)
+            torch.cumsum(counts, 0, out=offsets[1:])
+            self.connectome.add(points + 0.5, offsets)
+        return points, counts, rows
+
+    def _check_connectome(self, env):
+        if not self._device_output(env):
+            raise ValueError('a connectome is fed by the device output stage, which this '
+                             'env (host buffers) does not have')
+        dims = tuple(int(v) for v in tuple(env.tracking_mask.data.shape)[:3])
+        if dims != tuple(self.connectome.dims):
+            raise ValueError(f'the connectome\'s label image {tuple(self.connectome.dims)} is '
+                             f'not on the grid of the tracking mask {dims}')
 
     def _batch_arrays_host(self, env, scaled_min, scaled_max):
         """``device_output=False``: the length filter as torch expressions on
@@ -177,6 +210,8 @@ class Tracker(object):
             points, keep_sel, seeds = self._batch_arrays(env, scaled_min, scaled_max,
                                                          tol_vox)
         else:
+            if self.connectome is not None:
+                self._check_connectome(env)         # raises: no device output stage
             points, keep_sel, seeds = self._batch_arrays_host(env, scaled_min, scaled_max)
         if self.group_size > 1:
             # gather-to-root of exact sizes: only rank 0 consumes the tracts
@@ -265,6 +300,19 @@ class Tracker(object):
         tractogram.affine_to_rasmm = affine
         return tractogram
 
+    def track_connectome(self, env):
+        """``track`` for the connectome alone: every batch is tracked and its
+        ``select_tracts`` result accumulated on the device; nothing is cut into
+        items or downloaded.  Returns the connectome."""
+        if self.connectome is None:
+            raise ValueError('track_connectome needs Tracker(..., connectome=...)')
+        self.alg.agent.eval()
+        np.random.shuffle(env.seeds)
+        _, scaled_min, scaled_max, tol_vox = self._geometry(env)
+        for _ in self._tracked_batches(env):
+            self._selected_batch(env, scaled_min, scaled_max, tol_vox)
+        return self.connectome
+
     def track_to_file(self, env, path, header=None):
         """``track`` and ``io.streamlines.save`` in one: the output stage
         builds each batch's file body on the device (``select_tracts_file``),
@@ -275,6 +323,9 @@ class Tracker(object):
         0).  Seeds are saved (``save_seeds``) in .trk files only; .tck has no
         properties."""
         from tracktolearn_amd.io import streamlines as sio
+        if self.connectome is not None:
+            raise ValueError('track_to_file packs file records and never materialises the '
+                             'points a connectome reads: use track, or track_connectome')
         fmt = detect_format(path)
         if fmt is None:
             raise ValueError('output must be .trk or .tck')
