@@ -911,6 +911,74 @@ TTL_API int ttl_connectome_accumulate(const int32_t *node, const double *length,
                                       int32_t n_nodes, int64_t *count, int64_t *length_q,
                                       void *hip_stream);
 
+/* Weighted connectome edges (TTL_HAS_TRACT_SAMPLE, TTL_HAS_CONNECTOME_METRIC):
+ * the mean of a scalar volume (FA, MD, AFD) along every streamline, and its sum per edge.
+ * This project's own statement; the reference has no counterpart.  Input is the ragged layout
+ * of ttl_connectome_assign, in the corner-origin voxel coordinates of the volume's grid
+ * (voxel v spans [v, v + 1), its centre is v + 0.5); dims = {X, Y, Z} and lin (double [9],
+ * row-major linear part of voxel -> RAS mm) in host memory.  volume: device float32
+ * [X * Y * Z], word (x * Y + y) * Z + z.  Floats are read as float64 and all arithmetic is
+ * float64 in the written order.
+ *
+ * ttl_tract_sample_mean, for streamline s with points c_0 .. c_{L-1}:
+ *   sample s_j  at p = c_j: u = p - 0.5, i = floor(u) (floor, not truncation: -0.5 is voxel
+ *               -1), f = u - i, g = 1 - f per axis.  The eight corners are i + {0, 1}^3, each
+ *               index clamped to [0, dims_k - 1] (edge replicate; a dimension of 1 reads the
+ *               same voxel twice).  With V(a, b, c) the value at corner (x: a, y: b, z: c),
+ *               z pairs first, then y, then x:
+ *                 Z(a, b) = V(a, b, 0) * gz + V(a, b, 1) * fz
+ *                 Y(a)    = Z(a, 0) * gy + Z(a, 1) * fy
+ *                 s_j     = Y(0) * gx + Y(1) * fx
+ *   not sampled a point that is non-finite, that has some p_k < 0 or p_k > dims_k (the closed
+ *               volume [0, dims] is inside; decided in float64 before any conversion to an
+ *               integer, so a point at 1e30 is simply outside), or with a non-finite value
+ *               among its eight corners (a corner of weight 0 included).
+ *   weights     the trapezoid rule over the arc length in mm: |v_j| is
+ *               ttl_connectome_assign's segment length of lin (c_{j+1} - c_j), but 0 when
+ *               either end is non-finite; |v_{-1}| = |v_{L-1}| = 0; w_j = (|v_{j-1}| + |v_j|)
+ *               * 0.5, so the two end points weigh half their one segment.
+ *   weight[s]   = sum over the sampled j of w_j;
+ *   mean[s]     = (sum over the sampled j of w_j * s_j) / weight[s];
+ *               mean[s] = NaN and weight[s] = 0 when L < 2 or the sum of weights is not > 0
+ *               (nothing sampled, or every sampled point between segments of length 0).
+ *               Both sums are lane partial sums (lane l adds its points j = l, l + 64, ... in
+ *               that order) and then a butterfly, so the order over j is the kernel's.
+ *   tolerance   against the definition in exact arithmetic, with u = 2^-53, B_j the segment
+ *               length taken with |lin| and |c_{j+1} - c_j| (magnitudes, as DESIGN 3.15's A_s),
+ *               W_j = (B_{j-1} + B_j) / 2, S_j = the trilinear sum of |V| and, over the sampled
+ *               j, A = sum W_j, M = sum W_j S_j:  a segment length carries 8 roundings (3.15),
+ *               w_j one more, s_j 9 (g, product and sum on each of three levels), w_j * s_j
+ *               one, a sum of L terms at most L - 1 on any path, the division one:
+ *                 |weight - exact| <= (L + 9) u A
+ *                 |mean - exact|   <= u ((L + 19) M + (L + 9) A M / weight) / weight.
+ * One wavefront per streamline, lanes over the points, 64 a round.  A lane measures |v_j| and
+ * takes |v_{j-1}| from the lane below by a shuffle; lane 0 takes the last lane's of the round
+ * before, carried in a register (the bits a recomputation would give).  The two corners along
+ * z of a pair are adjacent floats (the same float when clamped).  No atomics, no LDS, plain
+ * stores by lane 0.  mean, weight: device double [n].
+ *
+ * ttl_connectome_accumulate_metric: metric_q and metric_n are device int64 [N + 1][N + 1],
+ * ADDED TO, with the cell rule of ttl_connectome_accumulate (a = min, b = max of the row's
+ * nodes, upper triangle, row 0 = unassigned).  A row is skipped when node[s][0] < 0 or it
+ * names a node above N, when mean[s] is non-finite, or when |mean[s] * scale| >= 2^40;
+ * otherwise metric_q[a][b] += llrint(mean[s] * scale) (half to even) and metric_n[a][b] += 1.
+ * scale is a power of two in 2^-60 .. 2^60, so the product is exact short of underflow.  The
+ * mean of an edge is metric_q / scale / metric_n: the mean over its streamlines of their
+ * means.  The wave-level election and the device-scope integer atomics of
+ * ttl_connectome_accumulate: exact, independent of the order and the split of the rows.
+ * Both: TTL_ERR_INVALID, before any HIP call, for a null pointer (except hip_stream), n < 0,
+ * a dim < 1, n_nodes outside 1 .. TTL_CONNECTOME_MAX_NODES, a scale that is not such a power
+ * of two; n == 0 is a successful no-op. */
+#define TTL_HAS_TRACT_SAMPLE 1
+#define TTL_HAS_CONNECTOME_METRIC 1
+TTL_API int ttl_tract_sample_mean(const float *points, const int64_t *offsets, int32_t n,
+                                  const float *volume, const int32_t *dims, const double *lin,
+                                  double *mean /*[n]*/, double *weight /*[n]*/, void *hip_stream);
+TTL_API int ttl_connectome_accumulate_metric(const int32_t *node, const double *mean, int32_t n,
+                                             int32_t n_nodes, double scale,
+                                             int64_t *metric_q, int64_t *metric_n,
+                                             void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

@@ -39,6 +39,8 @@ HAS_ACT_IN_STEP = 1                     # TTL_HAS_ACT_IN_STEP (ttl_env_set_act)
 HAS_CONNECTOME = 1                      # TTL_HAS_CONNECTOME (ttl_connectome_assign / _accumulate)
 CONNECTOME_MAX_NODES, CONNECTOME_MAX_REACH = 4096, 8    # TTL_CONNECTOME_MAX_NODES / _MAX_REACH
 CONNECTOME_LENGTH_SCALE = 1048576.0     # TTL_CONNECTOME_LENGTH_SCALE: 2^20 units per mm
+HAS_TRACT_SAMPLE = 1                    # TTL_HAS_TRACT_SAMPLE (ttl_tract_sample_mean)
+HAS_CONNECTOME_METRIC = 1               # TTL_HAS_CONNECTOME_METRIC (.._accumulate_metric)
 
 
 class TTLError(RuntimeError):
@@ -190,6 +192,12 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p]),
     'ttl_connectome_accumulate': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_tract_sample_mean': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    'ttl_connectome_accumulate_metric': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                   C.c_double, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -12,11 +12,19 @@ tractogram does not depend on the batch split or on the order of arrival:
     con.add_tractogram('tracts.trk')            # or Tracker(..., connectome=con)
     con.matrices()['count']                     # (N, N) int64, symmetric
 
+With ``metrics={'fa': fa_volume}`` every edge also gets the mean of that scalar
+map along its streamlines: ``ttl_tract_sample_mean`` samples the
+volume trilinearly at every point and takes the arc-length weighted mean per
+streamline, ``ttl_connectome_accumulate_metric`` sums those means per edge in
+fixed point, and ``matrices()`` gains ``mean_fa`` and ``fa_n``.  That is one more
+pass over the points per metric.
+
 There is no NumPy fallback: like the rest of the product path this needs the
 library.
 """
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -85,6 +93,122 @@ def accumulate(node, length, n_nodes, count, length_q):
             'ttl_connectome_accumulate')
 
 
+def _lin_of(affine):
+    a = np.asarray(affine, np.float64)
+    if a.shape == (4, 4):
+        a = a[:3, :3]
+    return np.ascontiguousarray(a.reshape(9))
+
+
+def sample_mean(points, offsets, volume, affine):
+    """``ttl_tract_sample_mean`` on device tensors: (mean, weight), each (n,)
+    float64, of the ragged rows ``points`` (M, 3) float32 / ``offsets`` (n + 1,)
+    int64 in corner-origin voxel coordinates of the grid of ``volume`` (an
+    (X, Y, Z) float32 tensor on the device of ``points``; an array is uploaded).
+    ``affine``: the (4, 4) voxel -> RAS mm of that grid, or its (3, 3) linear
+    part.  mean: the trapezoid-rule mean over the arc length in mm of the
+    trilinear samples; NaN (and weight 0) for a row without one."""
+    from tracktolearn_amd.experiment.oracle_validator import launch_ragged
+    n = max(int(offsets.shape[0]) - 1, 0)
+    dev = points.device
+    if not torch.is_tensor(volume):
+        volume = torch.from_numpy(np.ascontiguousarray(np.asarray(volume, np.float32))).to(dev)
+    if volume.dim() != 3 or volume.numel() == 0:
+        raise ValueError(f'a scalar map is a 3-D volume, not of shape {tuple(volume.shape)}')
+    if volume.dtype != torch.float32 or not volume.is_contiguous() or volume.device != dev:
+        raise ValueError('volume must be a contiguous float32 tensor on the device of points')
+    mean = torch.full((n,), float('nan'), dtype=torch.float64, device=dev)
+    weight = torch.zeros(n, dtype=torch.float64, device=dev)
+    if n == 0 or points.shape[0] == 0:      # no launch: an empty tensor has no pointer
+        return mean, weight
+    launch_ragged('ttl_tract_sample_mean', points, offsets, volume.shape,
+                  before=(volume.data_ptr(),),
+                  after=((C.c_double * 9)(*_lin_of(affine)), mean.data_ptr(),
+                         weight.data_ptr()))
+    return mean, weight
+
+
+def accumulate_metric(node, mean, n_nodes, scale, metric_q, metric_n):
+    """``ttl_connectome_accumulate_metric``: llrint(mean * scale) of the scored
+    rows with a finite mean added into ``metric_q``, and 1 into ``metric_n``
+    ((N + 1, N + 1) int64, device), on the current stream of their device."""
+    dev = node.device
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.load().ttl_connectome_accumulate_metric(
+            node.data_ptr(), mean.data_ptr(), int(node.shape[0]), int(n_nodes), float(scale),
+            metric_q.data_ptr(), metric_n.data_ptr(), stream),
+            'ttl_connectome_accumulate_metric')
+
+
+def metric_scale(volume):
+    """The fixed-point scale of a metric volume (float32, as uploaded): with m the
+    largest finite |value| (1 for an all-zero or all-NaN volume) and e the smallest
+    integer with m < 2^e, 2^(39 - e): |mean| * scale < 2^40, and 2^23 streamlines
+    fit in a cell.  The exponent is held to the -60 .. 60 the library takes."""
+    v = np.abs(np.asarray(volume, np.float32).astype(np.float64))
+    v = v[np.isfinite(v)]
+    m = float(v.max()) if v.size and v.max() > 0 else 1.0
+    e = math.frexp(m)[1]                # m = f * 2^e with 0.5 <= f < 1
+    return 2.0 ** min(max(39 - e, -60), 60)
+
+
+def metric_matrices_from(metric_q_upper, metric_n_upper, scale):
+    """(mean (N, N) float64, symmetric, NaN where no streamline contributed; n
+    (N, N) int64) of the two accumulated matrices of one metric."""
+    def symmetric(m):
+        inner = np.asarray(m, np.int64)[1:, 1:]
+        return inner + inner.T - np.diag(np.diag(inner))
+    q, n = symmetric(metric_q_upper), symmetric(metric_n_upper)
+    mean = np.full(q.shape, np.nan)
+    np.divide(q.astype(np.float64) / scale, n, out=mean, where=n > 0)
+    return mean, n
+
+
+def check_metrics(metrics, dims):
+    """name -> contiguous (X, Y, Z) float32 array of the ``metrics`` argument of
+    ``Connectome``: ValueError for an empty name, one with ``=`` (the commands
+    split NAME=FILE there) or a volume that is not of the labels' shape."""
+    out = {}
+    for name, volume in (metrics or {}).items():
+        if not isinstance(name, str) or not name or '=' in name:
+            raise ValueError(f'a metric name is a non-empty string without "=", not {name!r}')
+        data = np.asarray(volume)
+        if data.shape != tuple(dims):
+            raise ValueError(f'metric {name} has shape {data.shape}, the label image '
+                             f'{tuple(dims)}: there is no resampling')
+        out[name] = np.ascontiguousarray(data.astype(np.float32))
+    return out
+
+
+def parse_metric(text):
+    """(name, file) of a ``NAME=FILE`` option; ValueError otherwise."""
+    name, eq, filename = str(text).partition('=')
+    if not eq or not name or not filename:
+        raise ValueError(f'{text!r}: a metric is given as NAME=FILE')
+    return name, filename
+
+
+def load_metric(name, filename, shape, affine, grid_of):
+    """The (X, Y, Z) float32 volume of the NIfTI ``filename``, which must be on
+    the grid (``shape``, ``affine`` to 1e-3) of ``grid_of``: there is no
+    resampling, and the error names both grids."""
+    from tracktolearn_amd.io import nifti
+    img = nifti.load(filename)
+    got = tuple(int(v) for v in img.shape[:3])
+    data = np.asarray(img.get_fdata(dtype=np.float64))
+    if data.ndim == 4 and data.shape[3] == 1:
+        data = data[..., 0]
+    shape = tuple(int(v) for v in shape)
+    affine = np.asarray(affine, np.float64)
+    if data.ndim != 3 or got != shape or not np.allclose(img.affine, affine, atol=1e-3):
+        raise ValueError(
+            f'metric {name} ({filename}: shape {tuple(img.shape)}, affine '
+            f'{np.asarray(img.affine).round(4).tolist()}) is not on the grid of {grid_of} '
+            f'(shape {shape}, affine {affine.round(4).tolist()}): resample it')
+    return data.astype(np.float32)
+
+
 def matrices_from(count_upper, length_q_upper):
     """The public matrices of the two accumulated ones ((N + 1, N + 1) int64,
     upper triangle, row 0 = unassigned): ``count`` (N, N) int64, symmetric;
@@ -128,12 +252,15 @@ def load_labels(labels):
 
 
 class Connectome:
-    """``Connectome(labels, affine, radius_mm=2.0, device='cuda')``: the two
-    device matrices of a label image and what streams into them.  ``labels``:
-    an integer (X, Y, Z) array or a NIfTI file name; ``affine``: the (4, 4)
-    voxel -> RAS mm of its grid (None: the file's own)."""
+    """``Connectome(labels, affine, radius_mm=2.0, device='cuda', metrics=None)``:
+    the two device matrices of a label image and what streams into them.
+    ``labels``: an integer (X, Y, Z) array or a NIfTI file name; ``affine``: the
+    (4, 4) voxel -> RAS mm of its grid (None: the file's own).  ``metrics``: a
+    dict of name -> scalar map, a 3-D array on the labels' grid, uploaded once as
+    float32; each adds two matrices and one sampling pass over the points of
+    every ``add``."""
 
-    def __init__(self, labels, affine, radius_mm=2.0, device='cuda'):
+    def __init__(self, labels, affine, radius_mm=2.0, device='cuda', metrics=None):
         if isinstance(labels, (str, bytes, os.PathLike)):
             from tracktolearn_amd.io import nifti
             img = nifti.load(os.fsdecode(labels))
@@ -148,6 +275,7 @@ class Connectome:
         self.lin = np.ascontiguousarray(self.affine[:3, :3])
         self.radius_mm = float(radius_mm)
         self.reach = reach_for(self.lin, self.radius_mm)
+        volumes = check_metrics(metrics, self.dims)
         _lib.load()
         self.device = torch.device(device)
         self.labels = torch.from_numpy(data.reshape(-1)).to(self.device)
@@ -156,15 +284,30 @@ class Connectome:
         self.length_q = torch.zeros((side, side), dtype=torch.int64, device=self.device)
         self._skipped = torch.zeros((), dtype=torch.int64, device=self.device)
         self._dropped = 0           # rows the intake left out (fewer than 2 points)
+        #: name -> {'volume': (X, Y, Z) float32 on the device, 'scale', 'q', 'n'}
+        self.metrics = {}
+        #: name -> (mean, weight) per row of the latest ``add``
+        self.last_means = {}
+        for name, data in volumes.items():
+            self.metrics[name] = {
+                'volume': torch.from_numpy(data).to(self.device), 'scale': metric_scale(data),
+                'q': torch.zeros((side, side), dtype=torch.int64, device=self.device),
+                'n': torch.zeros((side, side), dtype=torch.int64, device=self.device)}
 
     def add(self, points, offsets):
         """Device tensors in corner-origin voxel coordinates of the label
-        grid: assign, then accumulate.  Returns ``node`` (n, 2) int32."""
+        grid: assign, then accumulate; then, per metric, sample and accumulate
+        (one more pass over the points each).  Returns ``node`` (n, 2) int32."""
         node, length = assign_nodes(points, offsets, self.labels, self.dims, self.lin,
                                     self.radius_mm, self.n_nodes)
         if node.shape[0]:
             accumulate(node, length, self.n_nodes, self.count, self.length_q)
             self._skipped += (node[:, 0] < 0).sum()
+        for name, m in self.metrics.items():
+            mean, weight = sample_mean(points, offsets, m['volume'], self.lin)
+            if node.shape[0]:
+                accumulate_metric(node, mean, self.n_nodes, m['scale'], m['q'], m['n'])
+            self.last_means[name] = (mean, weight)
         return node
 
     def add_tractogram(self, tractogram_or_filename, env=None, in_rasmm=False):
@@ -195,23 +338,34 @@ class Connectome:
         return int(self._skipped.item()) + self._dropped
 
     def matrices(self):
-        return matrices_from(self.count.cpu().numpy(), self.length_q.cpu().numpy())
+        """``matrices_from`` and, per metric, ``mean_<name>`` ((N, N) float64,
+        symmetric: the mean over an edge's streamlines of their means, NaN where
+        none contributed) and ``<name>_n`` (how many did)."""
+        out = matrices_from(self.count.cpu().numpy(), self.length_q.cpu().numpy())
+        for name, m in self.metrics.items():
+            out['mean_' + name], out[name + '_n'] = metric_matrices_from(
+                m['q'].cpu().numpy(), m['n'].cpu().numpy(), m['scale'])
+        return out
 
     def totals(self):
         """What ``prefix.json`` holds."""
         m = self.matrices()
         scored = int(np.triu(m['count']).sum() + m['unassigned_one_end'].sum()
                      + m['unassigned_both'])
-        return {'n_nodes': self.n_nodes, 'radius_mm': self.radius_mm,
-                'reach': [int(r) for r in self.reach], 'streamlines': scored + self.skipped,
-                'scored': scored, 'skipped': self.skipped,
-                'connected': int(np.triu(m['count']).sum()),
-                'unassigned_one_end': int(m['unassigned_one_end'].sum()),
-                'unassigned_both': m['unassigned_both']}
+        out = {'n_nodes': self.n_nodes, 'radius_mm': self.radius_mm,
+               'reach': [int(r) for r in self.reach], 'streamlines': scored + self.skipped,
+               'scored': scored, 'skipped': self.skipped,
+               'connected': int(np.triu(m['count']).sum()),
+               'unassigned_one_end': int(m['unassigned_one_end'].sum()),
+               'unassigned_both': m['unassigned_both']}
+        if self.metrics:
+            out['metrics'] = {name: {'scale': v['scale']} for name, v in self.metrics.items()}
+        return out
 
     def save(self, prefix):
         """``prefix_count.npy``, ``prefix_mean_length.npy``, ``prefix_count.csv``
-        and ``prefix.json`` (the totals, radius and node count)."""
+        and ``prefix.json`` (the totals, radius and node count; the metrics' names
+        and scales); per metric ``prefix_mean_<name>.npy``."""
         m = self.matrices()
         folder = os.path.dirname(os.path.abspath(prefix))
         os.makedirs(folder, exist_ok=True)
@@ -220,8 +374,13 @@ class Connectome:
         np.savetxt(prefix + '_count.csv', m['count'], fmt='%d', delimiter=',')
         with open(prefix + '.json', 'w') as f:
             json.dump(self.totals(), f, indent=2)
-        return [prefix + s for s in ('_count.npy', '_mean_length.npy', '_count.csv', '.json')]
+        for name in self.metrics:
+            np.save(f'{prefix}_mean_{name}.npy', m['mean_' + name])
+        return [prefix + s for s in ('_count.npy', '_mean_length.npy', '_count.csv', '.json')] \
+            + [f'{prefix}_mean_{name}.npy' for name in self.metrics]
 
 
-__all__ = ['Connectome', 'assign_nodes', 'accumulate', 'reach_for', 'matrices_from',
-           'load_labels', 'MAX_NODES', 'MAX_REACH', 'LENGTH_SCALE']
+__all__ = ['Connectome', 'assign_nodes', 'accumulate', 'sample_mean', 'accumulate_metric',
+           'metric_scale', 'metric_matrices_from', 'check_metrics', 'parse_metric',
+           'load_metric', 'reach_for', 'matrices_from', 'load_labels', 'MAX_NODES', 'MAX_REACH',
+           'LENGTH_SCALE']

@@ -8,6 +8,8 @@
 // accumulate: one thread per row; the rows of a wavefront that share a cell of
 // the (N + 1) x (N + 1) matrices are summed in the wave and one lane adds them
 // with one integer atomic per matrix, so the sums do not depend on the order.
+// accumulate_metric: the same for a per-row value (the mean of a scalar map along
+// the streamline, ttl_tract_sample.hip) at a power-of-two scale.
 #include "ttl_internal.h"
 
 namespace {
@@ -183,6 +185,45 @@ __global__ __launch_bounds__(BLOCK) void k_connectome_accumulate(
     }
 }
 
+// accumulate for a per-row value: the election of k_connectome_accumulate, written beside it
+// so that the kernel above stays as it was compiled.  q = llrint(mean * scale) of the rows
+// that count; the rest (not scored, a non-finite mean, |mean * scale| >= 2^40) hold no cell.
+__global__ __launch_bounds__(BLOCK) void k_connectome_accumulate_metric(
+    const int *__restrict__ node, const double *__restrict__ mean, int n, int N, double scale,
+    u64 *__restrict__ metric_q, u64 *__restrict__ metric_n) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    const long long first = (long long)blockIdx.x * BLOCK + (threadIdx.x & ~63);
+    for (long long base = first; base < n; base += stride) {
+        const long long row = base + lane;
+        int cell = -1;
+        long long q = 0;
+        if (row < n) {
+            const int n0 = node[2 * row], n1 = node[2 * row + 1];
+            const double scaled = mean[row] * scale;
+            // a NaN fails the comparison; an infinite mean gives an infinite product
+            if (n0 >= 0 && n1 >= 0 && n0 <= N && n1 <= N && fabs(scaled) < 1099511627776.0) {
+                const int a = n0 < n1 ? n0 : n1, b = n0 < n1 ? n1 : n0;
+                cell = a * (N + 1) + b;
+                q = llrint(scaled);
+            }
+        }
+        u64 todo = __ballot(cell >= 0);
+        while (todo) {
+            const int leader = __builtin_ctzll(todo);
+            const int c = __shfl(cell, leader);
+            const bool mine = cell == c;
+            const u64 group = __ballot(mine);
+            const long long sum = wave_sum(mine ? q : 0ll);
+            if (lane == leader) {
+                atomicAdd(&metric_n[c], (u64)__popcll(group));
+                atomicAdd(&metric_q[c], (u64)sum);
+            }
+            todo &= ~group;
+        }
+    }
+}
+
 bool bad_dims(const int32_t *dims) {
     return !dims || dims[0] < 1 || dims[1] < 1 || dims[2] < 1;
 }
@@ -227,6 +268,28 @@ int ttl_connectome_accumulate(const int32_t *node, const double *length, int32_t
                        dim3((unsigned)(want < ACCUMULATE_GRID ? want : ACCUMULATE_GRID)),
                        dim3(BLOCK), 0, (hipStream_t)hip_stream, node, length, n, n_nodes,
                        (u64 *)count, (u64 *)length_q);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+int ttl_connectome_accumulate_metric(const int32_t *node, const double *mean, int32_t n,
+                                     int32_t n_nodes, double scale, int64_t *metric_q,
+                                     int64_t *metric_n, void *hip_stream) {
+    if (!node || !mean || !metric_q || !metric_n || n < 0 || bad_nodes(n_nodes))
+        return fail(TTL_ERR_INVALID, "ttl_connectome_accumulate_metric: bad arguments");
+    int exponent = 0;
+    // a finite power of two: frexp gives exactly 0.5; (0.5, e) is 2^(e - 1)
+    if (!std::isfinite(scale) || std::frexp(scale, &exponent) != 0.5 || exponent - 1 < -60 ||
+        exponent - 1 > 60)
+        return fail(TTL_ERR_INVALID,
+                    "ttl_connectome_accumulate_metric: scale must be a power of two in "
+                    "2^-60 .. 2^60");
+    if (n == 0) return TTL_OK;
+    const long long want = ((long long)n + BLOCK - 1) / BLOCK;
+    hipLaunchKernelGGL(k_connectome_accumulate_metric,
+                       dim3((unsigned)(want < ACCUMULATE_GRID ? want : ACCUMULATE_GRID)),
+                       dim3(BLOCK), 0, (hipStream_t)hip_stream, node, mean, n, n_nodes, scale,
+                       (u64 *)metric_q, (u64 *)metric_n);
     HIP_TRY(hipGetLastError());
     return TTL_OK;
 }

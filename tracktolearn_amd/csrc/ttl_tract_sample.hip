@@ -1,0 +1,141 @@
+// ttl_tract_sample.hip -- the arc-length weighted mean of a scalar volume along
+// every streamline (restated in include/ttl_hip.h at ttl_tract_sample_mean);
+// part of libttl_hip.so.  One wavefront per streamline of the ragged layout of
+// ttl_tract_coverage, lanes over the points, 64 a round: a lane measures the
+// segment that leaves its point (ttl_connectome_assign's expression), takes the
+// one that arrives from the lane below by a shuffle (lane 0: the last lane's of
+// the round before, carried in a register), samples the volume trilinearly at its
+// point and adds weight and weight * sample to two lane sums; a butterfly sum
+// ends the row.  No atomics, no LDS, plain stores by lane 0.
+#include "ttl_internal.h"
+
+namespace {
+constexpr int BLOCK = TTL_BLOCK;
+
+struct Lin {
+    double m[9];
+};
+
+// butterfly: a + b == b + a, so every lane ends with the same bits
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// row r of lin applied to d: ((m0 x + m1 y) + m2 z)
+__device__ __forceinline__ double lin_row(const Lin &A, int r, const double (&d)[3]) {
+    return (A.m[3 * r] * d[0] + A.m[3 * r + 1] * d[1]) + A.m[3 * r + 2] * d[2];
+}
+
+__device__ __forceinline__ bool finite3(const double (&c)[3]) {
+    return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
+}
+
+// |lin (c1 - c0)| in mm, 0 when an end is non-finite
+__device__ __forceinline__ double segment_mm(const Lin &A, const double (&c0)[3],
+                                             const double (&c1)[3]) {
+    if (!finite3(c0) || !finite3(c1)) return 0.0;
+    const double e[3] = {c1[0] - c0[0], c1[1] - c0[1], c1[2] - c0[2]};
+    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
+    return sqrt((vx * vx + vy * vy) + vz * vz);
+}
+
+// The trilinear sample at p; false when p is not sampled (ttl_hip.h).  The inside
+// test comes before any conversion to an integer; every index is clamped, so no
+// load leaves the volume.
+__device__ __forceinline__ bool sample_at(const double (&p)[3], const float *__restrict__ volume,
+                                          const WalkDims &D, double &value) {
+    int lo[3], hi[3];
+    double f[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (!(p[k] >= 0.0 && p[k] <= (double)D.d[k])) return false;     // a NaN fails too
+        const double u = p[k] - 0.5, i = floor(u);
+        f[k] = u - i;
+        const int v = (int)i, last = D.d[k] - 1;                        // -1 .. dims - 1
+        lo[k] = v < 0 ? 0 : v;
+        hi[k] = v + 1 > last ? last : v + 1;
+    }
+    const double gx = 1.0 - f[0], gy = 1.0 - f[1], gz = 1.0 - f[2];
+    double cy[2];
+    bool finite = true;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        double cz[2];
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const float *line = volume + walk_index(D, a ? hi[0] : lo[0], b ? hi[1] : lo[1], 0);
+            const double v0 = line[lo[2]], v1 = line[hi[2]];
+            finite = finite && isfinite(v0) && isfinite(v1);
+            cz[b] = v0 * gz + v1 * f[2];
+        }
+        cy[a] = cz[0] * gy + cz[1] * f[1];
+    }
+    value = cy[0] * gx + cy[1] * f[0];
+    return finite;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_tract_sample_mean(
+    const float *__restrict__ points, const long long *__restrict__ offsets, int n,
+    const float *__restrict__ volume, WalkDims D, Lin A, double *__restrict__ mean,
+    double *__restrict__ weight) {
+    const int lane = threadIdx.x & 63;
+    wave_rows(n, [&](int row) {
+        const long long o0 = offsets[row], L = offsets[row + 1] - o0;
+        const float *p = points + 3 * o0;
+        double sum_w = 0.0, sum_ws = 0.0;
+        double carry = 0.0;                     // the segment that arrives at lane 0's point
+        for (long long base = 0; base < L; base += 64) {        // wave-uniform bound
+            const long long j = base + lane;
+            double after = 0.0, value = 0.0;    // |v_j|, s_j
+            bool sampled = false;
+            if (j < L) {
+                const float *q = p + 3 * j;
+                const double c[3] = {q[0], q[1], q[2]};
+                if (j < L - 1) {
+                    const double c1[3] = {q[3], q[4], q[5]};
+                    after = segment_mm(A, c, c1);
+                }
+                sampled = sample_at(c, volume, D, value);
+            }
+            double before = __shfl_up(after, 1);                // |v_{j-1}|
+            if (lane == 0) before = carry;
+            carry = __shfl(after, 63);
+            if (sampled) {
+                const double w = (before + after) * 0.5;
+                sum_w += w;
+                sum_ws += w * value;
+            }
+        }
+        sum_w = wave_sum(sum_w);
+        sum_ws = wave_sum(sum_ws);
+        if (lane == 0) {
+            const bool scored = L >= 2 && sum_w > 0.0;
+            mean[row] = scored ? sum_ws / sum_w : __longlong_as_double(0x7ff8000000000000ll);
+            weight[row] = scored ? sum_w : 0.0;
+        }
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int ttl_tract_sample_mean(const float *points, const int64_t *offsets, int32_t n,
+                          const float *volume, const int32_t *dims, const double *lin,
+                          double *mean, double *weight, void *hip_stream) {
+    if (!points || !offsets || !volume || !dims || !lin || !mean || !weight || n < 0 ||
+        dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
+        return fail(TTL_ERR_INVALID, "ttl_tract_sample_mean: bad arguments");
+    if (n == 0) return TTL_OK;
+    const WalkDims D{{dims[0], dims[1], dims[2]}};
+    Lin A;
+    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    hipLaunchKernelGGL(k_tract_sample_mean, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK), 0,
+                       (hipStream_t)hip_stream, points, (const long long *)offsets, n, volume, D,
+                       A, mean, weight);
+    HIP_TRY(hipGetLastError());
+    return TTL_OK;
+}
+
+}  // extern "C"

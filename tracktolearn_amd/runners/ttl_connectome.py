@@ -2,7 +2,8 @@
 """ttl_connectome.py -- the structural connectome of a tractogram on the MI355X.
 
     ttl_connectome.py in_tractogram labels out_prefix
-        [--reference NIFTI] [--radius MM] [--save_assignments] [-f]
+        [--reference NIFTI] [--radius MM] [--metric NAME=FILE ...]
+        [--save_assignments] [-f]
 
 ``labels`` is an integer image (.nii.gz): the values 1 .. N name the nodes.
 Every streamline of 2 points or more gets the node at either end -- the label
@@ -13,8 +14,14 @@ centre within ``--radius`` mm -- and its length in mm (connectome.py, DESIGN
 ``out_prefix_count.csv`` and ``out_prefix.json`` (totals, radius, node count);
 with ``--save_assignments`` also ``out_prefix_nodes.npy``: rows of (index in
 the input, node of the first point, node of the last), 0 = no node, -1 = not
-scored.  A .tck input needs ``--reference``, the anatomy whose grid the labels
-are on; a .trk is read in its header's space unless one is given.
+scored.  Every ``--metric NAME=FILE`` (a scalar map on the labels' grid: FA, MD,
+AFD; there is no resampling) adds ``out_prefix_mean_NAME.npy``: per edge the mean
+over its streamlines of the map's arc-length weighted mean along each (DESIGN
+3.16; NaN where no streamline contributed), and with ``--save_assignments``
+``out_prefix_NAME_streamlines.npy``: rows of (index in the input, mean, weight
+in mm), NaN and 0 without a mean.  A .tck input needs ``--reference``, the
+anatomy whose grid the labels are on; a .trk is read in its header's space
+unless one is given.
 """
 import argparse
 import json
@@ -37,12 +44,22 @@ def parse_args(argv=None):
                         help='Reference anatomy: the grid of the label image.')
     parser.add_argument('--radius', default=2.0, type=float, metavar='MM',
                         help='Search radius round an end outside every node. [%(default)s]')
+    parser.add_argument('--metric', action='append', default=[], metavar='NAME=FILE',
+                        help='Scalar map (.nii.gz) on the grid of the label image; writes\n'
+                             'out_prefix_mean_NAME.npy. May be given several times.')
     parser.add_argument('--save_assignments', action='store_true',
-                        help='Write out_prefix_nodes.npy: (index, node0, node1) per streamline.')
+                        help='Write out_prefix_nodes.npy: (index, node0, node1) per streamline,\n'
+                             'and per metric out_prefix_NAME_streamlines.npy: (index, mean, '
+                             'weight).')
     parser.add_argument('-f', dest='overwrite', action='store_true',
                         help='Force overwriting of the output files.')
     args = parser.parse_args(argv)
-    for f in (args.in_tractogram, args.labels) + ((args.reference,) if args.reference else ()):
+    try:
+        args.metric = metric_options(args.metric)
+    except ValueError as e:
+        parser.error(str(e))
+    for f in (args.in_tractogram, args.labels) + ((args.reference,) if args.reference else ()) \
+            + tuple(f for _, f in args.metric):
         if not os.path.isfile(f):
             parser.error(f'{f} does not exist')
     lower = args.in_tractogram.lower()
@@ -53,10 +70,25 @@ def parse_args(argv=None):
     if not (np.isfinite(args.radius) and args.radius >= 0):
         parser.error('--radius must be >= 0 mm')
     written = OUTPUTS + (('_nodes.npy',) if args.save_assignments else ())
+    for name, _ in args.metric:
+        written += (f'_mean_{name}.npy',) + \
+            ((f'_{name}_streamlines.npy',) if args.save_assignments else ())
     held = [args.out_prefix + s for s in written if os.path.exists(args.out_prefix + s)]
     if held and not args.overwrite:
         parser.error(f'{held[0]} exists; use -f to overwrite')
     return args
+
+
+def metric_options(values):
+    """[(name, file)] of the ``NAME=FILE`` options; ValueError for a malformed
+    one or a name given twice."""
+    from tracktolearn_amd.connectome import parse_metric
+    pairs = [parse_metric(v) for v in values or ()]
+    names = [name for name, _ in pairs]
+    for name in names:
+        if names.count(name) > 1:
+            raise ValueError(f'metric {name} is given more than once')
+    return pairs
 
 
 def scoring_space(labels_img, header, reference, in_tractogram):
@@ -81,14 +113,16 @@ def scoring_space(labels_img, header, reference, in_tractogram):
 
 def main(argv=None):
     args = parse_args(argv)
-    from tracktolearn_amd.connectome import Connectome
+    from tracktolearn_amd.connectome import Connectome, load_metric
     from tracktolearn_amd.experiment.oracle_validator import load_tractogram
     from tracktolearn_amd.io import nifti
     labels_img = nifti.load(args.labels)
     tract, header = load_tractogram(args.in_tractogram)
     affine = scoring_space(labels_img, header, args.reference, args.in_tractogram)
+    metrics = {name: load_metric(name, f, labels_img.shape[:3], labels_img.affine,
+                                 f'the label image {args.labels}') for name, f in args.metric}
     connectome = Connectome(labels_img.get_fdata(dtype=np.float64), affine,
-                            radius_mm=args.radius, device=get_device())
+                            radius_mm=args.radius, device=get_device(), metrics=metrics)
     node, index = connectome.add_tractogram(tract, in_rasmm=True)
     connectome.save(args.out_prefix)
     if args.save_assignments:
@@ -96,6 +130,11 @@ def main(argv=None):
         rows[:, 0] = np.arange(len(rows))
         rows[index, 1:] = node.cpu().numpy()
         np.save(args.out_prefix + '_nodes.npy', rows)
+        for name, (mean, weight) in connectome.last_means.items():
+            rows = np.zeros((len(tract.streamlines), 3), np.float64)
+            rows[:, 0], rows[:, 1] = np.arange(len(rows)), np.nan
+            rows[index, 1], rows[index, 2] = mean.cpu().numpy(), weight.cpu().numpy()
+            np.save(f'{args.out_prefix}_{name}_streamlines.npy', rows)
     print(json.dumps(connectome.totals()))
 
 

@@ -11,7 +11,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--act_include FILE --act_exclude FILE] [--act_mode {act,cmc}]
         [--act_filter {none,exclude,endpoints}] [--act_in_step]
         [--connectome LABELS --connectome_out PREFIX] [--connectome_radius MM]
-        [--connectome_only]
+        [--connectome_only] [--connectome_metric NAME=FILE ...]
 
 With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
 itself (classical deterministic / probabilistic tracking as one GPU kernel,
@@ -29,7 +29,9 @@ byte for byte, with the graphed tracking loop.
 With ``--connectome`` (a label image on the grid of in_mask) the node x node
 matrices of the streamlines that are written (connectome.py) are
 accumulated on the GPU while tracking; ``--connectome_only`` writes no
-tractogram at all.
+tractogram at all.  Every ``--connectome_metric NAME=FILE`` (a scalar map on the
+same grid: FA, MD, AFD) adds PREFIX_mean_NAME.npy, the map's mean along the
+streamlines of every edge.
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -130,6 +132,7 @@ class TrackToLearnTrack(object):
         if self.connectome_radius is None:
             self.connectome_radius = 2.0
         self.connectome_only = bool(track_dto.get('connectome_only'))
+        self.connectome_metric = list(track_dto.get('connectome_metric') or ())
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -228,10 +231,14 @@ class TrackToLearnTrack(object):
         alg = self._load_policy(env)
         connectome = None
         if self.connectome_file:
-            from tracktolearn_amd.connectome import Connectome
-            connectome = Connectome(
-                load_on_mask_grid('--connectome', self.connectome_file, self.in_mask),
-                ref_img.affine, radius_mm=self.connectome_radius, device=self.device)
+            from tracktolearn_amd.connectome import Connectome, load_metric
+            labels = load_on_mask_grid('--connectome', self.connectome_file, self.in_mask)
+            metrics = {name: load_metric(name, f, labels.shape,
+                                         nifti.load(self.connectome_file).affine,
+                                         f'the label image {self.connectome_file}')
+                       for name, f in self.connectome_metric}
+            connectome = Connectome(labels, ref_img.affine, radius_mm=self.connectome_radius,
+                                    device=self.device, metrics=metrics)
         tracker = Tracker(alg, self.n_actor, compress=self.compress,
                           min_length=self.min_length, max_length=self.max_length,
                           save_seeds=self.save_seeds, bidirectional=self.bidirectional,
@@ -399,6 +406,11 @@ def add_track_args(parser):
                             'centre within\nthis distance. [2.0]')
     con_g.add_argument('--connectome_only', action='store_true',
                        help='Write the connectome and no tractogram.')
+    con_g.add_argument('--connectome_metric', action='append', default=None,
+                       metavar='NAME=FILE',
+                       help='Scalar map (.nii.gz, on the grid of the label image): writes '
+                            'PREFIX_mean_NAME.npy,\nits mean along the streamlines of every '
+                            'edge. May be given several times.')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -453,7 +465,17 @@ def parse_args(argv=None):
                 parser.error('--{} is used only with --connectome.'.format(name))
         if args.connectome_only:
             parser.error('--connectome_only is used only with --connectome.')
+        if args.connectome_metric:
+            parser.error('--connectome_metric is used only with --connectome.')
     else:
+        from tracktolearn_amd.runners.ttl_connectome import metric_options
+        try:
+            args.connectome_metric = metric_options(args.connectome_metric)
+        except ValueError as e:
+            parser.error('--connectome_metric: {}.'.format(e))
+        for _, f in args.connectome_metric:
+            if not os.path.isfile(f):
+                parser.error('Input file {} does not exist.'.format(f))
         if not os.path.isfile(args.connectome):
             parser.error('Input file {} does not exist.'.format(args.connectome))
         if args.connectome_out is None:
