@@ -979,6 +979,96 @@ TTL_API int ttl_connectome_accumulate_metric(const int32_t *node, const double *
                                              int64_t *metric_q, int64_t *metric_n,
                                              void *hip_stream);
 
+/* Track density maps (TTL_HAS_TRACT_DENSITY): per voxel, the number of
+ * streamlines passing through it, the mm of streamline lying in it (in total and per RAS
+ * axis: the direction-encoded density) and the number of streamline ends in it -- scilpy's
+ * compute_tract_counts_map / MRtrix's tckmap.  This project's own statement; the reference
+ * has no counterpart.  Input is the ragged layout of ttl_tract_coverage: points are float32
+ * corner-origin voxel coordinates of the MAP's grid (a super-resolution map is fed points
+ * already scaled to its grid), offsets int64 [n + 1]; dims = {X, Y, Z} with X * Y * Z <
+ * 2^31 - 1, lin = double [9], row-major linear part of voxel -> RAS mm.  Floats are read as
+ * float64 and all arithmetic is float64 in the written order.
+ *
+ * For streamline s with points c_0 .. c_{L-1}:
+ *   not added   status[s] = -1 and no map changes when L < 2, when a point is non-finite or
+ *               when the length sum_j |v_j| is not < 2^40 mm (ttl_connectome_assign's
+ *               expressions and butterfly sum); decided before the row adds anything.
+ *   pieces      the walk is ttl_tract_coverage's: same crossings, order and ties.  Per segment
+ *               j (a = c_j, b = c_{j+1}, d = b - a) the merged crossing order cuts [0, 1]
+ *               into pieces; a piece lies in the voxel the walk occupies between two
+ *               consecutive crossings.  The first piece starts at t = 0 in floor(a), the last
+ *               ends at t = 1; only pieces whose voxel is inside the volume exist.  In the
+ *               bounded walk: a visited voxel is entered at its crossing's t and left at the
+ *               t of the next crossing of the merged order -- the next visit, or the crossing
+ *               X that leaves the volume -- or at 1 when there is none; floor(a)'s piece
+ *               starts at 0 when a lies inside, and when a lies outside the first piece
+ *               starts at E.  Every t is (plane - a_i) / d_i.  Tied crossings give pieces of
+ *               length 0 in the voxels between them; those voxels are still visited.
+ *   v_j         = lin d, each row ((m0 x + m1 y) + m2 z); |v_j| = sqrt((vx^2 + vy^2) + vz^2).
+ * The maps are device arrays of [X * Y * Z] words, word (x * Y + y) * Z + z, ADDED TO: the
+ * caller zeroes them once.  Each pointer may be NULL, not all of them.
+ *   count       int32: += 1 for every voxel of V(s), the SET of voxels the row visits
+ *               (floor(c_0) when inside, and every voxel entered); a voxel left and entered
+ *               again, at once or later, counts once.
+ *   length_q    int64: per piece += llrint(((t_hi - t_lo) * |v_j|) * TTL_CONNECTOME_LENGTH_SCALE),
+ *               rounded half to even.
+ *   dec_q       int64 [X * Y * Z][3]: per piece and k in {x, y, z}
+ *               += llrint(((t_hi - t_lo) * fabs(v_jk)) * TTL_CONNECTOME_LENGTH_SCALE).
+ *   ends        int32: += 1 at floor(c_0) and at floor(c_{L-1}), each when inside the volume;
+ *               two ends in one voxel add 2.
+ * All sums are integer atomics of device scope: the maps do not depend on the order of the
+ * rows, their split into calls or the grid.  On rows that are added, (count > 0) is
+ * ttl_tract_coverage's map.
+ *   tolerance   of a piece against the definition in exact arithmetic, u = 2^-53: each t
+ *               carries 3 roundings (plane - a_i, d_i, the division) and is <= 1, their
+ *               difference one more: |(t_hi - t_lo) - exact| <= 7u; |v_j| carries 8 (DESIGN
+ *               3.15) against B_j, the length taken with |lin| and |d|; the product one.  To
+ *               first order |piece - exact| <= 16 u B_j, and 12 u B_jk for a component (4
+ *               roundings per term of a row of lin).  In units of 2^-20 mm, with one unit for
+ *               a llrint that falls on the other side: 1 + 17 u B_j 2^20 (13 for dec_q; the
+ *               17th and 13th cover the second-order terms), summed over a voxel's pieces.
+ *
+ * The set and status (device int32 [n], overwritten).  Only count needs the set; the other
+ * maps are added piece by piece.  With |V(s)| the number of distinct voxels:
+ *    0   |V(s)| <= wave_slots / 2: counted through the wave's set in LDS (also: count NULL)
+ *    1   otherwise, |V(s)| <= spill_slots / 2 and a workspace was given: counted by the
+ *        spill pass of the same call
+ *    2   otherwise: count got NOTHING from this row (all or nothing); the other three maps
+ *        got everything.  The caller calls again for those rows with only count non-null
+ *        and a larger workspace.
+ *   -1   not added.
+ * The thresholds are exact: the tier is a function of |V(s)| alone.  wave_slots: a power of
+ * two in 64 .. TTL_DENSITY_MAX_WAVE_SLOTS, 0 = the default (2048); 4 * wave_slots * 4 bytes
+ * of LDS per workgroup, refused (TTL_ERR_INVALID, after the device was asked: the one refusal
+ * that follows a HIP call, as for ttl_resample_streamlines) when the device does not have them.  spill_slots: 0 or a
+ * power of two in 64 .. 2^26.  workspace: NULL, or device memory of at least
+ * ttl_tract_density_workspace_bytes(spill_slots, n) bytes (0 for arguments out of range),
+ * zeroed once by the caller; every call leaves it zeroed.  With count NULL there is no set
+ * and no spill pass: a workspace is checked as always and then neither read nor written.
+ * Calls that share a workspace must be ordered (one stream).
+ * One wavefront per row, lanes over the segments; open addressing with at most table-size
+ * probes, and no insertion once more than half the table is new keys, so a full table ends
+ * a row's count and never holds a lane.  No float atomics.  TTL_ERR_INVALID, before any HIP
+ * call (but for the LDS above), for a null desc / points / offsets / status, n < 0, bad dims, no map, slots out of
+ * range, a workspace without spill_slots or too small; n == 0 is a successful no-op. */
+#define TTL_HAS_TRACT_DENSITY 1
+#define TTL_DENSITY_MAX_WAVE_SLOTS 8192
+typedef struct {
+    int32_t dims[3];
+    double lin[9];
+    int32_t *count;
+    int64_t *length_q, *dec_q;
+    int32_t *ends;
+    int32_t wave_slots;   /* power of two, 64 .. TTL_DENSITY_MAX_WAVE_SLOTS; 0 = default */
+    int32_t spill_slots;  /* power of two, or 0 */
+    void *workspace;
+    size_t workspace_bytes;
+} ttl_density_desc;
+TTL_API size_t ttl_tract_density_workspace_bytes(int32_t spill_slots, int32_t n_max);
+TTL_API int ttl_tract_density(const ttl_density_desc *desc, const float *points,
+                              const int64_t *offsets, int32_t n, int32_t *status,
+                              void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

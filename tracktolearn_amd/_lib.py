@@ -41,6 +41,9 @@ CONNECTOME_MAX_NODES, CONNECTOME_MAX_REACH = 4096, 8    # TTL_CONNECTOME_MAX_NOD
 CONNECTOME_LENGTH_SCALE = 1048576.0     # TTL_CONNECTOME_LENGTH_SCALE: 2^20 units per mm
 HAS_TRACT_SAMPLE = 1                    # TTL_HAS_TRACT_SAMPLE (ttl_tract_sample_mean)
 HAS_CONNECTOME_METRIC = 1               # TTL_HAS_CONNECTOME_METRIC (.._accumulate_metric)
+HAS_TRACT_DENSITY = 1                   # TTL_HAS_TRACT_DENSITY (ttl_tract_density)
+DENSITY_MAX_WAVE_SLOTS = 8192           # TTL_DENSITY_MAX_WAVE_SLOTS
+DENSITY_WAVE_SLOTS = 2048               # what wave_slots = 0 means
 
 
 class TTLError(RuntimeError):
@@ -140,6 +143,23 @@ class ActDesc(C.Structure):
     ]
 
 
+class DensityDesc(C.Structure):
+    """struct ttl_density_desc (include/ttl_hip.h): the maps of
+    ``ttl_tract_density``, its grid and its set sizes."""
+    _fields_ = [
+        ('dims', C.c_int32 * 3),
+        ('lin', C.c_double * 9),
+        ('count', C.c_void_p),
+        ('length_q', C.c_void_p),
+        ('dec_q', C.c_void_p),
+        ('ends', C.c_void_p),
+        ('wave_slots', C.c_int32),
+        ('spill_slots', C.c_int32),
+        ('workspace', C.c_void_p),
+        ('workspace_bytes', C.c_size_t),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/ttl_hip.h and
 # include/ttl_learner.h declare
 SYMBOLS = {
@@ -198,6 +218,9 @@ SYMBOLS = {
     'ttl_connectome_accumulate_metric': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                    C.c_double, C.c_void_p, C.c_void_p,
                                                    C.c_void_p]),
+    'ttl_tract_density_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'ttl_tract_density': (C.c_int, [C.POINTER(DensityDesc), C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

@@ -282,10 +282,13 @@ __device__ __forceinline__ void walk_first_point(const float *__restrict__ p, co
 // leaves that index inside form one run; the in-volume crossings are the part of the
 // merged order after the last axis enters (E) and up to the first axis leaving (X).  The
 // runs start at E by binary search (t is monotone along a run), so the work is the
-// voxels visited plus O(log dim).  visit(x, y, z) gets the in-volume voxels in walk order.
+// voxels visited plus O(log dim).  visit(x, y, z, t) gets the in-volume voxels in walk
+// order, each with the t of the crossing that enters it.  Returns the t at which the last
+// voxel visited is left when the walk ends: X's, or 1 when no axis leaves the volume (the
+// pieces of ttl_tract_density; 1 as well when nothing is visited).
 template <class Visit>
-__device__ void walk_segment(const float *__restrict__ pa, const float *__restrict__ pb,
-                             const WalkDims &D, Visit visit) {
+__device__ double walk_segment_pieces(const float *__restrict__ pa, const float *__restrict__ pb,
+                                      const WalkDims &D, Visit visit) {
     double a[3], b[3], d[3];
     long long idx[3], cur[3], left[3];
     int step[3];
@@ -293,7 +296,7 @@ __device__ void walk_segment(const float *__restrict__ pa, const float *__restri
     int eax = -1, xax = 3;
     for (int i = 0; i < 3; ++i) {
         const double ai = pa[i], bi = pb[i];
-        if (!isfinite(ai) || !isfinite(bi)) return;
+        if (!isfinite(ai) || !isfinite(bi)) return 1.0;
         a[i] = ai;
         b[i] = bi;
         d[i] = bi - ai;
@@ -305,7 +308,7 @@ __device__ void walk_segment(const float *__restrict__ pa, const float *__restri
         idx[i] = va;
         left[i] = 0;
         if (va == vb) {
-            if (!inside) return;               // this index never enters the volume
+            if (!inside) return 1.0;           // this index never enters the volume
             continue;
         }
         long long first, last, exit_plane = -2;
@@ -324,7 +327,7 @@ __device__ void walk_segment(const float *__restrict__ pa, const float *__restri
         left[i] = count > 0 ? count : 0;
         cur[i] = first;
         if (!inside) {
-            if (left[i] == 0) return;
+            if (left[i] == 0) return 1.0;
             const double t = ((double)first - a[i]) / d[i];
             if (walk_before(et, eax, t, i)) {
                 et = t;
@@ -366,10 +369,20 @@ __device__ void walk_segment(const float *__restrict__ pa, const float *__restri
             if (left[i] && (m < 0 || walk_before(tn[i], i, tn[m], m))) m = i;
         if (m < 0 || walk_before(xt, xax, tn[m], m)) break;
         idx[m] = step[m] > 0 ? cur[m] : cur[m] - 1;
-        walk_visit(D, idx[0], idx[1], idx[2], visit);
+        const double t = tn[m];
+        auto visit_at = [&](int x, int y, int z) { visit(x, y, z, t); };
+        walk_visit(D, idx[0], idx[1], idx[2], visit_at);
         cur[m] += step[m];
         if (--left[m]) tn[m] = ((double)cur[m] - a[m]) / d[m];
     }
+    return xax < 3 ? xt : 1.0;
+}
+
+// ... and for a visitor that needs no t: visit(x, y, z)
+template <class Visit>
+__device__ void walk_segment(const float *__restrict__ pa, const float *__restrict__ pb,
+                             const WalkDims &D, Visit visit) {
+    walk_segment_pieces(pa, pb, D, [&](int x, int y, int z, double) { visit(x, y, z); });
 }
 
 // row-major index of voxel (x, y, z)

@@ -12,6 +12,7 @@ Same command line as TrackToLearn/runners/ttl_track.py:
         [--act_filter {none,exclude,endpoints}] [--act_in_step]
         [--connectome LABELS --connectome_out PREFIX] [--connectome_radius MM]
         [--connectome_only] [--connectome_metric NAME=FILE ...]
+        [--density_map PREFIX] [--density_zoom K] [--density_dec] [--density_only]
 
 With ``--odf_policy`` no agent is loaded: the streamlines follow the fODF
 itself (classical deterministic / probabilistic tracking as one GPU kernel,
@@ -32,6 +33,14 @@ accumulated on the GPU while tracking; ``--connectome_only`` writes no
 tractogram at all.  Every ``--connectome_metric NAME=FILE`` (a scalar map on the
 same grid: FA, MD, AFD) adds PREFIX_mean_NAME.npy, the map's mean along the
 streamlines of every edge.
+
+With ``--density_map PREFIX`` the track density maps of the streamlines that
+are written (density.py) are accumulated the same way on the grid
+of in_mask, ``--density_zoom K`` times finer: PREFIX_count.nii.gz (streamlines
+per voxel), PREFIX_length.nii.gz (mm of streamline per voxel),
+PREFIX_ends.nii.gz, with ``--density_dec`` PREFIX_dec.nii.gz (the mm along x, y
+and z) and PREFIX.json; ``--density_only`` writes no tractogram.  With
+``--compress`` the maps are of the compressed points.
 
 Launch with ``torchrun --nproc-per-node R`` to shard every seed batch over R
 GPUs (volumes replicated, RCCL gather-to-root of the finished tracts, rank 0
@@ -133,6 +142,11 @@ class TrackToLearnTrack(object):
             self.connectome_radius = 2.0
         self.connectome_only = bool(track_dto.get('connectome_only'))
         self.connectome_metric = list(track_dto.get('connectome_metric') or ())
+        # the track density maps of the streamlines that are written
+        self.density_map = track_dto.get('density_map')
+        self.density_zoom = track_dto.get('density_zoom') or 1
+        self.density_dec = bool(track_dto.get('density_dec'))
+        self.density_only = bool(track_dto.get('density_only'))
         self.fa_map = None
         self.device = torch.device('cuda', torch.cuda.current_device()) \
             if torch.cuda.is_available() else get_device()
@@ -239,10 +253,16 @@ class TrackToLearnTrack(object):
                        for name, f in self.connectome_metric}
             connectome = Connectome(labels, ref_img.affine, radius_mm=self.connectome_radius,
                                     device=self.device, metrics=metrics)
+        density = None
+        if self.density_map:
+            from tracktolearn_amd.density import DensityMap
+            mask_shape = tuple(int(v) for v in nifti.load(self.in_mask).shape[:3])
+            density = DensityMap(mask_shape, ref_img.affine, zoom=self.density_zoom,
+                                 device=self.device, dec=self.density_dec)
         tracker = Tracker(alg, self.n_actor, compress=self.compress,
                           min_length=self.min_length, max_length=self.max_length,
                           save_seeds=self.save_seeds, bidirectional=self.bidirectional,
-                          act_filter=self.act_filter, connectome=connectome)
+                          act_filter=self.act_filter, connectome=connectome, density=density)
         # re-derives the step in voxels, the step counts and the neighbourhood
         # radius from the rescaled step (environments/env.py:196-212)
         env.load_subject()
@@ -252,8 +272,9 @@ class TrackToLearnTrack(object):
             env.noise_rng = per_rank_noise_rng(self.random_seed, tracker.rank)
         header = sio.create_tractogram_header(
             ref_img.affine, ref_img.shape[:3], ref_img.get_zooms()[:3])
-        if self.connectome_only:
-            tracker.track_connectome(env)
+        if self.connectome_only or self.density_only:
+            # either walks the batches without writing them and feeds both products
+            (tracker.track_connectome if connectome is not None else tracker.track_density)(env)
             n = None
         else:
             n = tracker.save(env, self.out_tractogram, header, direct=self.direct_output)
@@ -263,7 +284,13 @@ class TrackToLearnTrack(object):
             print('Saved the connectome of {} streamlines ({} nodes, {} connected, {} skipped) '
                   'to {}'.format(totals['streamlines'], totals['n_nodes'], totals['connected'],
                                  totals['skipped'], self.connectome_out))
-        if n is None:           # not rank 0, or --connectome_only
+        if density is not None:
+            density.save(self.density_map)
+            totals = density.totals()
+            print('Saved the density maps of {} streamlines ({} skipped, grid {}) to {}'.format(
+                totals['added'], totals['skipped'], 'x'.join(str(v) for v in totals['dims']),
+                self.density_map))
+        if n is None:           # not rank 0, --connectome_only or --density_only
             return
         print('Saved {} streamlines to {}'.format(n, self.out_tractogram))
 
@@ -411,6 +438,20 @@ def add_track_args(parser):
                        help='Scalar map (.nii.gz, on the grid of the label image): writes '
                             'PREFIX_mean_NAME.npy,\nits mean along the streamlines of every '
                             'edge. May be given several times.')
+    den_g = parser.add_argument_group(
+        'Track density maps',
+        'Streamlines, mm of streamline and ends per voxel of the streamlines that are '
+        'written,\naccumulated on the GPU while tracking (one process only). With --compress '
+        'the maps are\nof the compressed points.')
+    den_g.add_argument('--density_map', type=str, default=None, metavar='PREFIX',
+                       help='Writes PREFIX_count.nii.gz, PREFIX_length.nii.gz, '
+                            'PREFIX_ends.nii.gz and PREFIX.json.')
+    den_g.add_argument('--density_zoom', type=int, default=None, metavar='K',
+                       help='Super-resolution: a grid K times finer than in_mask, 1 .. 8. [1]')
+    den_g.add_argument('--density_dec', action='store_true',
+                       help='Also PREFIX_dec.nii.gz: the mm per voxel along x, y and z.')
+    den_g.add_argument('--density_only', action='store_true',
+                       help='Write the maps and no tractogram.')
     parser.add_argument('--rng_seed', default=1337, type=int,
                         help='Random number generator seed [%(default)s].')
 
@@ -486,6 +527,19 @@ def parse_args(argv=None):
         if args.connectome_radius is not None and not \
                 (np.isfinite(args.connectome_radius) and args.connectome_radius >= 0):
             parser.error('--connectome_radius must be >= 0 mm.')
+    if args.density_map is None:
+        if args.density_zoom is not None:
+            parser.error('--density_zoom is used only with --density_map.')
+        if args.density_dec:
+            parser.error('--density_dec is used only with --density_map.')
+        if args.density_only:
+            parser.error('--density_only is used only with --density_map.')
+    else:
+        if args.density_zoom is not None and not 1 <= args.density_zoom <= 8:
+            parser.error('--density_zoom must be in 1 .. 8.')
+        if args.direct_output:
+            parser.error('--density_map reads the packed points, which --direct_output '
+                         'never makes: drop one of them.')
     if args.odf_policy:
         if args.agent is not None or args.hyperparameters is not None:
             parser.error('--odf_policy tracks without an agent: drop --agent / '

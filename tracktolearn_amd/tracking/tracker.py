@@ -64,7 +64,7 @@ class Tracker(object):
 
     def __init__(self, alg, n_actor, prob=0., compress=0.0, min_length=20,
                  max_length=200, save_seeds=False, device_output=None,
-                 bidirectional=False, act_filter=None, connectome=None):
+                 bidirectional=False, act_filter=None, connectome=None, density=None):
         self.alg = alg
         self.n_actor = n_actor
         self.prob = prob
@@ -105,6 +105,18 @@ class Tracker(object):
                                  'device_output=False has none')
             if self.group_size > 1:
                 raise ValueError('a connectome is not summed across ranks: track it with '
+                                 'one process')
+        #: a ``density.DensityMap`` whose reference grid is the env's: fed like the
+        #: connectome, with the same points.  With ``compress`` the map is of the
+        #: compressed points (the streamlines that are written), whose chords cut
+        #: corners the tracked steps went round
+        self.density = density
+        if density is not None:
+            if device_output is not None and not device_output:
+                raise ValueError('a density map is fed by the device output stage: '
+                                 'device_output=False has none')
+            if self.group_size > 1:
+                raise ValueError('a density map is not summed across ranks: track it with '
                                  'one process')
 
     # ------------------------------------------------------------------ #
@@ -170,21 +182,31 @@ class Tracker(object):
         points, counts, rows = select_tracts(
             env._buf_streamlines[:n], env._buf_lengths[:n], env._buf_flags[:n],
             scaled_min, scaled_max, tol_vox, reject=self._act_reject(env))
-        if self.connectome is not None:
-            self._check_connectome(env)
+        if self.connectome is not None or self.density is not None:
+            self._check_products(env)
             offsets = torch.zeros(counts.shape[0] + 1, dtype=torch.int64, device=counts.device)
             torch.cumsum(counts, 0, out=offsets[1:])
-            self.connectome.add(points + 0.5, offsets)
+            corner = points + 0.5
+            if self.connectome is not None:
+                self.connectome.add(corner, offsets)
+            if self.density is not None:
+                self.density.add(corner, offsets)
         return points, counts, rows
 
-    def _check_connectome(self, env):
+    def _check_products(self, env):
+        """What a connectome and a density map both need of ``env``: the device
+        output stage, and the grid of the tracking mask."""
         if not self._device_output(env):
-            raise ValueError('a connectome is fed by the device output stage, which this '
+            what = 'a connectome' if self.connectome is not None else 'a density map'
+            raise ValueError(f'{what} is fed by the device output stage, which this '
                              'env (host buffers) does not have')
         dims = tuple(int(v) for v in tuple(env.tracking_mask.data.shape)[:3])
-        if dims != tuple(self.connectome.dims):
+        if self.connectome is not None and dims != tuple(self.connectome.dims):
             raise ValueError(f'the connectome\'s label image {tuple(self.connectome.dims)} is '
                              f'not on the grid of the tracking mask {dims}')
+        if self.density is not None and dims != tuple(self.density.ref_dims):
+            raise ValueError(f'the density map\'s reference grid {tuple(self.density.ref_dims)} '
+                             f'is not the grid of the tracking mask {dims}')
 
     def _batch_arrays_host(self, env, scaled_min, scaled_max):
         """``device_output=False``: the length filter as torch expressions on
@@ -210,8 +232,8 @@ class Tracker(object):
             points, keep_sel, seeds = self._batch_arrays(env, scaled_min, scaled_max,
                                                          tol_vox)
         else:
-            if self.connectome is not None:
-                self._check_connectome(env)         # raises: no device output stage
+            if self.connectome is not None or self.density is not None:
+                self._check_products(env)         # raises: no device output stage
             points, keep_sel, seeds = self._batch_arrays_host(env, scaled_min, scaled_max)
         if self.group_size > 1:
             # gather-to-root of exact sizes: only rank 0 consumes the tracts
@@ -300,18 +322,31 @@ class Tracker(object):
         tractogram.affine_to_rasmm = affine
         return tractogram
 
-    def track_connectome(self, env):
-        """``track`` for the connectome alone: every batch is tracked and its
-        ``select_tracts`` result accumulated on the device; nothing is cut into
-        items or downloaded.  Returns the connectome."""
-        if self.connectome is None:
-            raise ValueError('track_connectome needs Tracker(..., connectome=...)')
+    def _track_products(self, env):
+        """``track`` for the products alone: every batch is tracked and its
+        ``select_tracts`` result handed to the connectome and the density map on
+        the device; nothing is cut into items or downloaded."""
         self.alg.agent.eval()
         np.random.shuffle(env.seeds)
         _, scaled_min, scaled_max, tol_vox = self._geometry(env)
         for _ in self._tracked_batches(env):
             self._selected_batch(env, scaled_min, scaled_max, tol_vox)
+
+    def track_connectome(self, env):
+        """``track`` for the connectome alone (``_track_products``; a density map
+        that is attached is fed too).  Returns the connectome."""
+        if self.connectome is None:
+            raise ValueError('track_connectome needs Tracker(..., connectome=...)')
+        self._track_products(env)
         return self.connectome
+
+    def track_density(self, env):
+        """``track`` for the density map alone (``_track_products``; a connectome
+        that is attached is fed too).  Returns the map."""
+        if self.density is None:
+            raise ValueError('track_density needs Tracker(..., density=...)')
+        self._track_products(env)
+        return self.density
 
     def track_to_file(self, env, path, header=None):
         """``track`` and ``io.streamlines.save`` in one: the output stage
@@ -326,6 +361,9 @@ class Tracker(object):
         if self.connectome is not None:
             raise ValueError('track_to_file packs file records and never materialises the '
                              'points a connectome reads: use track, or track_connectome')
+        if self.density is not None:
+            raise ValueError('track_to_file packs file records and never materialises the '
+                             'points a density map reads: use track, or track_density')
         fmt = detect_format(path)
         if fmt is None:
             raise ValueError('output must be .trk or .tck')
