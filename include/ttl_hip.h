@@ -1069,6 +1069,90 @@ TTL_API int ttl_tract_density(const ttl_density_desc *desc, const float *points,
                               const int64_t *offsets, int32_t n, int32_t *status,
                               void *hip_stream);
 
+/* Bundle profiles (TTL_HAS_BUNDLE_PROFILE): the mean and the spread of a scalar
+ * volume at K stations along a bundle -- AFQ's tract profile, scil_bundle_mean_std
+ * --per_point.  This project's own statement; the reference has no counterpart.  Input is
+ * the ragged layout of ttl_tract_coverage in the corner-origin voxel coordinates of the
+ * volume's grid; bundle: device int32 [n], the bundle number of every row
+ * (ttl_tractometer_classify's, or any other); n_bundles = B in 1 .. TTL_PROFILE_MAX_BUNDLES,
+ * nb_points = K in 2 .. TTL_PROFILE_MAX_POINTS; lin (host double [9], row-major linear part
+ * of voxel -> RAS mm) and dims = {X, Y, Z} in host memory.  Floats are read as float64 and
+ * all arithmetic is float64 in the written order.
+ *
+ * Stations.  r_0 .. r_{K-1} of a row are the float32 points ttl_resample_streamlines gives
+ * for it at nb_points = K, the same bits (the one resampler, with the cumulative arc
+ * length replayed from 64 lane prefixes): equidistant in arc length IN VOXEL UNITS.  On an
+ * anisotropic grid they are not equidistant in mm.
+ *
+ * ttl_bundle_orient.  model: device float32 [B][K][3], a model line per bundle, in the
+ * rows' coordinates.  Row s with b = bundle[s] and L points TAKES PART iff 0 <= b < B,
+ * L >= 2, every point is finite and every resampled coordinate has |r_kc * scale| < 2^40.
+ * Any other row: flip[s] = 0, mdf[s] = NaN, nothing is added.  A row that takes part:
+ *   d(a, m)   = |lin (a - m)|: with e = a - m per axis, v_i = (lin_i0 e_0 + lin_i1 e_1) +
+ *               lin_i2 e_2, sqrt((v_0 v_0 + v_1 v_1) + v_2 v_2) -- ttl_tract_sample_mean's
+ *               segment length of m -> a, without its test for non-finite ends;
+ *   D         = (sum_k d(r_k, m_k)) / K,   F = (sum_k d(r_{K-1-k}, m_k)) / K, each sum as
+ *               lane partial sums (lane l adds k = l, l + 64, ... in that order) and then
+ *               ttl_tract_sample_mean's butterfly;
+ *   flip[s]   = F < D, strictly: a tie, or a comparison with a NaN, leaves the row as it is;
+ *   mdf[s]    = flip ? F : D, the mean distance to the model in mm;
+ *   o_k       = flip ? r_{K-1-k} : r_k;
+ *   sum_q[b][k][c] += llrint((double)o_kc * scale) (half to even; the product is exact),
+ *   sum_n[b]  += 1.
+ * A model with a non-finite entry follows from this: D and F both contain that station, so
+ * both are NaN or +Inf, F < D is false, flip is 0, mdf is that non-finite value (NaN for a
+ * NaN entry), and the row is still summed.
+ *   tolerance against the definition in exact arithmetic, u = 2^-53, A the mean over k of
+ *               the distance taken with magnitudes (|lin| and |a - m|, as DESIGN 3.15's
+ *               A_s): a distance carries 8 roundings (3.15's segment), a sum of K terms at
+ *               most K - 1 on any path, the division one: |D - exact| <= (K + 8) u A, and
+ *               the same for F with its own A.  flip is decided when |D - F| exceeds the sum
+ *               of the two bounds.
+ * sum_q: device int64 [B][K][3], sum_n: device int64 [B], both ADDED TO; flip: device int32
+ * [n]; mdf: device double [n].  The centroid of bundle b is sum_q[b] / scale / sum_n[b].
+ *
+ * ttl_bundle_profile.  volume: device float32 [X * Y * Z], word (x * Y + y) * Z + z.  A row
+ * takes part iff 0 <= b < B, L >= 2 and every point is finite.  Station k of the row is o_k
+ * = flip[s] != 0 ? r_{K-1-k} : r_k; its value v is ttl_tract_sample_mean's sample s_j at
+ * p = o_k with that function's not-sampled rules (the closed volume, edge replicate, a
+ * non-finite corner).  A station COUNTS iff it is sampled, |v * scale| < 2^40 and
+ * |(v * v) * scale_sq| < 2^40; then
+ *   sum_q[b][k]  += llrint(v * scale),
+ *   sum_qq[b][k] += llrint((v * v) * scale_sq)   (the square of v, not of the rounded value),
+ *   count[b][k]  += 1.
+ * All three: device int64 [B][K], ADDED TO.  values: device double [n][K] or NULL; v where
+ * the station is sampled (counted or not), NaN elsewhere; rows that take no part all NaN.
+ * mean = sum_q / scale / count, variance = sum_qq / scale_sq / count - mean^2.
+ *
+ * Both: scale (and scale_sq) a power of two in 2^-60 .. 2^60, the rule of
+ * ttl_connectome_accumulate_metric.  TTL_ERR_INVALID, before any HIP call, for a null
+ * pointer (except values and hip_stream), n < 0, B or K out of range, a dim < 1, a scale
+ * that is not such a power of two; n == 0 is a successful no-op.
+ *
+ * One wavefront per streamline over a capped grid; the row is resampled into the wave's LDS
+ * (64 * 8 bytes of prefixes + 12 K bytes of stations, whatever the row's length); the model
+ * row is read from global memory by lane k.  The gates of a row (all points finite, every
+ * coordinate in range) are wave-wide ballots taken before the first add: a row is added
+ * completely or not at all.  Lane k owns stations k, k + 64, ...; a wave takes a contiguous
+ * range of the call's rows and keeps its lanes' integer sums in registers while consecutive
+ * rows have the same bundle; device-scope 64-bit atomics are issued when the bundle changes
+ * and after the wave's last row.  Integer sums: the result is that of one atomic per
+ * addend, whatever the flush points, the order or the split of the rows. */
+#define TTL_HAS_BUNDLE_PROFILE 1
+#define TTL_PROFILE_MAX_POINTS 256
+#define TTL_PROFILE_MAX_BUNDLES 64
+TTL_API int ttl_bundle_orient(const float *points, const int64_t *offsets, int32_t n,
+                              const int32_t *bundle, int32_t n_bundles, int32_t nb_points,
+                              const float *model, const double *lin, double scale,
+                              int32_t *flip /*[n]*/, double *mdf /*[n]*/, int64_t *sum_q,
+                              int64_t *sum_n, void *hip_stream);
+TTL_API int ttl_bundle_profile(const float *points, const int64_t *offsets, int32_t n,
+                               const int32_t *bundle, const int32_t *flip, int32_t n_bundles,
+                               int32_t nb_points, const float *volume, const int32_t *dims,
+                               double scale, double scale_sq, int64_t *sum_q, int64_t *sum_qq,
+                               int64_t *count, double *values /*[n][K] or NULL*/,
+                               void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

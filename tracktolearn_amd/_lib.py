@@ -44,6 +44,8 @@ HAS_CONNECTOME_METRIC = 1               # TTL_HAS_CONNECTOME_METRIC (.._accumula
 HAS_TRACT_DENSITY = 1                   # TTL_HAS_TRACT_DENSITY (ttl_tract_density)
 DENSITY_MAX_WAVE_SLOTS = 8192           # TTL_DENSITY_MAX_WAVE_SLOTS
 DENSITY_WAVE_SLOTS = 2048               # what wave_slots = 0 means
+HAS_BUNDLE_PROFILE = 1                  # TTL_HAS_BUNDLE_PROFILE (ttl_bundle_orient / _profile)
+PROFILE_MAX_POINTS, PROFILE_MAX_BUNDLES = 256, 64   # TTL_PROFILE_MAX_POINTS / _MAX_BUNDLES
 
 
 class TTLError(RuntimeError):
@@ -221,6 +223,14 @@ SYMBOLS = {
     'ttl_tract_density_workspace_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'ttl_tract_density': (C.c_int, [C.POINTER(DensityDesc), C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p]),
+    'ttl_bundle_orient': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.POINTER(C.c_double), C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    'ttl_bundle_profile': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
+                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

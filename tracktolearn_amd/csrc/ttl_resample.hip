@@ -2,7 +2,7 @@
 // TractOracle-Net scoring path (TrackToLearn/oracles/oracle.py:52,70:
 // dipy set_number_of_points(streamlines, 128)); part of libttl_hip.so.
 // One wavefront per streamline and ONE statement of the algorithm,
-// resample_row(): float64 segment lengths -> blocked wave scan of the
+// resample_row() (ttl_internal.h, shared with ttl_bundle_profile.hip): float64 segment lengths -> blocked wave scan of the
 // cumulative arc length -> each lane places its target points by binary search
 // and interpolates linearly inside the segment, the last point kept exactly.
 // It is parameterised by how the cumulative arc length is kept: CumStored
@@ -22,14 +22,13 @@
 namespace {
 constexpr int BLOCK = TTL_BLOCK;
 
-// Dynamic LDS of a launch whose waves keep `per_wave` bytes each, and this wave's part of it
-__host__ __device__ inline size_t wave_lds_bytes(size_t per_wave) {
-    return (size_t)(BLOCK / 64) * ((per_wave + 15) & ~(size_t)15);
-}
-__device__ __forceinline__ char *wave_lds(size_t per_wave) {
-    extern __shared__ __align__(16) char lds_all[];
-    return lds_all + (size_t)(threadIdx.x >> 6) * ((per_wave + 15) & ~(size_t)15);
-}
+// resample_row() and its cumulative arc lengths: ttl_internal.h
+using ttl_shared::CumReplayed;
+using ttl_shared::CumStored;
+using ttl_shared::resample_row;
+using ttl_shared::wave_lds;
+using ttl_shared::wave_lds_bytes;
+
 // ... per wave: k_resample cum [max_len] doubles; k_oracle_segments cum [n_pts] doubles,
 // pts [3 n_pts] floats, res [3 nb] floats; k_oracle_segments_packed pre [64] doubles,
 // res [3 nb] floats
@@ -38,148 +37,6 @@ __host__ __device__ inline size_t segments_lds(int n_pts, int nb) {
     return (size_t)n_pts * 8 + (size_t)n_pts * 12 + (size_t)nb * 12;
 }
 __host__ __device__ inline size_t packed_lds(int nb) { return (size_t)64 * 8 + (size_t)nb * 12; }
-
-// float64 length of segment j of the float32 points p
-template <class I>
-__device__ __forceinline__ double seg_len(const float *__restrict__ p, I j) {
-    const double dx = (double)p[3 * (j + 1) + 0] - (double)p[3 * j + 0];
-    const double dy = (double)p[3 * (j + 1) + 1] - (double)p[3 * j + 1];
-    const double dz = (double)p[3 * (j + 1) + 2] - (double)p[3 * j + 2];
-    return sqrt((dx * dx + dy * dy) + dz * dz);
-}
-
-// the sum of `local` over the lanes below this one: inclusive Hillis-Steele scan
-// over the lanes, minus the lane's own
-__device__ __forceinline__ double lanes_below(double local, int lane) {
-    double before = local;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double up = __shfl_up(before, off);
-        if (lane >= off) before = before + up;
-    }
-    return before - local;
-}
-
-// The cumulative arc length cum[0 .. nseg] of a row, by a blocked scan: lane l owns the
-// contiguous segments [l per, (l + 1) per), cum[j + 1] = local_j + before, where local_j
-// is the lane's running sum and `before` the sum of the lower lanes.  Two ways to keep it,
-// with the same members: build() from the points, at(m) = cum[m], and count_le(target,
-// nseg) = #{m in [0, nseg) : cum[m + 1] <= target} as the binary search finds it.
-//
-// Stored: every value in this wave's LDS.
-struct CumStored {
-    using Index = int;
-    double *cum;                                // [nseg + 1]
-    __device__ __forceinline__ void build(const float *__restrict__ p, int nseg, int lane) {
-        const int per = (nseg + 63) >> 6;
-        const int lo = min(lane * per, nseg), hi = min(lo + per, nseg);
-        double local = 0.0;
-        for (int j = lo; j < hi; ++j) {
-            local = local + seg_len(p, j);
-            cum[j + 1] = local;                 // within-block prefix for now
-        }
-        const double before = lanes_below(local, lane);
-        for (int j = lo; j < hi; ++j) cum[j + 1] = cum[j + 1] + before;
-        if (lane == 0) cum[0] = 0.0;
-    }
-    __device__ __forceinline__ double at(int m) const { return cum[m]; }
-    __device__ __forceinline__ int count_le(double target, int nseg) const {
-        int a = 0, b = nseg;
-        while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (cum[mid + 1] <= target) a = mid + 1;
-            else b = mid;
-        }
-        return a;
-    }
-};
-
-// Replayed, for rows of any length: LDS holds the 64 exclusive lane prefixes only.  A
-// value cum[m] is recomputed on demand by re-walking its owner lane's block, which gives
-// the bits CumStored stores (local_j + before).  The target search replays CumStored's
-// binary search probe by probe while the interval spans several lane blocks (cum may step
-// back by an ulp at a block boundary, where `before` comes from a subtraction); inside
-// one block cum is non-decreasing, so the rest of that search is the first m with
-// cum[m + 1] > target, found by one walk of the block.
-struct CumReplayed {
-    using Index = long long;
-    double *pre;                                // [64]
-    const float *p = nullptr;                   // the row and its segments per lane: build()
-    long long per = 1;
-    __device__ __forceinline__ void build(const float *__restrict__ points, long long nseg,
-                                          int lane) {
-        p = points;
-        per = nseg > 0 ? (nseg + 63) >> 6 : 1;
-        const long long lo = min((long long)lane * per, nseg), hi = min(lo + per, nseg);
-        double local = 0.0;
-        for (long long j = lo; j < hi; ++j) local = local + seg_len(p, j);
-        pre[lane] = lanes_below(local, lane);
-    }
-    __device__ __forceinline__ double at(long long m) const {
-        if (m < 1) return 0.0;
-        const long long seg = m - 1, owner = seg / per;
-        double local = 0.0;
-        for (long long j = owner * per; j <= seg; ++j) local = local + seg_len(p, j);
-        return local + pre[owner];
-    }
-    __device__ __forceinline__ long long count_le(double target, long long nseg) const {
-        long long a = 0, b = nseg;
-        while (a < b) {
-            if (a / per == (b - 1) / per) {     // one block: cum is monotone here
-                const long long owner = a / per;
-                double acc = 0.0;
-                long long first = b;
-                for (long long j = owner * per; j < b; ++j) {
-                    acc = acc + seg_len(p, j);
-                    if (j >= a && acc + pre[owner] > target) {
-                        first = j;
-                        break;
-                    }
-                }
-                return first;
-            }
-            const long long mid = (a + b) >> 1;
-            if (at(mid + 1) <= target) a = mid + 1;
-            else b = mid;
-        }
-        return a;
-    }
-};
-
-// One wave resamples the nseg + 1 points p to nb points at equal arc length: 3 nb floats
-// to dst (LDS or global), visible to the whole wave on return; `cum` may then be rebuilt.
-template <class Cum>
-__device__ __forceinline__ void resample_row(Cum cum, const float *__restrict__ p,
-                                             typename Cum::Index nseg, int nb, float *dst,
-                                             int lane) {
-    using Index = typename Cum::Index;
-    cum.build(p, nseg, lane);
-    wave_sync();
-    const double total = cum.at(nseg);
-    for (int k = lane; k < nb; k += 64) {
-        float x, y, z;
-        if (k == nb - 1 || nseg == 0) {         // the last point is kept exactly
-            x = p[3 * nseg + 0];
-            y = p[3 * nseg + 1];
-            z = p[3 * nseg + 2];
-        } else {
-            const double target = total * ((double)k / (double)(nb - 1));
-            const Index j = min(cum.count_le(target, nseg), nseg - 1);
-            const double c0 = cum.at(j), c1 = cum.at(j + 1);
-            const double den = c1 - c0;
-            const double r = den > 0.0 ? (target - c0) / den : 0.0;
-            const double ax = p[3 * j + 0], ay = p[3 * j + 1], az = p[3 * j + 2];
-            const double bx = p[3 * j + 3], by = p[3 * j + 4], bz = p[3 * j + 5];
-            x = (float)(ax + r * (bx - ax));
-            y = (float)(ay + r * (by - ay));
-            z = (float)(az + r * (bz - az));
-        }
-        dst[3 * k + 0] = x;
-        dst[3 * k + 1] = y;
-        dst[3 * k + 2] = z;
-    }
-    wave_sync();
-}
 
 // The network's input of a row: the float32 differences of its nb resampled points `res`
 // (LDS), which the next row may overwrite on return

@@ -12,69 +12,8 @@
 namespace {
 constexpr int BLOCK = TTL_BLOCK;
 
-struct Lin {
-    double m[9];
-};
-
-// butterfly: a + b == b + a, so every lane ends with the same bits
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// row r of lin applied to d: ((m0 x + m1 y) + m2 z)
-__device__ __forceinline__ double lin_row(const Lin &A, int r, const double (&d)[3]) {
-    return (A.m[3 * r] * d[0] + A.m[3 * r + 1] * d[1]) + A.m[3 * r + 2] * d[2];
-}
-
-__device__ __forceinline__ bool finite3(const double (&c)[3]) {
-    return isfinite(c[0]) && isfinite(c[1]) && isfinite(c[2]);
-}
-
-// |lin (c1 - c0)| in mm, 0 when an end is non-finite
-__device__ __forceinline__ double segment_mm(const Lin &A, const double (&c0)[3],
-                                             const double (&c1)[3]) {
-    if (!finite3(c0) || !finite3(c1)) return 0.0;
-    const double e[3] = {c1[0] - c0[0], c1[1] - c0[1], c1[2] - c0[2]};
-    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
-    return sqrt((vx * vx + vy * vy) + vz * vz);
-}
-
-// The trilinear sample at p; false when p is not sampled (ttl_hip.h).  The inside
-// test comes before any conversion to an integer; every index is clamped, so no
-// load leaves the volume.
-__device__ __forceinline__ bool sample_at(const double (&p)[3], const float *__restrict__ volume,
-                                          const WalkDims &D, double &value) {
-    int lo[3], hi[3];
-    double f[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (!(p[k] >= 0.0 && p[k] <= (double)D.d[k])) return false;     // a NaN fails too
-        const double u = p[k] - 0.5, i = floor(u);
-        f[k] = u - i;
-        const int v = (int)i, last = D.d[k] - 1;                        // -1 .. dims - 1
-        lo[k] = v < 0 ? 0 : v;
-        hi[k] = v + 1 > last ? last : v + 1;
-    }
-    const double gx = 1.0 - f[0], gy = 1.0 - f[1], gz = 1.0 - f[2];
-    double cy[2];
-    bool finite = true;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        double cz[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const float *line = volume + walk_index(D, a ? hi[0] : lo[0], b ? hi[1] : lo[1], 0);
-            const double v0 = line[lo[2]], v1 = line[hi[2]];
-            finite = finite && isfinite(v0) && isfinite(v1);
-            cz[b] = v0 * gz + v1 * f[2];
-        }
-        cy[a] = cz[0] * gy + cz[1] * f[1];
-    }
-    value = cy[0] * gx + cy[1] * f[0];
-    return finite;
-}
+// Lin, wave_sum, lin_row, segment_mm and sample_at: ttl_internal.h
+using namespace ttl_shared;
 
 __global__ __launch_bounds__(BLOCK) void k_tract_sample_mean(
     const float *__restrict__ points, const long long *__restrict__ offsets, int n,

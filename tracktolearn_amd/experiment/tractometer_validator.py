@@ -613,9 +613,13 @@ class TractometerValidator(Validator):
         ``{}`` without a streamline of >= 2 points."""
         return self._score(*self.corner_voxels(tractogram_or_filename, env))
 
-    def score_loaded(self, tractogram, affine):
-        """``score`` of what ``load`` returned."""
-        return self._score(*corner_voxels(tractogram, affine, in_rasmm=True), affine)
+    def score_loaded(self, tractogram, affine, return_intake=False):
+        """``score`` of what ``load`` returned.  ``return_intake``: (result,
+        (points, offsets, index)) -- the rows that were scored, for a caller that
+        goes on with them (``bundle`` of the result numbers these rows)."""
+        intake = corner_voxels(tractogram, affine, in_rasmm=True)
+        result = self._score(*intake, affine)
+        return (result, intake) if return_intake else result
 
     def _score(self, points, offsets, index, affine):
         n = len(offsets) - 1

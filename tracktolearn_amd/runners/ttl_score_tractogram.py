@@ -3,6 +3,7 @@
 
     ttl_score_tractogram.py in_tractogram scoring_data out_dir
         [--reference NIFTI] [--dilate_endpoints K] [--compute_ic] [--save_bundles] [-f]
+        [--profile NAME=MAP ...] [--profile_points K] [--profile_max_mdf MM]
 
 ``scoring_data`` holds ``scil_scoring_config.json`` and its masks, as for
 ``sac_auto_train.py --tractometer_validator``.  The streamlines are segmented
@@ -16,7 +17,11 @@ its data_per_streamline: ``segmented_VB/<bundle>_VS``,
 ``segmented_IB/<roiA>__<roiB>_IC`` and ``NC`` (everything else, rows of fewer
 than 2 points included, which are not scored); empty files are not written.
 A .tck input needs ``--reference``; a .trk is scored in its header's space
-unless one is given.
+unless one is given.  With ``--profile NAME=MAP`` (repeatable; MAP a .nii.gz on
+the scoring grid) the valid bundles are also profiled from the same intake
+(bundle_profile.py): ``out_dir/profiles.json`` (per bundle the
+mean, std and count of every map at K stations; null where there is none) and
+``out_dir/profiles_centroids.npy`` ((bundles, K, 3) float64, RAS mm).
 """
 import argparse
 import json
@@ -45,14 +50,47 @@ def parse_args(argv=None):
                         help='Also segment the invalid connections (IC, IS, IB).')
     parser.add_argument('--save_bundles', action='store_true',
                         help='Write the segmented streamlines next to results.json.')
+    parser.add_argument('--profile', action='append', default=[], metavar='NAME=MAP',
+                        help='Also profile the valid bundles along their length on the scalar\n'
+                             'map MAP (.nii.gz on the scoring grid); repeatable.')
+    parser.add_argument('--profile_points', default=None, type=int, metavar='K',
+                        help='Stations per bundle, 2 .. 256. [100]')
+    parser.add_argument('--profile_max_mdf', default=None, type=float, metavar='MM',
+                        help='Leave streamlines further than MM mm from the model they were\n'
+                             'oriented against (the centroid of the pass before) out of the\n'
+                             'profiles.')
     parser.add_argument('-f', dest='overwrite', action='store_true',
                         help='Force overwriting of the output files.')
     args = parser.parse_args(argv)
     if not os.path.isfile(args.in_tractogram):
         parser.error(f'{args.in_tractogram} does not exist')
+    if not args.profile and (args.profile_points is not None or
+                             args.profile_max_mdf is not None):
+        parser.error('--profile_points and --profile_max_mdf go only with --profile')
+    args.profile = parse_metrics(parser, args.profile)
+    if args.profile_points is None:
+        args.profile_points = 100
+    if not 2 <= args.profile_points <= 256:
+        parser.error('--profile_points must be in 2 .. 256')
     if os.path.exists(os.path.join(args.out_dir, 'results.json')) and not args.overwrite:
         parser.error(f'{args.out_dir} holds results already; use -f to overwrite')
     return args
+
+
+def parse_metrics(parser, pairs):
+    """{name: file} of the NAME=MAP arguments; a parser error for a malformed or
+    repeated name or a file that does not exist."""
+    out = {}
+    for pair in pairs:
+        name, eq, path = pair.partition('=')
+        if not (name and eq and path):
+            parser.error(f'{pair}: a map is given as NAME=MAP')
+        if name in out:
+            parser.error(f'{name}: given twice')
+        if not os.path.isfile(path):
+            parser.error(f'{path} does not exist')
+        out[name] = path
+    return out
 
 
 def split(result, n_input):
@@ -87,6 +125,25 @@ def save_bundles(tract, header, groups, out_dir, ext):
         sio.save(part, os.path.join(out_dir, name + ext), header)
 
 
+def write_profiles(args, validator, affine, intake, result):
+    """profiles.json and profiles_centroids.npy of the valid bundles of ``result``,
+    from the rows ``intake`` = (points, offsets, index) that were scored."""
+    import torch
+
+    from tracktolearn_amd.bundle_profile import BundleProfiles, json_ready
+    from tracktolearn_amd.io import nifti
+    profiles = BundleProfiles(validator.dims, affine, list(result['bundles']),
+                              nb_points=args.profile_points, device=get_device(),
+                              max_mdf=args.profile_max_mdf)
+    profiles.fit(torch.from_numpy(intake[0]), torch.from_numpy(intake[1]),
+                 torch.from_numpy(np.asarray(result['bundle'], np.int32)))
+    for name, path in args.profile.items():
+        profiles.add_metric(name, np.asarray(nifti.load(path).get_fdata(), np.float32))
+    with open(os.path.join(args.out_dir, 'profiles.json'), 'w') as f:
+        json.dump(json_ready(profiles.profiles()), f, indent=2, allow_nan=False)
+    np.save(os.path.join(args.out_dir, 'profiles_centroids.npy'), profiles.centroids_rasmm())
+
+
 def main(argv=None):
     args = parse_args(argv)
     from tracktolearn_amd.experiment.tractometer_validator import TractometerValidator
@@ -94,10 +151,16 @@ def main(argv=None):
                                      dilate_endpoints=args.dilate_endpoints,
                                      device=get_device(), compute_ic=args.compute_ic)
     tract, header, affine = validator.load(args.in_tractogram)
-    result = validator.score_loaded(tract, affine)
+    profiled = None
+    if args.profile:        # one intake for the scores and the profiles
+        result, profiled = validator.score_loaded(tract, affine, return_intake=True)
+    else:
+        result = validator.score_loaded(tract, affine)
     os.makedirs(args.out_dir, exist_ok=True)
     with open(os.path.join(args.out_dir, 'results.json'), 'w') as f:
         json.dump({k: v for k, v in result.items() if k not in ARRAYS}, f, indent=2)
+    if result and args.profile:
+        write_profiles(args, validator, affine, profiled, result)
     if not result:
         print(f'{args.in_tractogram}: no streamline of 2 points or more, nothing scored')
     elif args.save_bundles:
