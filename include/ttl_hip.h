@@ -1153,6 +1153,59 @@ TTL_API int ttl_bundle_profile(const float *points, const int64_t *offsets, int3
                                int64_t *count, double *values /*[n][K] or NULL*/,
                                void *hip_stream);
 
+/* Bundle recognition (TTL_HAS_BUNDLE_RECOGNIZE): for every streamline the
+ * nearest of M model lines by the minimum-average-direct-flip distance (MDF), the direction
+ * and the nearest model of another bundle -- the assignment step of RecoBundles /
+ * QuickBundles.  This project's own statement; the reference has no counterpart.  Input is
+ * the ragged layout and the coordinates of ttl_bundle_orient; models: device float32
+ * [M][K][3] in the rows' coordinates, n_models = M in 1 .. TTL_RECOGNIZE_MAX_MODELS,
+ * nb_points = K in 2 .. TTL_PROFILE_MAX_POINTS; label: device int32 [M], the bundle of every
+ * model, any values (negative and repeated ones too), or NULL: label_m = m; lin: host
+ * double [9] as above.
+ *
+ * Row s with L points TAKES PART iff L >= 2 and every point is finite (no fixed-point gate:
+ * nothing is summed into integers).  Its stations r_0 .. r_{K-1} are ttl_bundle_orient's,
+ * the same bits.  For a row that takes part and model m, with ttl_bundle_orient's d(a, b):
+ *   D_m       = (sum_k d(r_k, m_k)) / K,   F_m = (sum_k d(r_{K-1-k}, m_k)) / K, each sum
+ *               sequential: ((d_0 + d_1) + d_2) + ... in increasing k from 0.0 + d_0, which
+ *               is d_0 -- K - 1 roundings, then the division;
+ *   f_m       = F_m < D_m, strictly: a tie, or a comparison with a NaN, gives 0;
+ *   delta_m   = f_m ? F_m : D_m.
+ *   tolerance ttl_bundle_orient's, unchanged: |D_m - exact| <= (K + 8) u A, F_m with its own
+ *               A; f_m is decided when |D_m - F_m| exceeds the sum of the two bounds.
+ * A model with a non-finite station has D_m and F_m both NaN or +Inf, as there.
+ *   best[s]      = the m of the smallest delta_m that is not a NaN; among equal delta_m the
+ *                  lowest m.  +Inf may win.
+ *   flip[s]      = f_best,   mdf[s] = delta_best;
+ *   runner_up[s] = the smallest delta_m that is not a NaN over the m with label_m !=
+ *                  label_best; NaN when there is none.
+ * A row that takes no part, or for which every delta_m is a NaN: best = -1, flip = 0, mdf =
+ * NaN, runner_up = NaN.  best, flip: device int32 [n]; mdf: device double [n]; runner_up:
+ * device double [n] or NULL.  Every output is written for every row.  The minimum of
+ * doubles is exact and the sums are per (row, model) pair, so the outputs are the same bits
+ * whatever the order of the rows, the split into calls or, with indices mapped back and no
+ * tie, the order of the models.
+ *
+ * TTL_ERR_INVALID, before any HIP call, for a null pointer (except label, runner_up and
+ * hip_stream), n < 0, M or K out of range; n == 0 is a successful no-op.
+ *
+ * A workgroup of 256 threads takes 8 consecutive rows, 2 per wave, resampled into the
+ * wave's LDS (64 * 8 bytes of prefixes + 2 * 12 K bytes of stations); the models pass
+ * through an LDS tile of 64 models x min(K, 32) stations, station-major ([k][c][model], 65
+ * words per line), shared by the 4 waves: a lane owns a model, keeps the 2 sums of each of
+ * its wave's 2 rows in registers across the station chunks, and every model station read
+ * feeds 4 distances.  Lane states (nearest, nearest of another label) are merged by a
+ * butterfly of the lexicographic (delta, m) minimum. */
+#define TTL_HAS_BUNDLE_RECOGNIZE 1
+#define TTL_RECOGNIZE_MAX_MODELS 4096
+TTL_API int ttl_bundle_recognize(const float *points, const int64_t *offsets, int32_t n,
+                                 const float *models /*[M][K][3]*/,
+                                 const int32_t *label /*[M] or NULL*/, int32_t n_models,
+                                 int32_t nb_points, const double *lin /*host [9]*/,
+                                 int32_t *best /*[n]*/, int32_t *flip /*[n]*/,
+                                 double *mdf /*[n]*/, double *runner_up /*[n] or NULL*/,
+                                 void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

@@ -46,6 +46,8 @@ DENSITY_MAX_WAVE_SLOTS = 8192           # TTL_DENSITY_MAX_WAVE_SLOTS
 DENSITY_WAVE_SLOTS = 2048               # what wave_slots = 0 means
 HAS_BUNDLE_PROFILE = 1                  # TTL_HAS_BUNDLE_PROFILE (ttl_bundle_orient / _profile)
 PROFILE_MAX_POINTS, PROFILE_MAX_BUNDLES = 256, 64   # TTL_PROFILE_MAX_POINTS / _MAX_BUNDLES
+HAS_BUNDLE_RECOGNIZE = 1                # TTL_HAS_BUNDLE_RECOGNIZE (ttl_bundle_recognize)
+RECOGNIZE_MAX_MODELS = 4096             # TTL_RECOGNIZE_MAX_MODELS
 
 
 class TTLError(RuntimeError):
@@ -231,6 +233,9 @@ SYMBOLS = {
                                      C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32),
                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_bundle_recognize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                       C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
