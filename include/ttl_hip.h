@@ -1206,6 +1206,78 @@ TTL_API int ttl_bundle_recognize(const float *points, const int64_t *offsets, in
                                  double *mdf /*[n]*/, double *runner_up /*[n] or NULL*/,
                                  void *hip_stream);
 
+/* Streamline-based linear registration, the cost (TTL_HAS_BUNDLE_REGISTER):
+ * the bundle-minimum distance (BMD; Garyfallidis 2015) between A fixed and B moving lines
+ * under each of T candidate transforms, in one launch -- the function and, by a central
+ * difference, the gradient that a quasi-Newton optimiser asks for.  This project's own
+ * statement; the reference has no counterpart.  fixed: device float32 [A][K][3], moving:
+ * device float32 [B][K][3], stations already resampled to nb_points = K in 2 ..
+ * TTL_PROFILE_MAX_POINTS, both in the corner-origin voxel coordinates of one grid;
+ * n_fixed = A and n_moving = B in 1 .. TTL_REGISTER_MAX_LINES; xf: DEVICE double [T][12],
+ * n_xf = T in 1 .. TTL_REGISTER_MAX_TRANSFORMS, xf[t] a row-major 3 x 4 affine x in those
+ * coordinates; lin: host double [9] as above.  Floats are read as float64 and all
+ * arithmetic is float64 in the written order, nothing fused.
+ *
+ * Station k of moving line j under transform t, per axis c, NOT rounded to float32:
+ *   m'_c      = ((x_c0 m_0 + x_c1 m_1) + x_c2 m_2) + x_c3.
+ * A fixed line TAKES PART iff its K stations are finite; a moving line takes part under t
+ * iff its K stations are finite and so is every m' of it.  A transform with a non-finite
+ * entry leaves no moving line that takes part.  For a fixed line i and a moving line j that
+ * take part, with ttl_bundle_orient's d(a, b) and ttl_bundle_recognize's sums (sequential in
+ * k from 0.0 + d_0, then the division), the fixed line's stations a_k in the place of the
+ * row's and m'_k in the place of the model's:
+ *   D         = (sum_k d(a_k, m'_k)) / K,   F = (sum_k d(a_{K-1-k}, m'_k)) / K,
+ *   delta_ij  = F < D (strictly) ? F : D.
+ *   row_min[t][i] = the smallest delta_ij that is not a NaN over the j that take part,
+ *   col_min[t][j] = the smallest delta_ij that is not a NaN over the i that take part;
+ *               NaN (0x7ff8000000000000) for a line that takes no part or has no such
+ *               partner.  A minimum of doubles is exact, so both are the same bits
+ *               whatever the order of the lines or the split of the T transforms into calls.
+ *   cost[t]   = 0.25 * (s * s), s = mean(row_min[t]) + mean(col_min[t]), each mean over the
+ *               entries that are not NaN: lane partial sums (lane l of 64 adds entries l,
+ *               l + 64, ... in that order), ttl_tract_sample_mean's butterfly, the division
+ *               by their number; NaN when either side has none.  cost depends on the order
+ *               of the lines through these sums only.
+ *   tolerance against the definition in exact arithmetic, u = 2^-53, magnitudes as for
+ *               ttl_bundle_orient: a coordinate of m' carries at most 4 roundings on any
+ *               path (a product and three adds), stated with room for the higher orders as
+ *               |m'_c - exact| <= 6 u M_c, M_c = (|x_c0||m_0| + |x_c1||m_1|) + |x_c2||m_2| +
+ *               |x_c3|; d is 1-Lipschitz in |lin| e, so with G the mean over k of
+ *               |(|lin| M_k)| and A the mean over k of the distance taken with magnitudes,
+ *               |D - exact| <= b_D = (K + 8) u A + 6 u G, F with its own A: delta_ij lies in
+ *               [min(D - b_D, F - b_F), min(D + b_D, F + b_F)] of the exact D and F, and
+ *               row_min and col_min between the minima of those lower and of those upper
+ *               ends over their pairs, an interval of width w.  A mean of n entries
+ *               carries at most ceil(n / 64) + 6 roundings: with e_r = mean(w) + (ceil(A /
+ *               64) + 6) u mean(row_min), e_c likewise and e_s = e_r + e_c + u s,
+ *               |cost - exact| <= (2 s e_s + e_s e_s) / 4 + 2 u cost.
+ * row_min: device double [T][A]; col_min: device double [T][B]; cost: device double [T];
+ * every output is written for every t.
+ *
+ * TTL_ERR_INVALID, before any HIP call, for a null pointer (except hip_stream), A, B, T or
+ * K out of range.
+ *
+ * Three stream-ordered steps: col_min is set to the all-ones pattern, which is above the
+ * bits of every distance (distances are +0 or larger: their order as doubles is their
+ * order as unsigned integers); a workgroup of 256 threads takes 8 consecutive fixed lines
+ * of one transform, 2 per wave, their stations in the wave's LDS (2 * 12 K bytes); the
+ * moving set passes through an LDS tile of 64 lines x min(K, 32) float64 stations (16 for K
+ * > 128), station-major ([k][c][line], 65 doubles per line), transformed while it is
+ * staged; a lane owns a moving line and keeps the 2 sums of each of its wave's 2 fixed
+ * lines across the station chunks.  row_min is a butterfly of the lanes' running minima and
+ * a plain store; col_min is the minimum over the 4 waves in LDS and one 64-bit atomic
+ * unsigned minimum per moving line and workgroup.  A closing launch of one wave per
+ * transform turns the columns nothing lowered into the NaN and computes cost. */
+#define TTL_HAS_BUNDLE_REGISTER 1
+#define TTL_REGISTER_MAX_TRANSFORMS 64
+#define TTL_REGISTER_MAX_LINES 1048576
+TTL_API int ttl_bundle_register_cost(const float *fixed /*[A][K][3]*/, int32_t n_fixed,
+                                     const float *moving /*[B][K][3]*/, int32_t n_moving,
+                                     int32_t nb_points, const double *xf /*device [T][12]*/,
+                                     int32_t n_xf, const double *lin /*host [9]*/,
+                                     double *row_min /*[T][A]*/, double *col_min /*[T][B]*/,
+                                     double *cost /*[T]*/, void *hip_stream);
+
 /* OracleReward's sparse bonus (oracle_reward.py:84-93) for the rows of
  * ttl_env_stopped(): term[0 .. n_active) = 0, then term[row_q] = bonus where
  * scores[q] > 0.5 (q < n_scored <= n_stopped; the rest was not scored), and

@@ -48,6 +48,8 @@ HAS_BUNDLE_PROFILE = 1                  # TTL_HAS_BUNDLE_PROFILE (ttl_bundle_ori
 PROFILE_MAX_POINTS, PROFILE_MAX_BUNDLES = 256, 64   # TTL_PROFILE_MAX_POINTS / _MAX_BUNDLES
 HAS_BUNDLE_RECOGNIZE = 1                # TTL_HAS_BUNDLE_RECOGNIZE (ttl_bundle_recognize)
 RECOGNIZE_MAX_MODELS = 4096             # TTL_RECOGNIZE_MAX_MODELS
+HAS_BUNDLE_REGISTER = 1                 # TTL_HAS_BUNDLE_REGISTER (ttl_bundle_register_cost)
+REGISTER_MAX_TRANSFORMS, REGISTER_MAX_LINES = 64, 1048576   # TTL_REGISTER_MAX_TRANSFORMS / _LINES
 
 
 class TTLError(RuntimeError):
@@ -236,6 +238,10 @@ SYMBOLS = {
     'ttl_bundle_recognize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'ttl_bundle_register_cost': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_void_p, C.c_int32,
+                                           C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     'ttl_oracle_bonus': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     'ttl_env_harvest_wait': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,

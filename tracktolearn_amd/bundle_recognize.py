@@ -14,8 +14,9 @@ needs no scoring masks:
     got['bundle']                       # (streamlines of the file,) int32, -1: in no bundle
     atlas.summary()                     # per bundle n, mdf_mean, n_gated
 
-The atlas is taken to be in the subject's space: there is no registration.
-There is no NumPy fallback: like the rest of the product path this needs the
+The atlas is taken to be in the subject's space; one that is not is fitted first
+by ``bundle_register.register_atlas`` and moved with
+``BundleAtlas.transformed``.  There is no NumPy fallback: like the rest of the product path this needs the
 library.
 """
 import ctypes as C
@@ -264,6 +265,17 @@ class BundleAtlas:
                          float('nan'),
                          'n_gated': int(((last['won'] == b) & ~kept).sum())}
         return out
+
+    def transformed(self, matrix_ras):
+        """A new atlas on the same grid with every model line moved by the (4, 4)
+        RAS-mm ``matrix_ras`` (``bundle_register.register_atlas``'s ``matrix``): the
+        same labels and names, the stations computed in float64 and stored as
+        float32."""
+        from tracktolearn_amd.bundle_register import to_voxel
+        v = to_voxel(np.asarray(matrix_ras, np.float64).reshape(4, 4), self.affine)
+        moved = self.models_vox.astype(np.float64) @ v[:, :3].T + v[:, 3]
+        return BundleAtlas(self.dims, self.affine, moved, self.names, label=self.label,
+                           device=self.device)
 
     def one_model_per_label(self):
         """(labels, K, 3) float32, the model of every label in label order, when

@@ -17,7 +17,8 @@ SOURCES = [os.path.join(HERE, f) for f in
            ('ttl_hip.hip', 'ttl_state.hip', 'ttl_peaks.hip', 'ttl_resample.hip', 'ttl_order.hip', 'ttl_learner.hip',
             'ttl_oracle_net.hip', 'ttl_coverage.hip', 'ttl_tract.hip', 'ttl_tractometer.hip',
             'ttl_odf_policy.hip', 'ttl_act.hip', 'ttl_connectome.hip', 'ttl_tract_sample.hip',
-            'ttl_tract_density.hip', 'ttl_bundle_profile.hip', 'ttl_bundle_recognize.hip')]
+            'ttl_tract_density.hip', 'ttl_bundle_profile.hip', 'ttl_bundle_recognize.hip',
+            'ttl_bundle_register.hip')]
 HEADERS = [os.path.join(ROOT, 'include', 'ttl_hip.h'),
            os.path.join(ROOT, 'include', 'ttl_learner.h'),
            os.path.join(HERE, 'ttl_internal.h')]

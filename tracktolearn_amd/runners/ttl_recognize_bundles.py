@@ -4,10 +4,18 @@ lines, on the MI355X.
 
     ttl_recognize_bundles.py in_tractogram reference atlas out_prefix
         [--atlas_labels IDS.npy --nb_points K] [--atlas_names NAMES.json] [--max_mdf MM]
-        [--max_ratio R] [--save_bundles] [--profile NAME=MAP ...] [-f]
+        [--max_ratio R] [--save_bundles] [--profile NAME=MAP ...]
+        [--register {rigid,similarity,affine} [--register_max_fixed N]
+         [--register_no_progressive]] [-f]
 
 ``reference`` is the subject's anatomy (.nii.gz); the atlas is taken to be in its
-space.  ``atlas`` is an ``out_prefix_centroids.npy`` of ttl_bundle_profile.py
+space unless ``--register`` fits it to the tractogram first (bundle_register.py,
+DESIGN 3.20: the transform that minimises the bundle-minimum distance between at
+most ``--register_max_fixed`` streamlines and the model lines, through translation,
+rigid and similarity up to the kind asked for unless ``--register_no_progressive``);
+what follows then uses the moved atlas, and ``out_prefix_registration.json`` holds
+the matrix (atlas mm -> subject mm), the parameters, the kind, the centre, the costs
+before and after and the number of evaluations.  ``atlas`` is an ``out_prefix_centroids.npy`` of ttl_bundle_profile.py
 ((bundles, K, 3) float64, RAS mm: one model line per bundle), or a .trk / .tck of
 model lines with ``--atlas_labels`` (the bundle number of every line) resampled to
 ``--nb_points`` stations.  ``--atlas_names``: a JSON list of bundle names, or a
@@ -39,6 +47,7 @@ from tracktolearn_amd.utils.torch_utils import get_device
 
 OUTPUTS = ('_bundles.npy', '_recognized.npy', '_recognized.json')
 PROFILE_OUTPUTS = ('_profiles.json', '_centroids.npy', '_centroids.trk')
+REGISTER_OUTPUT = '_registration.json'
 RECORD = np.dtype([('model', '<i4'), ('flip', '<i4'), ('mdf', '<f8'), ('runner_up', '<f8')])
 
 
@@ -65,9 +74,23 @@ def parse_args(argv=None):
     parser.add_argument('--profile', action='append', default=[], metavar='NAME=MAP',
                         help='Also the tract profiles of a scalar map (.nii.gz on the\n'
                              'reference grid); repeatable.')
+    parser.add_argument('--register', default=None, choices=('rigid', 'similarity', 'affine'),
+                        help='Fit the atlas to the tractogram first (streamline-based linear\n'
+                             'registration); also out_prefix_registration.json.')
+    parser.add_argument('--register_max_fixed', default=None, type=int, metavar='N',
+                        help='Streamlines of the tractogram the fit uses at most. [4096]')
+    parser.add_argument('--register_no_progressive', action='store_true',
+                        help='Fit --register at once, not translation -> rigid -> ... first.')
     parser.add_argument('-f', dest='overwrite', action='store_true',
                         help='Force overwriting of the output files.')
     args = parser.parse_args(argv)
+    if args.register is None and (args.register_max_fixed is not None or
+                                  args.register_no_progressive):
+        parser.error('--register_max_fixed and --register_no_progressive only with --register')
+    if args.register_max_fixed is None:
+        args.register_max_fixed = 4096
+    if args.register_max_fixed < 1:
+        parser.error('--register_max_fixed must be 1 or more')
     for f in (args.in_tractogram, args.reference, args.atlas, args.atlas_labels,
               args.atlas_names):
         if f is not None and not os.path.isfile(f):
@@ -90,7 +113,8 @@ def parse_args(argv=None):
         if value is not None and not value > 0:
             parser.error(f'--{name} must be positive')
     args.profile = parse_metrics(parser, args.profile)
-    written = OUTPUTS + (PROFILE_OUTPUTS if args.profile else ())
+    written = OUTPUTS + (PROFILE_OUTPUTS if args.profile else ()) + \
+        ((REGISTER_OUTPUT,) if args.register else ())
     held = [args.out_prefix + s for s in written if os.path.exists(args.out_prefix + s)]
     if held and not args.overwrite:
         parser.error(f'{held[0]} exists; use -f to overwrite')
@@ -134,13 +158,26 @@ def main(argv=None):
                 names = read_names(json.load(f))
         atlas = BundleAtlas.from_tractogram(args.reference, args.atlas, label, names,
                                             args.nb_points, device=device)
-    models = atlas.one_model_per_label()
-    if args.profile and (models is None or len(atlas.names) > 64):
+    if args.profile and (atlas.one_model_per_label() is None or len(atlas.names) > 64):
         raise ValueError('--profile needs an atlas of one model line per bundle, 64 bundles at '
                          'most')
-    got = atlas.recognize(tract, in_rasmm=True, max_mdf=args.max_mdf, max_ratio=args.max_ratio)
     folder = os.path.dirname(os.path.abspath(args.out_prefix))
     os.makedirs(folder, exist_ok=True)
+    if args.register:
+        from tracktolearn_amd.bundle_register import register_atlas
+        fit = register_atlas(atlas, tract, in_rasmm=True, kind=args.register,
+                             progressive=not args.register_no_progressive,
+                             max_fixed=args.register_max_fixed)
+        atlas = fit['atlas']
+        record = {'kind': fit['kind'], 'matrix': fit['matrix'].tolist(),
+                  'params': fit['params'].tolist(), 'centre': fit['centre'].tolist(),
+                  'cost_before': fit['cost_before'], 'cost_after': fit['cost_after'],
+                  'evaluations': fit['evaluations'], 'n_fixed': fit['n_fixed'],
+                  'n_moving': fit['n_moving']}
+        with open(args.out_prefix + REGISTER_OUTPUT, 'w') as f:
+            json.dump(json_ready(record), f, indent=2, allow_nan=False)
+    models = atlas.one_model_per_label()
+    got = atlas.recognize(tract, in_rasmm=True, max_mdf=args.max_mdf, max_ratio=args.max_ratio)
     np.save(args.out_prefix + OUTPUTS[0], got['bundle'])
     record = np.zeros(len(got['bundle']), RECORD)
     for key in RECORD.names:
