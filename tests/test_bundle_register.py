@@ -499,9 +499,10 @@ def _straight(rng, n, K):
 @pytest.mark.parametrize('K,lin_name', [(3, 'axis'), (20, 'oblique'), (65, 'anisotropic')])
 def test_identity_agrees_with_bundle_recognize(K, lin_name):
     """Under the identity row_min is ttl_bundle_recognize's mdf with the fixed
-    lines as its rows and the moving set as its models, within twice the bound
-    (the width of the reference's interval).  The rows are lines the resampler
-    leaves as they are."""
+    lines as its rows and the moving set as its models, bit for bit: the two
+    kernels run one statement of the tile walk (the same distance, sum order and
+    flip rule), ((1 p0 + 0 p1) + 0 p2) + 0 is p0, and the rows are lines the
+    resampler leaves as they are."""
     from ref_oracle_validator import resample_blocked
     from tracktolearn_amd.bundle_recognize import bundle_recognize
     rng = np.random.default_rng(K)
@@ -520,8 +521,7 @@ def test_identity_agrees_with_bundle_recognize(K, lin_name):
     assert not np.isnan(mdf).any()
     width = f64(r['row_hi'][0] - r['row_lo'][0])
     print('largest |row_min - mdf| / width', float((np.abs(got['row_min'][0] - mdf) / width).max()))
-    assert (np.abs(got['row_min'][0].astype(LD) - mdf.astype(LD)) <=
-            r['row_hi'][0] - r['row_lo'][0]).all()
+    assert np.array_equal(_bits(got['row_min'][0]), _bits(mdf))
 
 
 @pytest.mark.gpu

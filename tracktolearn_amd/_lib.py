@@ -7,6 +7,8 @@ There is no CPU fallback: if the shared library is missing or does not load,
 import ctypes as C
 import os
 
+import numpy as np
+
 # PyTorch-ROCm ships its own HIP runtime (torch/lib/libamdhip64.so, SONAME
 # libamdhip64.so.7).  It must be in the process BEFORE libttl_hip.so is
 # dlopen-ed so that the dynamic loader binds our NEEDED libamdhip64.so.7 to
@@ -420,3 +422,29 @@ def check(code, what=''):
     if code != 0:
         msg = load().ttl_last_error().decode('utf-8', 'replace')
         raise TTLError(f'{what} failed ({code}): {msg}')
+
+
+def ragged_rows(points, offsets):
+    """n of the ragged rows an entry takes, or ValueError: ``points`` (P, 3) float32 and
+    ``offsets`` (n + 1,) int64, contiguous tensors on one device."""
+    if not (torch.is_tensor(points) and points.dtype == torch.float32 and points.dim() == 2 and
+            points.shape[1] == 3 and points.is_contiguous()):
+        raise ValueError('points must be a contiguous (P, 3) float32 tensor')
+    if not (torch.is_tensor(offsets) and offsets.dtype == torch.int64 and offsets.dim() == 1 and
+            offsets.is_contiguous() and offsets.device == points.device):
+        raise ValueError('offsets must be a contiguous (n + 1,) int64 tensor on the device of '
+                         'points')
+    return max(int(offsets.shape[0]) - 1, 0)
+
+
+def lin9(lin):
+    """The ``lin[9]`` of an entry from the (3, 3) linear part of voxel -> RAS mm or its 9 values."""
+    lin = np.asarray(lin, np.float64)
+    if lin.size != 9:
+        raise ValueError(f'lin must be (3, 3), not {lin.shape}')
+    return (C.c_double * 9)(*lin.reshape(9))
+
+
+def stream_of(device):
+    """The ``hip_stream`` of an entry: torch's current stream of ``device``."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

@@ -47,14 +47,7 @@ def _is_scale(scale):
 
 
 def _check_rows(points, offsets, bundle, n_bundles, nb_points):
-    if not (torch.is_tensor(points) and points.dtype == torch.float32 and points.dim() == 2 and
-            points.shape[1] == 3 and points.is_contiguous()):
-        raise ValueError('points must be a contiguous (M, 3) float32 tensor')
-    if not (torch.is_tensor(offsets) and offsets.dtype == torch.int64 and offsets.dim() == 1 and
-            offsets.is_contiguous() and offsets.device == points.device):
-        raise ValueError('offsets must be a contiguous (n + 1,) int64 tensor on the device of '
-                         'points')
-    n = max(int(offsets.shape[0]) - 1, 0)
+    n = _lib.ragged_rows(points, offsets)
     if not (torch.is_tensor(bundle) and bundle.dtype == torch.int32 and bundle.is_contiguous() and
             tuple(bundle.shape) == (n,) and bundle.device == points.device):
         raise ValueError(f'bundle must be a contiguous ({n},) int32 tensor on the device of points')
@@ -73,7 +66,7 @@ def _check_sum(name, t, shape, dev, dtype=torch.int64):
 
 
 def bundle_orient(points, offsets, bundle, n_bundles, nb_points, model, lin, scale, sum_q, sum_n):
-    """``ttl_bundle_orient`` on device tensors: the ragged rows ``points`` (M, 3)
+    """``ttl_bundle_orient`` on device tensors: the ragged rows ``points`` (P, 3)
     float32 / ``offsets`` (n + 1,) int64 with their bundle numbers ``bundle``
     (n,) int32, oriented against ``model`` (B, K, 3) float32; the oriented
     stations are added into ``sum_q`` (B, K, 3) int64 at the power of two
@@ -86,17 +79,16 @@ def bundle_orient(points, offsets, bundle, n_bundles, nb_points, model, lin, sca
     _check_sum('sum_n', sum_n, (B,), dev)
     if not _is_scale(scale):
         raise ValueError(f'scale must be a power of two in 2^-60 .. 2^60, not {scale!r}')
-    lin_c = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
+    lin_c = _lib.lin9(lin)
     flip = torch.zeros(n, dtype=torch.int32, device=dev)
     mdf = torch.full((n,), float('nan'), dtype=torch.float64, device=dev)
     if n == 0 or points.shape[0] == 0:      # no launch: an empty tensor has no pointer
         return flip, mdf
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_bundle_orient(
             points.data_ptr(), offsets.data_ptr(), n, bundle.data_ptr(), B, K, model.data_ptr(),
             lin_c, float(scale), flip.data_ptr(), mdf.data_ptr(), sum_q.data_ptr(),
-            sum_n.data_ptr(), stream), 'ttl_bundle_orient')
+            sum_n.data_ptr(), _lib.stream_of(dev)), 'ttl_bundle_orient')
     return flip, mdf
 
 
@@ -125,12 +117,11 @@ def bundle_profile(points, offsets, bundle, flip, n_bundles, nb_points, volume, 
         return out
     dims_c = (C.c_int32 * 3)(*(int(v) for v in volume.shape))
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_bundle_profile(
             points.data_ptr(), offsets.data_ptr(), n, bundle.data_ptr(), flip.data_ptr(), B, K,
             volume.data_ptr(), dims_c, float(scale), float(scale_sq), sum_q.data_ptr(),
-            sum_qq.data_ptr(), count.data_ptr(), out.data_ptr() if values else None, stream),
-            'ttl_bundle_profile')
+            sum_qq.data_ptr(), count.data_ptr(), out.data_ptr() if values else None,
+            _lib.stream_of(dev)), 'ttl_bundle_profile')
     return out
 
 

@@ -19,7 +19,6 @@ by ``bundle_register.register_atlas`` and moved with
 ``BundleAtlas.transformed``.  There is no NumPy fallback: like the rest of the product path this needs the
 library.
 """
-import ctypes as C
 import json
 import os
 
@@ -42,15 +41,7 @@ def bundle_recognize(points, offsets, models, lin, label=None, runner_up=False):
     model (None: every model is its own); ``lin``: the (3, 3) linear part of
     voxel -> RAS mm.  Returns (best (n,) int32, flip (n,) int32, mdf (n,)
     float64, runner_up (n,) float64 or None)."""
-    if not (torch.is_tensor(points) and points.dtype == torch.float32 and points.dim() == 2 and
-            points.shape[1] == 3 and points.is_contiguous()):
-        raise ValueError('points must be a contiguous (P, 3) float32 tensor')
-    dev = points.device
-    if not (torch.is_tensor(offsets) and offsets.dtype == torch.int64 and offsets.dim() == 1 and
-            offsets.is_contiguous() and offsets.device == dev):
-        raise ValueError('offsets must be a contiguous (n + 1,) int64 tensor on the device of '
-                         'points')
-    n = max(int(offsets.shape[0]) - 1, 0)
+    n, dev = _lib.ragged_rows(points, offsets), points.device
     if not (torch.is_tensor(models) and models.dtype == torch.float32 and models.dim() == 3 and
             models.shape[2] == 3 and models.is_contiguous() and models.device == dev):
         raise ValueError('models must be a contiguous (M, K, 3) float32 tensor on the device of '
@@ -64,10 +55,7 @@ def bundle_recognize(points, offsets, models, lin, label=None, runner_up=False):
             torch.is_tensor(label) and label.dtype == torch.int32 and label.is_contiguous() and
             tuple(label.shape) == (M,) and label.device == dev):
         raise ValueError(f'label must be a contiguous ({M},) int32 tensor on the device of points')
-    lin = np.asarray(lin, np.float64)
-    if lin.size != 9:
-        raise ValueError(f'lin must be (3, 3), not {lin.shape}')
-    lin_c = (C.c_double * 9)(*lin.reshape(9))
+    lin_c = _lib.lin9(lin)
     best = torch.full((n,), -1, dtype=torch.int32, device=dev)
     flip = torch.zeros(n, dtype=torch.int32, device=dev)
     mdf = torch.full((n,), float('nan'), dtype=torch.float64, device=dev)
@@ -75,12 +63,11 @@ def bundle_recognize(points, offsets, models, lin, label=None, runner_up=False):
     if n == 0 or points.shape[0] == 0:      # no launch: an empty tensor has no pointer
         return best, flip, mdf, second
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_bundle_recognize(
             points.data_ptr(), offsets.data_ptr(), n, models.data_ptr(),
             None if label is None else label.data_ptr(), M, K, lin_c, best.data_ptr(),
-            flip.data_ptr(), mdf.data_ptr(), second.data_ptr() if runner_up else None, stream),
-            'ttl_bundle_recognize')
+            flip.data_ptr(), mdf.data_ptr(), second.data_ptr() if runner_up else None,
+            _lib.stream_of(dev)), 'ttl_bundle_recognize')
     return best, flip, mdf, second
 
 

@@ -19,8 +19,6 @@ There is no NumPy fallback for the cost: like the rest of the product path it
 needs the library.  ``register`` takes another ``evaluate`` so that the driver
 can be run against a reference.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -70,18 +68,14 @@ def bundle_register_cost(fixed, moving, xf, lin):
     T = int(xf.shape[0])
     if not 1 <= T <= MAX_TRANSFORMS:
         raise ValueError(f'xf must have 1 .. {MAX_TRANSFORMS} transforms, not {T}')
-    lin = np.asarray(lin, np.float64)
-    if lin.size != 9:
-        raise ValueError(f'lin must be (3, 3), not {lin.shape}')
-    lin_c = (C.c_double * 9)(*lin.reshape(9))
+    lin_c = _lib.lin9(lin)
     row_min = torch.empty((T, A), dtype=torch.float64, device=dev)
     col_min = torch.empty((T, B), dtype=torch.float64, device=dev)
     cost = torch.empty(T, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_bundle_register_cost(
             fixed.data_ptr(), A, moving.data_ptr(), B, K, xf.data_ptr(), T, lin_c,
-            row_min.data_ptr(), col_min.data_ptr(), cost.data_ptr(), stream),
+            row_min.data_ptr(), col_min.data_ptr(), cost.data_ptr(), _lib.stream_of(dev)),
             'ttl_bundle_register_cost')
     return row_min, col_min, cost
 

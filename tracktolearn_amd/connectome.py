@@ -74,7 +74,7 @@ def assign_nodes(points, offsets, labels_dev, dims, lin, radius_mm, n_nodes):
         raise ValueError('labels_dev must be a contiguous int32 tensor of X * Y * Z words')
     launch_ragged('ttl_connectome_assign', points, offsets, dims,
                   before=(labels_dev.data_ptr(),),
-                  after=(int(n_nodes), (C.c_double * 9)(*lin), float(radius_mm),
+                  after=(int(n_nodes), _lib.lin9(lin), float(radius_mm),
                          (C.c_int32 * 3)(*(int(r) for r in reach)), node.data_ptr(),
                          length.data_ptr()))
     return node, length
@@ -86,11 +86,10 @@ def accumulate(node, length, n_nodes, count, length_q):
     ((N + 1, N + 1) int64, device), on the current stream of their device."""
     dev = node.device
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_connectome_accumulate(
             node.data_ptr(), None if length is None else length.data_ptr(),
-            int(node.shape[0]), int(n_nodes), count.data_ptr(), length_q.data_ptr(), stream),
-            'ttl_connectome_accumulate')
+            int(node.shape[0]), int(n_nodes), count.data_ptr(), length_q.data_ptr(),
+            _lib.stream_of(dev)), 'ttl_connectome_accumulate')
 
 
 def _lin_of(affine):
@@ -123,7 +122,7 @@ def sample_mean(points, offsets, volume, affine):
         return mean, weight
     launch_ragged('ttl_tract_sample_mean', points, offsets, volume.shape,
                   before=(volume.data_ptr(),),
-                  after=((C.c_double * 9)(*_lin_of(affine)), mean.data_ptr(),
+                  after=(_lib.lin9(_lin_of(affine)), mean.data_ptr(),
                          weight.data_ptr()))
     return mean, weight
 
@@ -134,10 +133,9 @@ def accumulate_metric(node, mean, n_nodes, scale, metric_q, metric_n):
     ((N + 1, N + 1) int64, device), on the current stream of their device."""
     dev = node.device
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_connectome_accumulate_metric(
             node.data_ptr(), mean.data_ptr(), int(node.shape[0]), int(n_nodes), float(scale),
-            metric_q.data_ptr(), metric_n.data_ptr(), stream),
+            metric_q.data_ptr(), metric_n.data_ptr(), _lib.stream_of(dev)),
             'ttl_connectome_accumulate_metric')
 
 

@@ -11,8 +11,6 @@
 // stays the same; the device-scope atomics are issued when the bundle changes and after
 // the wave's last row.  TTL_BUNDLE_PROFILE_NO_RUNS (a build-time switch for the
 // benchmark's variant, never set in the library) flushes after every row instead.
-#include <cmath>
-
 #include "ttl_internal.h"
 
 namespace {
@@ -27,10 +25,6 @@ typedef unsigned long long u64;
 // per wave: pre [64] doubles, res [3 nb] floats
 __host__ __device__ inline size_t profile_lds(int nb) { return (size_t)64 * 8 + (size_t)nb * 12; }
 
-__device__ __forceinline__ double quiet_nan() {
-    return __longlong_as_double(0x7ff8000000000000ll);
-}
-
 // body(row) for this wave's rows: the n rows are cut into contiguous ranges, one per wave
 // of the grid, so that rows sorted by bundle give a wave long runs of one bundle
 template <class F>
@@ -40,26 +34,6 @@ __device__ __forceinline__ void wave_row_range(int n, F body) {
     const long long wave = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const long long lo = wave * per, hi = lo + per < n ? lo + per : n;
     for (long long row = lo; row < hi; ++row) body((int)row);
-}
-
-// every point of the row finite: the same answer in every lane
-__device__ __forceinline__ bool row_is_finite(const float *__restrict__ p, long long L, int lane) {
-    bool bad = false;
-    for (long long j = lane; j < L; j += 64) {
-        const float *q = p + 3 * j;
-        bad |= !isfinite(q[0]) || !isfinite(q[1]) || !isfinite(q[2]);
-    }
-    return !__ballot(bad);
-}
-
-// d(a, m) = |lin (a - m)|: segment_mm's expression for the segment m -> a, without its
-// test for non-finite ends (a non-finite model entry gives a non-finite distance)
-__device__ __forceinline__ double distance_mm(const Lin &A, const float *a,
-                                              const float *__restrict__ m) {
-    const double e[3] = {(double)a[0] - (double)m[0], (double)a[1] - (double)m[1],
-                         (double)a[2] - (double)m[2]};
-    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
-    return sqrt((vx * vx + vy * vy) + vz * vz);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bundle_orient(
@@ -114,14 +88,15 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_orient(
         const float *m = model + (size_t)b * (size_t)K * 3;
         double d = 0.0, f = 0.0;
         for (int k = lane; k < K; k += 64) {
-            d += distance_mm(A, res + 3 * k, m + 3 * k);
-            f += distance_mm(A, res + 3 * (K - 1 - k), m + 3 * k);
+            const double mx = m[3 * k], my = m[3 * k + 1], mz = m[3 * k + 2];
+            d += distance_mm(A, res + 3 * k, mx, my, mz);
+            f += distance_mm(A, res + 3 * (K - 1 - k), mx, my, mz);
         }
-        const double D = wave_sum(d) / (double)K, F = wave_sum(f) / (double)K;
-        const bool flipped = F < D;             // strict: a tie or a NaN keeps the row
+        const Mdf w = mdf_of(wave_sum(d), wave_sum(f), K);
+        const bool flipped = w.flipped;
         if (lane == 0) {
             flip[row] = flipped ? 1 : 0;
-            mdf[row] = flipped ? F : D;
+            mdf[row] = w.delta;
         }
         if (b != run) {
             flush();
@@ -213,12 +188,6 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_profile(
     flush();
 }
 
-// a finite power of two in 2^-60 .. 2^60 (ttl_connectome_accumulate_metric's rule)
-bool bad_scale(double scale) {
-    int exponent = 0;
-    return !std::isfinite(scale) || std::frexp(scale, &exponent) != 0.5 || exponent - 1 < -60 ||
-           exponent - 1 > 60;
-}
 bool bad_shape(int32_t n, int32_t n_bundles, int32_t nb_points) {
     return n < 0 || n_bundles < 1 || n_bundles > TTL_PROFILE_MAX_BUNDLES || nb_points < 2 ||
            nb_points > TTL_PROFILE_MAX_POINTS;
@@ -234,17 +203,15 @@ int ttl_bundle_orient(const float *points, const int64_t *offsets, int32_t n,
     if (!points || !offsets || !bundle || !model || !lin || !flip || !mdf || !sum_q || !sum_n ||
         bad_shape(n, n_bundles, nb_points))
         return fail(TTL_ERR_INVALID, "ttl_bundle_orient: bad arguments");
-    if (bad_scale(scale))
+    if (ttl_detail_bad_scale(scale))
         return fail(TTL_ERR_INVALID,
                     "ttl_bundle_orient: scale must be a power of two in 2^-60 .. 2^60");
     if (n == 0) return TTL_OK;
     const size_t lds = wave_lds_bytes(profile_lds(nb_points));
-    LdsRoom room;
-    if (int rc = ttl_detail_reserve_lds((const void *)k_bundle_orient, lds, &room)) return rc;
-    if (!room.fits)
-        return fail(TTL_ERR_INVALID, "ttl_bundle_orient: %d stations exceed the LDS", nb_points);
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    if (int rc = ttl_detail_reserve_stations((const void *)k_bundle_orient, lds,
+                                             "ttl_bundle_orient", nb_points))
+        return rc;
+    const Lin A = ttl_detail_lin<Lin>(lin);
     hipLaunchKernelGGL(k_bundle_orient, dim3(ttl_detail_wave_grid(n, GRID_CAP)), dim3(BLOCK), lds,
                        (hipStream_t)hip_stream, points, (const long long *)offsets, n, bundle,
                        n_bundles, nb_points, model, A, scale, flip, mdf, (u64 *)sum_q,
@@ -261,16 +228,15 @@ int ttl_bundle_profile(const float *points, const int64_t *offsets, int32_t n,
     if (!points || !offsets || !bundle || !flip || !volume || !dims || !sum_q || !sum_qq ||
         !count || bad_shape(n, n_bundles, nb_points) || dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
         return fail(TTL_ERR_INVALID, "ttl_bundle_profile: bad arguments");
-    if (bad_scale(scale) || bad_scale(scale_sq))
+    if (ttl_detail_bad_scale(scale) || ttl_detail_bad_scale(scale_sq))
         return fail(TTL_ERR_INVALID,
                     "ttl_bundle_profile: scale and scale_sq must be powers of two in "
                     "2^-60 .. 2^60");
     if (n == 0) return TTL_OK;
     const size_t lds = wave_lds_bytes(profile_lds(nb_points));
-    LdsRoom room;
-    if (int rc = ttl_detail_reserve_lds((const void *)k_bundle_profile, lds, &room)) return rc;
-    if (!room.fits)
-        return fail(TTL_ERR_INVALID, "ttl_bundle_profile: %d stations exceed the LDS", nb_points);
+    if (int rc = ttl_detail_reserve_stations((const void *)k_bundle_profile, lds,
+                                             "ttl_bundle_profile", nb_points))
+        return rc;
     const WalkDims D{{dims[0], dims[1], dims[2]}};
     hipLaunchKernelGGL(k_bundle_profile, dim3(ttl_detail_wave_grid(n, GRID_CAP)), dim3(BLOCK), lds,
                        (hipStream_t)hip_stream, points, (const long long *)offsets, n, bundle,

@@ -4,13 +4,11 @@
 // another label: n * M * K * 2 float64 distances, the assignment step of RecoBundles /
 // QuickBundles.  A workgroup takes ROWS = 4 * ROWS_PER_WAVE consecutive rows; every wave
 // resamples its own rows into its LDS by the library's one resampler (resample_row over
-// CumReplayed, ttl_internal.h) and then all waves walk the models together: TILE_MODELS
-// models by at most TILE_STATIONS stations are staged in LDS station-major ([k][c][model],
-// padded so that the coalesced global read stores without a bank conflict), a lane owns one
-// model of the tile, reads the row's station as a broadcast and its own model's station
-// from consecutive banks, and every model station read feeds 2 * ROWS_PER_WAVE distances
-// (r_k and r_{K-1-k} of each row).  The two K-term sums of a (row, model) pair stay in the
-// lane's registers across the station chunks: k = 0, 1, .. K - 1 in that order.
+// CumReplayed, ttl_internal.h) and then all waves walk the models together by the
+// library's one tile walk (mdf_tile_walk, ttl_internal.h).  What this file
+// adds: the staging of a float tile of at most TILE_STATIONS stations (the coalesced
+// global read stores without a bank conflict in the padded tile) and the fold of a lane's
+// distances into the nearest model and the nearest of another label.
 #include "ttl_internal.h"
 
 namespace {
@@ -22,39 +20,15 @@ constexpr int WAVES = BLOCK / 64;
 #endif
 constexpr int ROWS_PER_WAVE = TTL_RECOGNIZE_ROWS_PER_WAVE;
 constexpr int ROWS = WAVES * ROWS_PER_WAVE;     // rows of a workgroup
-constexpr int TILE_MODELS = 64;                 // one model per lane
 constexpr int TILE_STATIONS = 32;               // stations of a tile, at most
-constexpr int TILE_PITCH = TILE_MODELS + 1;     // words per (k, c) line of the tile
 
 // per wave: pre [64] doubles, res [ROWS_PER_WAVE][3 nb] floats; behind the waves' parts the
-// tile [min(nb, TILE_STATIONS)][3][TILE_PITCH] floats
+// tile [min(nb, TILE_STATIONS)][3][MDF_TILE_PITCH] floats
 __host__ __device__ inline size_t recognize_wave_lds(int nb) {
     return (size_t)64 * 8 + (size_t)ROWS_PER_WAVE * (size_t)nb * 12;
 }
 __host__ __device__ inline size_t recognize_tile_lds(int nb) {
-    return (size_t)(nb < TILE_STATIONS ? nb : TILE_STATIONS) * 3 * TILE_PITCH * sizeof(float);
-}
-
-__device__ __forceinline__ double quiet_nan() {
-    return __longlong_as_double(0x7ff8000000000000ll);
-}
-
-// every point of the row finite: the same answer in every lane
-__device__ __forceinline__ bool row_is_finite(const float *__restrict__ p, long long L, int lane) {
-    bool bad = false;
-    for (long long j = lane; j < L; j += 64) {
-        const float *q = p + 3 * j;
-        bad |= !isfinite(q[0]) || !isfinite(q[1]) || !isfinite(q[2]);
-    }
-    return !__ballot(bad);
-}
-
-// d(a, m) = |lin (a - m)|, ttl_bundle_orient's expression
-__device__ __forceinline__ double distance_mm(const Lin &A, const float *a, double mx, double my,
-                                              double mz) {
-    const double e[3] = {(double)a[0] - mx, (double)a[1] - my, (double)a[2] - mz};
-    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
-    return sqrt((vx * vx + vy * vy) + vz * vz);
+    return (size_t)(nb < TILE_STATIONS ? nb : TILE_STATIONS) * 3 * MDF_TILE_PITCH * sizeof(float);
 }
 
 // The nearest model seen so far and the nearest of another label than its own.  second is
@@ -125,8 +99,7 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_recognize(
     char *base = wave_lds(per_wave);
     double *pre = reinterpret_cast<double *>(base);
     float *res = reinterpret_cast<float *>(base + 64 * 8);
-    float *tile = reinterpret_cast<float *>(base + (size_t)(WAVES - wave) *
-                                                       ((per_wave + 15) & ~(size_t)15));
+    float *tile = reinterpret_cast<float *>(shared_lds(per_wave));
     const long long row0 = (long long)blockIdx.x * ROWS + (long long)wave * ROWS_PER_WAVE;
 
     bool part[ROWS_PER_WAVE];
@@ -146,45 +119,27 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_recognize(
 #pragma unroll
     for (int r = 0; r < ROWS_PER_WAVE; ++r) near[r] = Nearest{0.0, quiet_nan(), -1, 0, 0};
 
-    for (int m0 = 0; m0 < M; m0 += TILE_MODELS) {
-        const int in_tile = min(TILE_MODELS, M - m0);
-        double d[ROWS_PER_WAVE], f[ROWS_PER_WAVE];
-#pragma unroll
-        for (int r = 0; r < ROWS_PER_WAVE; ++r) d[r] = f[r] = 0.0;
-        for (int k0 = 0; k0 < K; k0 += TILE_STATIONS) {
-            const int kc = min(TILE_STATIONS, K - k0), line = 3 * kc;
-            __syncthreads();                    // the tile before this one has been read
+    mdf_tile_walk<ROWS_PER_WAVE>(
+        A, res, K, M, tile, TILE_STATIONS, [](int) {},
+        [&](int m0, int in_tile, int k0, int kc) {
             // model ml's stations k0 .. k0 + kc are `line` consecutive floats: consecutive
-            // threads read consecutive floats and store TILE_PITCH words apart
+            // threads read consecutive floats and store MDF_TILE_PITCH words apart
+            const int line = 3 * kc;
             for (int e = threadIdx.x; e < in_tile * line; e += BLOCK) {
                 const int ml = e / line, j = e - ml * line;
-                tile[j * TILE_PITCH + ml] = models[((size_t)(m0 + ml) * K + k0) * 3 + j];
+                tile[j * MDF_TILE_PITCH + ml] = models[((size_t)(m0 + ml) * K + k0) * 3 + j];
             }
-            __syncthreads();
-            for (int kk = 0; kk < kc; ++kk) {
-                const float *t = tile + 3 * kk * TILE_PITCH + lane;
-                const double mx = t[0], my = t[TILE_PITCH], mz = t[2 * TILE_PITCH];
-                const int k = k0 + kk;
-#pragma unroll
-                for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-                    const float *row = res + (size_t)r * 3 * K;
-                    d[r] = d[r] + distance_mm(A, row + 3 * k, mx, my, mz);
-                    f[r] = f[r] + distance_mm(A, row + 3 * (K - 1 - k), mx, my, mz);
-                }
-            }
-        }
-        const int m = m0 + lane;
-        if (m < M) {                            // the lanes behind the last model read stale words
+        },
+        [&](int m0, const double(&d)[ROWS_PER_WAVE], const double(&f)[ROWS_PER_WAVE]) {
+            const int m = m0 + lane;
+            if (m >= M) return;                 // the lanes behind the last model read stale words
             const int lab = label ? label[m] : m;
 #pragma unroll
             for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-                const double D = d[r] / (double)K, F = f[r] / (double)K;
-                const bool flipped = F < D;     // strict: a tie or a NaN keeps the row
-                const double delta = flipped ? F : D;
-                if (delta == delta) nearest_add(near[r], delta, m, lab, flipped ? 1 : 0);
+                const Mdf w = mdf_of(d[r], f[r], K);
+                if (w.delta == w.delta) nearest_add(near[r], w.delta, m, lab, w.flipped ? 1 : 0);
             }
-        }
-    }
+        });
 #pragma unroll
     for (int r = 0; r < ROWS_PER_WAVE; ++r) {
         if (row0 + r >= n) continue;
@@ -212,13 +167,10 @@ int ttl_bundle_recognize(const float *points, const int64_t *offsets, int32_t n,
         return fail(TTL_ERR_INVALID, "ttl_bundle_recognize: bad arguments");
     if (n == 0) return TTL_OK;
     const size_t lds = wave_lds_bytes(recognize_wave_lds(nb_points)) + recognize_tile_lds(nb_points);
-    LdsRoom room;
-    if (int rc = ttl_detail_reserve_lds((const void *)k_bundle_recognize, lds, &room)) return rc;
-    if (!room.fits)
-        return fail(TTL_ERR_INVALID, "ttl_bundle_recognize: %d stations exceed the LDS",
-                    nb_points);
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    if (int rc = ttl_detail_reserve_stations((const void *)k_bundle_recognize, lds,
+                                             "ttl_bundle_recognize", nb_points))
+        return rc;
+    const Lin A = ttl_detail_lin<Lin>(lin);
     const unsigned grid = (unsigned)(((long long)n + ROWS - 1) / ROWS);
     hipLaunchKernelGGL(k_bundle_recognize, dim3(grid), dim3(BLOCK), lds, (hipStream_t)hip_stream,
                        points, (const long long *)offsets, n, models, label, n_models, nb_points,

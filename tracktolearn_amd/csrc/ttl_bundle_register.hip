@@ -2,10 +2,10 @@
 // ttl_hip.h, ttl_bundle_register_cost); part of libttl_hip.so.  For each of T
 // candidate transforms the bundle-minimum distance between A fixed and B moving lines of K
 // stations: A * B * K * 2 float64 distances per transform, reduced to the minimum of every
-// row and of every column of the MDF table.  The inner loop is ttl_bundle_recognize.hip's:
-// a workgroup takes ROWS = 4 * ROWS_PER_WAVE fixed lines of one transform, every wave keeps
-// its own lines' stations in its LDS, and all waves walk the moving set together through a
-// station-major LDS tile ([k][c][line]) in which a lane owns one moving line.  What is new:
+// row and of every column of the MDF table.  A workgroup takes ROWS = 4 * ROWS_PER_WAVE
+// fixed lines of one transform, every wave keeps its own lines' stations in its LDS, and all
+// waves walk the moving set together by the library's one tile walk (mdf_tile_walk,
+// ttl_internal.h).  What this file adds:
 // the tile holds float64 stations, transformed while they are staged (once per workgroup
 // instead of once per distance); a lane folds its distances into a running minimum per
 // fixed line (row_min, a plain store after a butterfly) and into the minimum over its
@@ -20,8 +20,7 @@ constexpr int BLOCK = TTL_BLOCK;
 constexpr int WAVES = BLOCK / 64;
 constexpr int ROWS_PER_WAVE = 2;
 constexpr int ROWS = WAVES * ROWS_PER_WAVE;     // fixed lines of a workgroup
-constexpr int TILE_LINES = 64;                  // one moving line per lane
-constexpr int TILE_PITCH = TILE_LINES + 1;      // doubles per (k, c) line of the tile
+constexpr int TILE_LINES = MDF_TILE_LINES, TILE_PITCH = MDF_TILE_PITCH;
 constexpr unsigned long long NONE = ~0ull;      // above the bits of every distance
 
 // stations of a tile: 32 as ttl_bundle_recognize while the workgroup stays within 64 KiB
@@ -40,18 +39,6 @@ __host__ __device__ inline size_t register_tile_lds(int nb) {
 }
 __host__ __device__ inline size_t register_shared_lds(int nb) {
     return register_tile_lds(nb) + (size_t)WAVES * 64 * 8 + (size_t)TILE_LINES * 4;
-}
-
-__device__ __forceinline__ double quiet_nan() {
-    return __longlong_as_double(0x7ff8000000000000ll);
-}
-
-// d(a, m) = |lin (a - m)|, ttl_bundle_orient's expression
-__device__ __forceinline__ double distance_mm(const Lin &A, const float *a, double mx, double my,
-                                              double mz) {
-    const double e[3] = {(double)a[0] - mx, (double)a[1] - my, (double)a[2] - mz};
-    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
-    return sqrt((vx * vx + vy * vy) + vz * vz);
 }
 
 __device__ __forceinline__ unsigned long long lower_bits(unsigned long long a,
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_register(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     char *base = wave_lds(per_wave);
     float *res = reinterpret_cast<float *>(base);
-    char *shared = base + (size_t)(WAVES - wave) * ((per_wave + 15) & ~(size_t)15);
+    char *shared = shared_lds(per_wave);
     double *tile = reinterpret_cast<double *>(shared);
     unsigned long long *colbuf =
         reinterpret_cast<unsigned long long *>(shared + register_tile_lds(K));
@@ -108,16 +95,13 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_register(
 #pragma unroll
     for (int r = 0; r < ROWS_PER_WAVE; ++r) rbits[r] = NONE;
 
-    for (int m0 = 0; m0 < B_lines; m0 += TILE_LINES) {
-        const int in_tile = min(TILE_LINES, B_lines - m0);
-        // the fold of the tile before this one is behind its barrier
-        if (threadIdx.x < TILE_LINES) bad[threadIdx.x] = 0;
-        double d[ROWS_PER_WAVE], f[ROWS_PER_WAVE];
-#pragma unroll
-        for (int r = 0; r < ROWS_PER_WAVE; ++r) d[r] = f[r] = 0.0;
-        for (int k0 = 0; k0 < K; k0 += tile_k) {
-            const int kc = min(tile_k, K - k0);
-            __syncthreads();                    // the tile before this one has been read
+    mdf_tile_walk<ROWS_PER_WAVE>(
+        A, res, K, B_lines, tile, tile_k,
+        [&](int) {
+            // the fold of the tile before this one is behind its barrier
+            if (threadIdx.x < TILE_LINES) bad[threadIdx.x] = 0;
+        },
+        [&](int m0, int in_tile, int k0, int kc) {
             // a thread takes a station: 3 consecutive floats in, 3 doubles out, 3 TILE_PITCH
             // doubles between the stations of consecutive threads
             for (int e = threadIdx.x; e < in_tile * kc; e += BLOCK) {
@@ -135,42 +119,31 @@ __global__ __launch_bounds__(BLOCK) void k_bundle_register(
                 }
                 if (nonfinite) bad[ml] = 1;     // every writer stores the same word
             }
-            __syncthreads();
-            for (int kk = 0; kk < kc; ++kk) {
-                const double *m = tile + 3 * kk * TILE_PITCH + lane;
-                const double mx = m[0], my = m[TILE_PITCH], mz = m[2 * TILE_PITCH];
-                const int k = k0 + kk;
+        },
+        [&](int m0, const double(&d)[ROWS_PER_WAVE], const double(&f)[ROWS_PER_WAVE]) {
+            const int j = m0 + lane;
+            unsigned long long cbits = NONE;
+            if (j < B_lines && !bad[lane]) {    // the lanes behind the last line read stale words
 #pragma unroll
                 for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-                    const float *row = res + (size_t)r * 3 * K;
-                    d[r] = d[r] + distance_mm(A, row + 3 * k, mx, my, mz);
-                    f[r] = f[r] + distance_mm(A, row + 3 * (K - 1 - k), mx, my, mz);
+                    const double delta = mdf_of(d[r], f[r], K).delta;
+                    if (part[r] && delta == delta) {
+                        const unsigned long long b =
+                            (unsigned long long)__double_as_longlong(delta);
+                        rbits[r] = lower_bits(rbits[r], b);
+                        cbits = lower_bits(cbits, b);
+                    }
                 }
             }
-        }
-        const int j = m0 + lane;
-        unsigned long long cbits = NONE;
-        if (j < B_lines && !bad[lane]) {        // the lanes behind the last line read stale words
+            colbuf[wave * 64 + lane] = cbits;
+            __syncthreads();
+            if (wave == 0) {
+                unsigned long long c = colbuf[lane];
 #pragma unroll
-            for (int r = 0; r < ROWS_PER_WAVE; ++r) {
-                const double D = d[r] / (double)K, F = f[r] / (double)K;
-                const double delta = F < D ? F : D;     // strict: a tie keeps D
-                if (part[r] && delta == delta) {
-                    const unsigned long long b = (unsigned long long)__double_as_longlong(delta);
-                    rbits[r] = lower_bits(rbits[r], b);
-                    cbits = lower_bits(cbits, b);
-                }
+                for (int w = 1; w < WAVES; ++w) c = lower_bits(c, colbuf[w * 64 + lane]);
+                if (j < B_lines && c != NONE) atomicMin(col_bits + (size_t)t * B_lines + j, c);
             }
-        }
-        colbuf[wave * 64 + lane] = cbits;
-        __syncthreads();
-        if (wave == 0) {
-            unsigned long long c = colbuf[lane];
-#pragma unroll
-            for (int w = 1; w < WAVES; ++w) c = lower_bits(c, colbuf[w * 64 + lane]);
-            if (j < B_lines && c != NONE) atomicMin(col_bits + (size_t)t * B_lines + j, c);
-        }
-    }
+        });
 #pragma unroll
     for (int r = 0; r < ROWS_PER_WAVE; ++r) {
         if (row0 + r >= A_lines) continue;
@@ -211,7 +184,7 @@ __global__ __launch_bounds__(64) void k_bundle_register_close(
     unsigned long long *col = col_bits + (size_t)t * B_lines;
     for (int j = lane; j < B_lines; j += 64) {
         unsigned long long b = col[j];
-        if (b == NONE) col[j] = b = 0x7ff8000000000000ull;
+        if (b == NONE) col[j] = b = QUIET_NAN_BITS;
         cols.add(__longlong_as_double((long long)b));
     }
     const double s = rows.of_wave() + cols.of_wave();
@@ -231,13 +204,10 @@ int ttl_bundle_register_cost(const float *fixed, int32_t n_fixed, const float *m
         nb_points > TTL_PROFILE_MAX_POINTS)
         return fail(TTL_ERR_INVALID, "ttl_bundle_register_cost: bad arguments");
     const size_t lds = wave_lds_bytes(register_wave_lds(nb_points)) + register_shared_lds(nb_points);
-    LdsRoom room;
-    if (int rc = ttl_detail_reserve_lds((const void *)k_bundle_register, lds, &room)) return rc;
-    if (!room.fits)
-        return fail(TTL_ERR_INVALID, "ttl_bundle_register_cost: %d stations exceed the LDS",
-                    nb_points);
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    if (int rc = ttl_detail_reserve_stations((const void *)k_bundle_register, lds,
+                                             "ttl_bundle_register_cost", nb_points))
+        return rc;
+    const Lin A = ttl_detail_lin<Lin>(lin);
     hipStream_t stream = (hipStream_t)hip_stream;
     HIP_TRY(hipMemsetAsync(col_min, 0xff, (size_t)n_xf * (size_t)n_moving * sizeof(double), stream));
     const dim3 grid((unsigned)((n_fixed + ROWS - 1) / ROWS), (unsigned)n_xf);

@@ -248,8 +248,7 @@ int ttl_connectome_assign(const float *points, const int64_t *offsets, int32_t n
     }
     if (n == 0) return TTL_OK;
     const WalkDims D{{dims[0], dims[1], dims[2]}};
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    const Lin A = ttl_detail_lin<Lin>(lin);
     hipLaunchKernelGGL(k_connectome_assign, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK), 0,
                        (hipStream_t)hip_stream, points, (const long long *)offsets, n, labels, D,
                        n_nodes, A, radius_mm * radius_mm, R, node, length);
@@ -277,10 +276,7 @@ int ttl_connectome_accumulate_metric(const int32_t *node, const double *mean, in
                                      int64_t *metric_n, void *hip_stream) {
     if (!node || !mean || !metric_q || !metric_n || n < 0 || bad_nodes(n_nodes))
         return fail(TTL_ERR_INVALID, "ttl_connectome_accumulate_metric: bad arguments");
-    int exponent = 0;
-    // a finite power of two: frexp gives exactly 0.5; (0.5, e) is 2^(e - 1)
-    if (!std::isfinite(scale) || std::frexp(scale, &exponent) != 0.5 || exponent - 1 < -60 ||
-        exponent - 1 > 60)
+    if (ttl_detail_bad_scale(scale))
         return fail(TTL_ERR_INVALID,
                     "ttl_connectome_accumulate_metric: scale must be a power of two in "
                     "2^-60 .. 2^60");

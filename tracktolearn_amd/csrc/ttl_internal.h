@@ -4,6 +4,7 @@
 #define TTL_INTERNAL_H
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 #include "ttl_hip.h"
@@ -405,6 +406,11 @@ __device__ __forceinline__ char *wave_lds(size_t per_wave) {
     extern __shared__ __align__(16) char lds_all[];
     return lds_all + (size_t)(threadIdx.x >> 6) * ((per_wave + 15) & ~(size_t)15);
 }
+// ... and the LDS the workgroup shares, behind the waves' parts
+__device__ __forceinline__ char *shared_lds(size_t per_wave) {
+    return wave_lds(per_wave) + (size_t)(TTL_BLOCK / 64 - (threadIdx.x >> 6)) *
+                                    ((per_wave + 15) & ~(size_t)15);
+}
 
 // float64 length of segment j of the float32 points p
 template <class I>
@@ -613,6 +619,85 @@ __device__ __forceinline__ bool sample_at(const double (&p)[3], const float *__r
     value = cy[0] * gx + cy[1] * f[0];
     return finite;
 }
+
+// The minimum-average-direct-flip distance between lines of K stations
+// (ttl_bundle_profile.hip, ttl_bundle_recognize.hip, ttl_bundle_register.hip), stated
+// once: include/ttl_hip.h, ttl_bundle_orient; DESIGN 3.19.
+constexpr unsigned long long QUIET_NAN_BITS = 0x7ff8000000000000ull;
+__device__ __forceinline__ double quiet_nan() {
+    return __longlong_as_double((long long)QUIET_NAN_BITS);
+}
+
+// every point of the row finite: the same answer in every lane
+__device__ __forceinline__ bool row_is_finite(const float *__restrict__ p, long long L, int lane) {
+    bool bad = false;
+    for (long long j = lane; j < L; j += 64) {
+        const float *q = p + 3 * j;
+        bad |= !isfinite(q[0]) || !isfinite(q[1]) || !isfinite(q[2]);
+    }
+    return !__ballot(bad);
+}
+
+// d(a, m) = |lin (a - m)|: segment_mm's expression for the segment m -> a, without its
+// test for non-finite ends (a non-finite station gives a non-finite distance)
+__device__ __forceinline__ double distance_mm(const Lin &A, const float *a, double mx, double my,
+                                              double mz) {
+    const double e[3] = {(double)a[0] - mx, (double)a[1] - my, (double)a[2] - mz};
+    const double vx = lin_row(A, 0, e), vy = lin_row(A, 1, e), vz = lin_row(A, 2, e);
+    return sqrt((vx * vx + vy * vy) + vz * vz);
+}
+
+// From the two K-term sums of a pair of lines, direct (d) and against one reversed (f)
+struct Mdf {
+    double delta;
+    bool flipped;
+};
+__device__ __forceinline__ Mdf mdf_of(double d, double f, int K) {
+    const double D = d / (double)K, F = f / (double)K;
+    const bool flipped = F < D;                 // strict: a tie or a NaN keeps the row
+    return Mdf{flipped ? F : D, flipped};
+}
+
+// The tile walk: every wave meets its ROWS_PER_WAVE rows of K stations in
+// `res` with all n_lines lines, MDF_TILE_LINES at a time, through the station-major LDS
+// tile [k][c][line] of MDF_TILE_PITCH words per (k, c), a lane owning one line.  The two
+// K-term sums of a (row, line) pair stay in registers across the chunks of at most tile_k
+// stations: k = 0, 1, .. K - 1 in that order.  Per tile, in every thread: begin(m0) before
+// its first barrier, stage(m0, in_tile, k0, kc) fills the tile between the two barriers of
+// a chunk, fold(m0, d, f) takes the sums of line m0 + lane.
+constexpr int MDF_TILE_LINES = 64;
+constexpr int MDF_TILE_PITCH = MDF_TILE_LINES + 1;
+template <int ROWS_PER_WAVE, class T, class Begin, class Stage, class Fold>
+__device__ __forceinline__ void mdf_tile_walk(const Lin &A, const float *res, int K, int n_lines,
+                                              const T *tile, int tile_k, Begin begin, Stage stage,
+                                              Fold fold) {
+    const int lane = threadIdx.x & 63;
+    for (int m0 = 0; m0 < n_lines; m0 += MDF_TILE_LINES) {
+        const int in_tile = min(MDF_TILE_LINES, n_lines - m0);
+        begin(m0);
+        double d[ROWS_PER_WAVE], f[ROWS_PER_WAVE];
+#pragma unroll
+        for (int r = 0; r < ROWS_PER_WAVE; ++r) d[r] = f[r] = 0.0;
+        for (int k0 = 0; k0 < K; k0 += tile_k) {
+            const int kc = min(tile_k, K - k0);
+            __syncthreads();                    // the tile before this one has been read
+            stage(m0, in_tile, k0, kc);
+            __syncthreads();
+            for (int kk = 0; kk < kc; ++kk) {
+                const T *t = tile + 3 * kk * MDF_TILE_PITCH + lane;
+                const double mx = t[0], my = t[MDF_TILE_PITCH], mz = t[2 * MDF_TILE_PITCH];
+                const int k = k0 + kk;
+#pragma unroll
+                for (int r = 0; r < ROWS_PER_WAVE; ++r) {
+                    const float *row = res + (size_t)r * 3 * K;
+                    d[r] = d[r] + distance_mm(A, row + 3 * k, mx, my, mz);
+                    f[r] = f[r] + distance_mm(A, row + 3 * (K - 1 - k), mx, my, mz);
+                }
+            }
+        }
+        fold(m0, d, f);
+    }
+}
 }  // namespace ttl_shared
 
 // ttl_resample.hip: the one place that reserves dynamic LDS.  Static + dynamic
@@ -627,6 +712,31 @@ struct LdsRoom {
     bool fits;
 };
 int ttl_detail_reserve_lds(const void *kernel, size_t dynamic, LdsRoom *room);
+// ... for the entry `who` of a kernel whose LDS grows with its nb_points stations
+inline int ttl_detail_reserve_stations(const void *kernel, size_t dynamic, const char *who,
+                                       int nb_points) {
+    LdsRoom room;
+    if (int rc = ttl_detail_reserve_lds(kernel, dynamic, &room)) return rc;
+    if (!room.fits)
+        return fail(TTL_ERR_INVALID, "%s: %d stations exceed the LDS", who, nb_points);
+    return TTL_OK;
+}
+
+// the kernels' Lin (ttl_shared's, or a file's own) of the ABI's 9 row-major doubles
+template <class L>
+inline L ttl_detail_lin(const double *lin) {
+    L A;
+    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    return A;
+}
+
+// a fixed-point scale is a finite power of two in 2^-60 .. 2^60: frexp gives exactly 0.5,
+// and (0.5, e) is 2^(e - 1)
+inline bool ttl_detail_bad_scale(double scale) {
+    int exponent = 0;
+    return !std::isfinite(scale) || std::frexp(scale, &exponent) != 0.5 || exponent - 1 < -60 ||
+           exponent - 1 > 60;
+}
 
 // records of the packed SH volume (padding records of the bricked order included)
 inline size_t ttl_detail_sh_records(const EnvParams &P) {

@@ -311,8 +311,7 @@ int ttl_tract_density(const ttl_density_desc *desc, const float *points, const i
         return fail(TTL_ERR_INVALID, "ttl_tract_density: wave_slots = %d exceeds the LDS of a workgroup",
                     wave_slots);
     const WalkDims D{{desc->dims[0], desc->dims[1], desc->dims[2]}};
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = desc->lin[i];
+    const Lin A = ttl_detail_lin<Lin>(desc->lin);
     const Maps M{desc->count, (u64 *)desc->length_q, (u64 *)desc->dec_q, desc->ends};
     char *ws = (char *)desc->workspace;
     unsigned *header = spill ? (unsigned *)ws : nullptr;

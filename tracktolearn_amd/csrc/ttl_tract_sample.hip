@@ -51,7 +51,7 @@ __global__ __launch_bounds__(BLOCK) void k_tract_sample_mean(
         sum_ws = wave_sum(sum_ws);
         if (lane == 0) {
             const bool scored = L >= 2 && sum_w > 0.0;
-            mean[row] = scored ? sum_ws / sum_w : __longlong_as_double(0x7ff8000000000000ll);
+            mean[row] = scored ? sum_ws / sum_w : quiet_nan();
             weight[row] = scored ? sum_w : 0.0;
         }
     });
@@ -68,8 +68,7 @@ int ttl_tract_sample_mean(const float *points, const int64_t *offsets, int32_t n
         return fail(TTL_ERR_INVALID, "ttl_tract_sample_mean: bad arguments");
     if (n == 0) return TTL_OK;
     const WalkDims D{{dims[0], dims[1], dims[2]}};
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    const Lin A = ttl_detail_lin<Lin>(lin);
     hipLaunchKernelGGL(k_tract_sample_mean, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK), 0,
                        (hipStream_t)hip_stream, points, (const long long *)offsets, n, volume, D,
                        A, mean, weight);

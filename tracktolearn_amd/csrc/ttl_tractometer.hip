@@ -393,8 +393,7 @@ int ttl_tractometer_classify(const float *points, const int64_t *offsets, int32_
     const WalkDims D{{dims[0], dims[1], dims[2]}};
     const Planes P{(const u64 *)head, (const u64 *)tail, (const u64 *)all, (const u64 *)any,
                    has_all, has_any};
-    Lin A;
-    for (int i = 0; i < 9; ++i) A.m[i] = lin[i];
+    const Lin A = ttl_detail_lin<Lin>(lin);
     hipLaunchKernelGGL(k_tractometer_classify, dim3(ttl_detail_wave_grid(n, 8192)), dim3(BLOCK),
                        0, (hipStream_t)hip_stream, points, (const long long *)offsets, n, D,
                        n_bundles, P, limits, A, bundle, (u64 *)connected);

@@ -98,7 +98,7 @@ def tract_density(points, offsets, dims, lin, count=None, length_q=None, dec_q=N
     words = dims[0] * dims[1] * dims[2]
     desc = _lib.DensityDesc()
     desc.dims = (C.c_int32 * 3)(*dims)
-    desc.lin = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
+    desc.lin = _lib.lin9(lin)
     for name, t, dtype, numel in (('count', count, torch.int32, words),
                                   ('length_q', length_q, torch.int64, words),
                                   ('dec_q', dec_q, torch.int64, 3 * words),
@@ -118,9 +118,9 @@ def tract_density(points, offsets, dims, lin, count=None, length_q=None, dec_q=N
     pts = points.to(torch.float32).contiguous()
     off = offsets.to(torch.int64).contiguous()
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(_lib.load().ttl_tract_density(C.byref(desc), pts.data_ptr(), off.data_ptr(), n,
-                                                 status.data_ptr(), stream), 'ttl_tract_density')
+                                                 status.data_ptr(), _lib.stream_of(dev)),
+                   'ttl_tract_density')
     return status
 
 

@@ -144,10 +144,9 @@ def launch_ragged(entry, points, offsets, dims, before=(), after=()):
     dims_c = (C.c_int32 * 3)(*(int(v) for v in dims))
     dev = pts.device
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(getattr(_lib.load(), entry)(
             pts.data_ptr(), off.data_ptr(), max(int(off.shape[0]) - 1, 0), *before, dims_c,
-            *after, stream), entry)
+            *after, _lib.stream_of(dev)), entry)
 
 
 def tract_coverage(points, offsets, dims, scores=None, threshold=0.5, visited=None):

@@ -33,7 +33,6 @@ the per-streamline ``bundle`` / ``pair`` arrays) that
 (``corner_voxels``) and the one device pass here: ``segment`` (classify, overlap,
 invalid) and its ``summary``, the single read-back, which names what it holds.
 """
-import ctypes as C
 import json
 import os
 from types import SimpleNamespace
@@ -41,6 +40,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from tracktolearn_amd import _lib
 from tracktolearn_amd.experiment.oracle_validator import (FILENAME, corner_voxels,
                                                           corner_voxels_from_rasmm,
                                                           launch_ragged, load_tractogram, pack,
@@ -372,11 +372,10 @@ def classify(points, offsets, data, lin):
     bundle = torch.empty(n, dtype=torch.int32, device=points.device)
     connected = torch.empty(n, dtype=torch.int64, device=points.device)
     if n:
-        lin_c = (C.c_double * 9)(*np.asarray(lin, np.float64).reshape(9))
         launch_ragged('ttl_tractometer_classify', points, offsets, data.dims, after=(
             data.n_bundles, data.head.data_ptr(), data.tail.data_ptr(), data.all.data_ptr(),
-            data.any.data_ptr(), data.has_all, data.has_any, data.limits.data_ptr(), lin_c,
-            bundle.data_ptr(), connected.data_ptr()))
+            data.any.data_ptr(), data.has_all, data.has_any, data.limits.data_ptr(),
+            _lib.lin9(lin), bundle.data_ptr(), connected.data_ptr()))
     return bundle, connected
 
 
